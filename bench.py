@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- throughput of the descriptor-track hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Primary workload (BASELINE.json configs[1]): ViT-B/16 224x224 bf16 encode, synthetic
@@ -10,7 +10,10 @@ per GPU through vsc_encoder_forward (patchify .. L2-normalised 512-d descriptors
 Frames shard across ranks with no data-path collective ("weak" scaling: per-GPU work
 fixed); value = frames of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  Extra objects:
+Prints ONE JSON line (rank 0).  A plain run does only what that headline needs: set up, --warmup steps, exactly --steps
+timed steps, the outputs (--dump-outputs DIR: the descriptors of the last timed step, DIR/descriptors.npy, float32
+[batch, 512], a seeded sample of rows past 64 MB; rank r > 0 writes descriptors_rank<r>.npy; inputs and weights are
+seeded, so runs with the same arguments see the same data), the line.  --full adds everything below; the --no-* options trim it.  Extra objects (--full):
   roofline      dominant kernel = the bf16 GEMM (gemm_bf16_v4_kernel: qkv/proj/fc1/fc2; _v3_ for the patch GEMM);
                 achieved = algorithmic FLOPs of those launches / their HIP-event time (events on the launch
                 stream, in a separate loop of --profile-steps steps right after the timed region: the headline
@@ -134,6 +137,11 @@ def parse():
     ap.add_argument("--force-sharded-search", action="store_true",
                     help="run the N > 1 search leg (RCCL all_gather + sweep) even with one rank; needs torchrun's env")
     ap.add_argument("--swin-batch", type=int, default=256)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: shader clock during the timed steps, the per-launch event loop "
+                         "(kernels{} / roofline), CPU baseline, fp16 operands, Swin, matching, ensemble, search (each trimmed by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the descriptors of the last timed step to DIR/descriptors.npy (float32; a seeded sample of rows past 64 MB)")
     return ap.parse_args()
 
 
@@ -696,7 +704,7 @@ def main():
         enc(frames)
     barrier()
     step_est = (time.perf_counter() - tw) / max(args.warmup, 1)   # sizes the clock probe below
-    sampler = ClockSampler() if rank == 0 else None
+    sampler = ClockSampler() if rank == 0 and args.full else None
     spin = None
     if sampler:
         sampler.__enter__()
@@ -726,7 +734,47 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(out).all()
-    # ---- a separate short loop with HIP events around every launch (on the launch stream): kernels{} and roofline
+    if args.dump_outputs:
+        # what a caller of the timed path receives: the descriptors of the last timed step (at most 64 MB over all ranks: past that, a
+        # fixed seeded sample of rows in ascending order)
+        desc = out.float().cpu().numpy()
+        cap = (64 << 20) // (world * desc.shape[1] * 4)
+        if len(desc) > cap:
+            desc = desc[np.sort(np.random.default_rng(0).choice(len(desc), cap, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "descriptors.npy" if rank == 0 else f"descriptors_rank{rank}.npy"), desc)
+    line = None
+    if rank == 0:
+        total_frames = args.steps * args.batch * world
+        line = {
+            "metric": "frames/s (ViT-B/16 224x224 encode -> L2-normalised 512-d descriptors)",
+            "value": round(total_frames / dt, 1), "unit": "frames/s", "n_gpus": world,
+            "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
+            **({"shared_device_plumbing_run": f"{world} ranks on {torch.cuda.device_count()} device(s), backend {args.backend}: exercises the N > 1 code path, "
+                                              "says nothing about scaling"} if args.share_device else {}),
+            "library": _lib.require_device().vsc_version().decode(),     # "... src <hash of csrc/* + include/vsc_hip.h>": which build was measured
+            "config": {"workload": f"{cfg.name} bf16 encode of {args.steps * args.batch} synthetic "
+                                   f"{cfg.image_size}x{cfg.image_size} frames per GPU in {args.steps} steps of {args.batch} "
+                                   "(BASELINE.json configs[1]: 100k frames)",
+                       "frames_per_gpu": args.steps * args.batch,
+                       "frames_per_step_per_gpu": args.batch, "encoder_chunk": args.max_batch,
+                       "lanes": args.lanes, "tokens": cfg.tokens,
+                       "gflop_per_frame": round(cfg.flops_per_frame() / 1e9, 2),
+                       "parallelism": f"frames sharded over {world} rank(s), no data-path collective"},
+            "model_tflops": round(cfg.flops_per_frame() * total_frames / dt / 1e12 / world, 1),
+        }
+    if not args.full:
+        if rank == 0:
+            enc.close()
+            os.write(result_fd, (json.dumps(line) + "\n").encode())
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # ---- --full: a separate short loop with HIP events around every launch (on the launch stream): kernels{} and roofline
     psteps = max(1, min(args.profile_steps, args.steps))
     enc.set_profiling(True)
     for _ in range(psteps):
@@ -743,7 +791,6 @@ def main():
             search_multi = {"error": f"{type(exc).__name__}: {exc}"}
 
     if rank == 0:
-        total_frames = args.steps * args.batch * world
         fpf = gemm_flops_per_frame(cfg)
         gemm_ms = sum(prof[k][0] for k in fpf)
         gemm_flops = sum(fpf.values()) * psteps * args.batch
@@ -768,24 +815,7 @@ def main():
                                            "bound": "hbm", "algorithmic_bytes_per_launch": round(att_bytes), "tb_per_s": round(tbs, 2),
                                            "frac_hbm": round(tbs / HBM_PEAK_TBS, 4), "hbm_peak_tb_per_s": HBM_PEAK_TBS})
         traffic, algo_bytes, traffic_src = gemm_traffic(cfg, min(args.max_batch, args.batch))
-        line = {
-            "metric": "frames/s (ViT-B/16 224x224 encode -> L2-normalised 512-d descriptors)",
-            "value": round(total_frames / dt, 1), "unit": "frames/s", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * dt / args.steps, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "bf16", "data": "synthetic",
-            **({"shared_device_plumbing_run": f"{world} ranks on {torch.cuda.device_count()} device(s), backend {args.backend}: exercises the N > 1 code path, "
-                                              "says nothing about scaling"} if args.share_device else {}),
-            "library": _lib.require_device().vsc_version().decode(),     # "... src <hash of csrc/* + include/vsc_hip.h>": which build was measured
-            "config": {"workload": f"{cfg.name} bf16 encode of {args.steps * args.batch} synthetic "
-                                   f"{cfg.image_size}x{cfg.image_size} frames per GPU in {args.steps} steps of {args.batch} "
-                                   "(BASELINE.json configs[1]: 100k frames)",
-                       "frames_per_gpu": args.steps * args.batch,
-                       "frames_per_step_per_gpu": args.batch, "encoder_chunk": args.max_batch,
-                       "lanes": args.lanes, "tokens": cfg.tokens,
-                       "gflop_per_frame": round(cfg.flops_per_frame() / 1e9, 2),
-                       "parallelism": f"frames sharded over {world} rank(s), no data-path collective"},
-            "model_tflops": round(cfg.flops_per_frame() * total_frames / dt / 1e12 / world, 1),
+        line.update({
             "roofline": {"bound": "mfma", "kernel": "gemm_bf16_v4_kernel (qkv/proj/fc1/fc2; the patch GEMM runs gemm_bf16_v3_kernel: same K loop, one tile per workgroup)",
                          "achieved": round(achieved, 1), "peak": BF16_PEAK_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(achieved / BF16_PEAK_TFLOPS, 4),
@@ -800,7 +830,7 @@ def main():
                                  "step on two streams (config.lanes); the event loop runs them back to back on one, so its kernel times "
                                  "are per kernel alone and their sum exceeds ms_per_step"},
             "kernels": per_class,
-        }
+        })
         clk = sampler.summary() if sampler else None
         if clk is None and spin is not None:
             clk = {}

@@ -1,9 +1,10 @@
-"""bench.py prints ONE JSON line with the keys the driver reads (short run: 2 steps, tiny secondaries)."""
+"""bench.py prints ONE JSON line with the keys the driver reads (short runs: 2 or 3 steps; --full with tiny secondaries)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 
 def test_bench_json_contract():
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "64", "--max-batch", "64",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--batch", "64", "--max-batch", "64",
            "--search-nq", "1024", "--search-nr", "50000", "--search-steps", "1", "--swin-batch", "8", "--no-cpu-baseline", "--ensemble-videos", "2"]
     # (8-frame Swin chunks would keep the GEMM launches in the 512-wide stage: VSC_SWIN_MLP512=1 takes the fused kernel as the full-size
     # bench does, so that the line's accounting of that kernel -- the qkv Linear inside it -- is what is checked here)
@@ -52,11 +53,30 @@ def test_bench_json_contract():
     assert en["value"] > 0 and en["encoder_bound_frames_per_s"] > en["value"] and set(en["models_frames_per_s"]) == {"swinv2_base_256", "vit_v68", "clip_vit_l14_224"}
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the run is set-up, warm-up, exactly --steps timed steps and the line; --dump-outputs writes the descriptors of
+    the last timed step."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "64", "--max-batch", "64",
+           "--dump-outputs", str(tmp_path / "out")]
+    out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.strip().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["unit"] == "frames/s" and d["higher_is_better"] is True and d["dtype"] == "bf16" and d["steps"] == 3 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] - 64 * 3 / (d["ms_per_step"] * 3e-3)) / d["value"] < 0.01
+    assert not {"roofline", "kernels", "cpu_baseline", "fp16_operands", "swin", "matching", "ensemble", "search"} & set(d)
+    assert os.listdir(tmp_path / "out") == ["descriptors.npy"]
+    desc = np.load(tmp_path / "out" / "descriptors.npy")
+    assert desc.dtype == np.float32 and desc.shape == (64, 512) and np.isfinite(desc).all()
+    assert np.allclose(np.linalg.norm(desc, axis=1), 1.0, atol=1e-4)          # L2-normalised rows
+
+
 def test_bench_stdout_is_one_line_with_a_process_group():
     """The N > 1 launch initialises RCCL, which prints a version banner on the C stdout at exit: stdout must still
     hold the JSON line and nothing else (exercised with world size 1 and the sharded-search leg forced on)."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", RANK="0", LOCAL_RANK="0", WORLD_SIZE="1")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-sharded-search", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--force-sharded-search", "--steps", "2", "--warmup", "1",
            "--batch", "64", "--max-batch", "64", "--search-nq", "1024", "--search-nr", "50000", "--search-steps", "1",
            "--no-swin", "--no-matching", "--no-cpu-baseline", "--no-ensemble"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
@@ -79,7 +99,7 @@ def test_bench_runs_with_world_size_two_on_one_gpu():
     scaling claim can be drawn from two ranks time-slicing one GPU (profiles/r06_two_ranks_one_gpu.txt holds a full-size run)."""
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29577",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--max-batch", "64",
+           os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "64", "--max-batch", "64",
            "--search-nq", "2048", "--search-nr", "100000", "--search-steps", "1", "--no-cpu-baseline", "--share-device", "--backend", "gloo"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

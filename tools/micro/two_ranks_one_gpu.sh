@@ -1,6 +1,6 @@
 set -x
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-B="--steps 5 --warmup 1 --search-nq 65536 --search-nr 1000000 --search-steps 1 --no-cpu-baseline"
+B="--full --steps 5 --warmup 1 --search-nq 65536 --search-nr 1000000 --search-steps 1 --no-cpu-baseline"
 # 1) RCCL with both ranks on device 0: expected to be refused
 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29561 bench.py --gpus 2 $B --share-device --backend nccl > gpurun_out/n2_nccl.json 2> gpurun_out/n2_nccl.err
 echo "nccl rc=$?"; tail -c 1500 gpurun_out/n2_nccl.err | grep -i "error\|duplicate\|invalid" | tail -5

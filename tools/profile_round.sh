@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 # --lanes 1: under the profiler the two chunks of a step run back to back, so a kernel's average duration is its own (with the
 # default two lanes the launches of the two chunks overlap and stretch each other: rocprofv3 then reports 300 us where the
 # kernel alone takes 207) -- the same serialisation bench.py applies to its per-launch event loop
-SHORT="--steps 3 --warmup 1 --profile-steps 3 --no-cpu-baseline --no-search --no-swin --no-matching --no-ensemble --no-fp16 --lanes 1"   # the ViT step and nothing else: every row of the summary is a ViT kernel
-python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+SHORT="--full --steps 3 --warmup 1 --profile-steps 3 --no-cpu-baseline --no-search --no-swin --no-matching --no-ensemble --no-fp16 --lanes 1"   # the ViT step and nothing else: every row of the summary is a ViT kernel
+python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
 tail -c 600 "$OUT/bench_default.json"
 (cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/stats" -o enc -- python $OLDPWD/bench.py $SHORT > "$OUT/bench_under_rocprof.json" 2> "$OUT/stats.err")
 (cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/stats_knn" -o knn -- python $OLDPWD/tools/knn_bench.py 65536 1000000 100 2 > "$OUT/knn_under_rocprof.txt" 2> "$OUT/stats_knn.err")
