@@ -283,6 +283,36 @@ int vsc_video_pair_max_f32(const float *q_dev, int64_t nq, const int32_t *q_vide
  * split) list held more than 1024 survivors).  Chosen like vsc_knn_ip_f32's path; VSC_PAIRMAX_PATH=exact|bf16 forces one. */
 int vsc_video_pair_max_last_path(void);
 
+/* Temporal-network (TN) alignment -- VCSL's `tn` (VSC22-Descriptor-Track-1st/infer/vcsl/vta.py:244-363, with `iou` :80-95),
+ * the alignment step of sscd_baseline's localize_and_verify -- over the matrices of vsc_pair_similarity_f32, one wave per pair.
+ * sims_dev: fp32 similarities (sims_len floats); pairs_host [n_pairs][3] = {element offset, q_rows, r_rows} (HOST memory):
+ * pair p is the row-major [q_rows, r_rows] matrix at sims_dev + offset.  Every element is used as s + bias (fp32 add).
+ * Outputs (device): boxes_dev int32 [n_pairs][max_path + 1][4] = {q from, r from, q to, r to} in acceptance order (unused
+ * slots 0), counts_dev int32 [n_pairs], maxsim_dev float [n_pairs][max_path + 1] = max of (s + bias) over the half-open box
+ * [q from:q to, r from:r to], minus bias (fp32; unused slots 0).
+ * Contract (the reference under numpy 2 / networkx 3.4, with one fixed tie rule):
+ *   nodes: 0 = source (-1,-1); 1 + q*top + k = (q, k-th best column of row q), top = min(top_k, r_rows), best = descending
+ *     biased similarity with ties to the LOWER column (the reference's np.argsort leaves tie order unspecified); sink = N-1.
+ *   regular edges (q_i, c) -> (q_j, r): q_i < q_j < q_i + max_step; C2 0 < col_j - col_i < max_step; C3 no column of the
+ *     running intermediate set of q_i (targets of its valid edges to earlier q_j) strictly between col_i and col_j; C4
+ *     sim_j >= float32(min_sim); weight sim_j; predecessor order (q_i, c) ascending.
+ *   sink edges: every node i < N-1 (source included) with q_sink > q_i, col_sink > col_i, both gaps <= max_step, weight 0
+ *     (a regular edge keeps its place, its weight becomes 0; new ones follow in node-id order).
+ *   longest path: dist(v) = first maximum over predecessors of dist(u) + w in fp32, (0, v) without predecessors or when
+ *     negative; the path ends at the first node of maximal dist in networkx's topological order (Kahn by generations,
+ *     generation 0 in node-id order, successors in (q_j, k) order, the sink edge last); traceback through stored predecessors.
+ *   rounds (at most max_path + 1): zero the path's edges; drop nodes 0 and N-1 (stop if nothing is left); score = fp32 sum
+ *     of the biased sims in path order; box = min / max of q and col if score > 0, else zeros; accept if
+ *     (double)score / ((dcol + dq) / 2) > min_sim (float64), min(dcol, dq) > min_length and the largest IoU ("+1" integer
+ *     areas, float64 division; 0 with no box yet) against the accepted boxes < max_iou.
+ *   A pair with an empty side yields no boxes.  Non-finite similarities are outside the contract.
+ * Limits: 1 <= top_k <= 16; max_step >= 1; (max_step - 1) * top_k <= 64 (predecessor bits per node); 0 <= max_path < 4096;
+ * min_length >= 0; q_rows <= 65536; r_rows <= 2^24.  Scratch: the search path's grow-only per-device buffers (40 bytes per
+ * graph node); vsc_search_release_scratch frees them.  Synchronises `stream` once (to upload the pair table). */
+int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias,
+                     int32_t max_step, int32_t top_k, int32_t max_path, double min_sim, int32_t min_length, double max_iou,
+                     int32_t *boxes_dev, int32_t *counts_dev, float *maxsim_dev, void *stream);
+
 /* sklearn.preprocessing.normalize(x) in place (l2, axis=1; zero rows untouched):
  * infer/extract_query_feats.py:178, infer/vsc/baseline/score_normalization.py:84-88. */
 int vsc_l2_normalize_f32(float *x_dev, int64_t n, int32_t d, void *stream);

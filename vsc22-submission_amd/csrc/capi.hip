@@ -155,6 +155,13 @@ extern "C" int vsc_debug_mlp512_timing(uint32_t *buf_dev) {
     return VSC_OK;
 }
 
+extern "C" int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias,
+                                int32_t max_step, int32_t top_k, int32_t max_path, double min_sim, int32_t min_length, double max_iou,
+                                int32_t *boxes_dev, int32_t *counts_dev, float *maxsim_dev, void *stream) {
+    return launch_tn_align(sims_dev, sims_len, pairs_host, n_pairs, bias, max_step, top_k, max_path, min_sim, min_length, max_iou,
+                           boxes_dev, counts_dev, maxsim_dev, (hipStream_t)stream);
+}
+
 extern "C" int vsc_merge_gather_bf16(const uint16_t *xb, uint16_t *out, int64_t frames, int32_t res, int32_t c,
                                      void *stream) {
     return launch_merge_gather(xb, out, frames, res, c, (hipStream_t)stream);

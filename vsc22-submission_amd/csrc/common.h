@@ -269,3 +269,11 @@ int launch_patchify_u8(const uint8_t *frames, uint16_t *patches, int64_t n, int 
                        const float *mean, const float *std, hipStream_t stream);
 int launch_f32_to_bf16(const float *src, uint16_t *dst, int64_t rows, int cols, int cols_pad,
                        hipStream_t stream);
+// grow-only device scratch of the search path (knn.hip), one set of slots per device; callers on one device are ordered
+// (one stream, or streams synchronised around the call)
+int search_scratch_get(int slot, size_t bytes, void **out);
+enum { SCRATCH_TN_TABLE = 19, SCRATCH_TN_NODES = 20 };   // slots of tn_align.hip (knn.hip uses 0-18)
+// temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h
+int launch_tn_align(const float *sims, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias, int max_step,
+                    int top_k, int max_path, double min_sim, int min_length, double max_iou, int32_t *boxes, int32_t *counts,
+                    float *maxsim, hipStream_t stream);

@@ -1367,6 +1367,7 @@ inline int blocks_for(int64_t items) {
 }  // namespace
 
 extern "C" int64_t vsc_search_release_scratch(void) { return scratch_release(); }
+int search_scratch_get(int slot, size_t bytes, void **out) { return scratch_get(slot, bytes, out); }
 
 // ---- per-phase HIP events of the last top-k call (bench.py: duration of the dominant kernel, on the caller's stream)
 static bool g_knn_profiling = false;

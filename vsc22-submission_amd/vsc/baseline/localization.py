@@ -6,9 +6,11 @@ Class names, constructor arguments and the `localize` / `localize_all` / `score`
   * similarity matrices: the reference multiplies `np.matmul(a, b.T)` per candidate on the host (:33-36); here the
     candidates of a `localize_all` call are laid out as one pair table over concatenated frame banks and computed by ONE
     `vsc_pair_similarity_f32` launch (`src.matching.pair_similarity_matrices`);
-  * the temporal alignment model is not rebuilt: it is the reference's own VCSL code (`vcsl.vta.build_vta_model`, CPU
+  * the temporal alignment model of the `VCSL*` classes is the reference's own VCSL code (`vcsl.vta.build_vta_model`, CPU
     graph search), imported late exactly as the reference does (:44) -- or any object with `forward_sim` passed as
-    `model=`.
+    `model=`, such as `vsc_hip.alignment.TnAlignment`.  The `HipTN*` classes need no VCSL: similarity, TN alignment and
+    MaxSim stay on the device (one pair-similarity launch and one `vsc_tn_align_f32` launch per `localize_all` call), and
+    only boxes and scores come back; they return what `VCSL*(..., model=TnAlignment(...))` returns.
 """
 from __future__ import annotations
 
@@ -119,4 +121,74 @@ class VCSLLocalizationCandidateScore(VCSLLocalization):
     """Score = the candidate's own (descriptor-track) score."""
 
     def score(self, candidate, match, box, similarity) -> float:
+        return candidate.score
+
+
+class HipTNLocalization(LocalizationWithMetadata):
+    """TN alignment on the device: per `localize_all` call one `vsc_pair_similarity_f32` launch over the candidates'
+    frame banks, one `vsc_tn_align_f32` launch over the resulting matrices (biased on the fly), then boxes (and MaxSim)
+    are copied back and become `Match` rows exactly as `VCSLLocalization._match` builds them."""
+
+    def __init__(self, queries, refs, similarity_bias=0.0, tn_max_step=10, tn_top_k=5, max_path=10, min_sim=0.2,
+                 min_length=5, max_iou=0.3):
+        from vsc_hip.alignment import TnAlignment
+        super().__init__(queries, refs)
+        self.model = TnAlignment(tn_max_step=tn_max_step, tn_top_k=tn_top_k, max_path=max_path, min_sim=min_sim,
+                                 min_length=min_length, max_iou=max_iou)
+        self.similarity_bias = similarity_bias
+
+    def _align(self, candidates: Sequence[CandidatePair]):
+        import torch
+
+        from src.matching import _Banks
+        from vsc_hip import _lib, ops
+        _lib.require_device()
+        dev = torch.device("cuda", torch.cuda.current_device())
+        banks = _Banks({c.query_id: self.queries[c.query_id].feature for c in candidates},
+                       {c.ref_id: self.refs[c.ref_id].feature for c in candidates},
+                       [(c.query_id, c.ref_id, c.score) for c in candidates])
+        if len(banks.q_bank) == 0 or len(banks.r_bank) == 0:
+            flat, offsets = torch.empty(0, dtype=torch.float32, device=dev), np.zeros(len(candidates) + 1, np.int64)
+        else:
+            flat, offsets = ops.pair_similarity(torch.from_numpy(banks.q_bank).to(dev),
+                                                torch.from_numpy(banks.r_bank).to(dev), banks.pairs)
+        boxes, counts, maxsim = self.model.align_pair_similarity(flat, offsets, banks.pairs, self.similarity_bias)
+        return boxes.cpu().numpy(), counts.cpu().numpy(), maxsim.cpu().numpy()
+
+    def _match(self, candidate: CandidatePair, box: Box, maxsim: np.float32) -> Match:
+        q_from, r_from, q_to, r_to = box
+        query, ref = self.queries[candidate.query_id], self.refs[candidate.ref_id]
+        segment = Match(candidate.query_id, candidate.ref_id, 0.0,
+                        query_start=query.get_timestamps(q_from)[0], query_end=query.get_timestamps(q_to)[1],
+                        ref_start=ref.get_timestamps(r_from)[0], ref_end=ref.get_timestamps(r_to)[1])
+        return segment._replace(score=self.score(candidate, maxsim))
+
+    def localize_all(self, candidates: Sequence[CandidatePair]) -> List[Match]:
+        candidates = list(candidates)
+        if not candidates:
+            return []
+        boxes, counts, maxsim = self._align(candidates)
+        found: List[Match] = []
+        for i, candidate in enumerate(candidates):
+            found += [self._match(candidate, tuple(int(v) for v in boxes[i, j]), maxsim[i, j]) for j in range(counts[i])]
+        return found
+
+    def localize(self, candidate: CandidatePair) -> List[Match]:
+        return self.localize_all([candidate])
+
+    def score(self, candidate: CandidatePair, maxsim: np.float32):
+        return 1.0
+
+
+class HipTNLocalizationMaxSim(HipTNLocalization):
+    """`VCSLLocalizationMaxSim` on the device: score = best (unbiased) similarity inside the half-open box."""
+
+    def score(self, candidate, maxsim):
+        return maxsim
+
+
+class HipTNLocalizationCandidateScore(HipTNLocalization):
+    """`VCSLLocalizationCandidateScore` on the device: score = the candidate's own score."""
+
+    def score(self, candidate, maxsim):
         return candidate.score

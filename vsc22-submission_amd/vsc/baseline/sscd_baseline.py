@@ -4,10 +4,11 @@ run by infer/eval.sh as `python3 -m vsc.baseline.sscd_baseline --query_features 
 
 On the HIP path: optional score normalisation, the exhaustive candidate search
 (`search`, sscd_baseline.py:89-103 -> CandidateGeneration.query) and, with ground truth, the
-descriptor-track micro-AP (:219-224).  `localize_and_verify` (:107-152) follows as in the reference when its
-VCSL package is importable: the per-candidate similarity matrices come from one HIP launch per batch
-(vsc.baseline.localization), the temporal alignment is the reference's own CPU code; without VCSL only
-candidates.csv is written (in the reference's format) and matches.csv is skipped with a log line.
+descriptor-track micro-AP (:219-224).  `localize_and_verify` (:107-152) follows: the per-candidate similarity matrices
+come from one HIP launch per batch (vsc.baseline.localization).  With `--alignment vcsl` (the default) the temporal
+alignment is the reference's own CPU code, and without its VCSL package only candidates.csv is written (in the
+reference's format) and matches.csv is skipped with a log line; with `--alignment hip` the TN alignment and MaxSim run on
+the device (vsc_tn_align_f32) and matches.csv is written without VCSL.
 """
 from __future__ import annotations
 
@@ -33,22 +34,40 @@ def search(queries: List[VideoFeature], refs: List[VideoFeature], retrieve_per_q
     return candidates
 
 
+ALIGNMENTS = ("vcsl", "hip")
+
+
 def localize_and_verify(queries: List[VideoFeature], refs: List[VideoFeature], candidates: List[CandidatePair],
-                        localize_per_query: float = 5.0, score_normalization: bool = False, model=None) -> List[Match]:
-    """sscd_baseline.py:107-152: the best `localize_per_query * len(queries)` candidates, aligned in batches of 512."""
+                        localize_per_query: float = 5.0, score_normalization: bool = False, model=None,
+                        alignment: str = "vcsl") -> List[Match]:
+    """sscd_baseline.py:107-152: the best `localize_per_query * len(queries)` candidates, aligned in batches of 512.
+    alignment="vcsl": the reference's VCSL TN model (or `model=`); "hip": the same TN alignment on the device
+    (vsc_tn_align_f32), no VCSL needed."""
     from vsc.baseline.localization import VCSLLocalizationCandidateScore, VCSLLocalizationMaxSim
+    if alignment not in ALIGNMENTS:
+        raise ValueError(f"alignment {alignment!r}: one of {ALIGNMENTS}")
     candidates = candidates[: int(len(queries) * localize_per_query)]
-    if score_normalization:
-        alignment = VCSLLocalizationMaxSim(queries, refs, model_type="TN", tn_max_step=5, min_length=4, concurrency=16,
-                                           similarity_bias=0.5, model=model)
+    if alignment == "hip":
+        if model is not None:
+            raise ValueError("model= selects a VCSL-interface model; alignment='hip' runs its own kernel")
+        from vsc.baseline.localization import HipTNLocalizationCandidateScore, HipTNLocalizationMaxSim
+        if score_normalization:
+            aligner = HipTNLocalizationMaxSim(queries, refs, similarity_bias=0.5, tn_max_step=5, min_length=4)
+        else:
+            from vsc.baseline.score_normalization import normalize_videos
+            aligner = HipTNLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), tn_max_step=5,
+                                                      min_length=4)
+    elif score_normalization:
+        aligner = VCSLLocalizationMaxSim(queries, refs, model_type="TN", tn_max_step=5, min_length=4, concurrency=16,
+                                         similarity_bias=0.5, model=model)
     else:
         from vsc.baseline.score_normalization import normalize_videos      # row-wise, a block of videos per device round trip
-        alignment = VCSLLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), model_type="TN",
-                                                   tn_max_step=5, min_length=4, concurrency=16, model=model)
+        aligner = VCSLLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), model_type="TN",
+                                                 tn_max_step=5, min_length=4, concurrency=16, model=model)
     matches: List[Match] = []
     logger.info("Aligning %s candidate pairs", len(candidates))
     for i in range(0, len(candidates), 512):
-        matches.extend(alignment.localize_all(candidates[i:i + 512]))
+        matches.extend(aligner.localize_all(candidates[i:i + 512]))
         logger.info("Aligned %d pairs of %d; %d predictions so far", min(i + 512, len(candidates)), len(candidates),
                     len(matches))
     return matches
@@ -80,7 +99,8 @@ def main(args) -> None:
     CandidatePair.write_csv(candidates, candidate_file)
     logger.info("Candidates: %s", candidate_file)
     try:
-        matches = localize_and_verify(queries, refs, candidates, score_normalization=bool(args.score_norm_features))
+        matches = localize_and_verify(queries, refs, candidates, score_normalization=bool(args.score_norm_features),
+                                      alignment=args.alignment)
     except ImportError as exc:
         logger.warning("matches.csv not written: %s", exc)
     else:
@@ -102,6 +122,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--output_path", required=True)
     ap.add_argument("--ground_truth")
     ap.add_argument("--overwrite", action="store_true")
+    ap.add_argument("--alignment", choices=ALIGNMENTS, default="vcsl",
+                    help="temporal alignment of matches.csv: the reference's VCSL package (vcsl) or the HIP kernel (hip)")
     return ap
 
 

@@ -97,6 +97,8 @@ SIGNATURES = {
     "vsc_video_pair_max_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32,
                                          c_int32, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                          c_void_p]),
+    "vsc_tn_align_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, ctypes.c_float, c_int32, c_int32, c_int32,
+                                   ctypes.c_double, c_int32, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_encoder_forward_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_swin_forward_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_debug_spin_ticks": (c_int32, [ctypes.c_uint64, c_void_p, c_void_p]),

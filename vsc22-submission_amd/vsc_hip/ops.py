@@ -211,6 +211,27 @@ def pair_similarity(q, r, pairs):
     return out, offsets
 
 
+def tn_align(sims, pairs, bias: float, max_step: int, top_k: int, max_path: int, min_sim: float, min_length: int,
+             max_iou: float):
+    """Temporal-network alignment (VCSL `tn`) of every matrix of a flat fp32 device tensor, one launch.
+    sims: flat float32 device tensor; pairs: int64 [n, 3] rows (element offset, q_rows, r_rows) on the host; every element is
+    used as s + bias.  -> (boxes int32 [n, max_path + 1, 4], counts int32 [n], maxsim float32 [n, max_path + 1]) on the
+    device: the first counts[p] boxes of pair p in acceptance order, maxsim = max of (s + bias) over the half-open box
+    minus bias.  Contract and limits: vsc_tn_align_f32 in include/vsc_hip.h."""
+    import numpy as np
+    lib = _rd()
+    sims = _dev(sims, torch.float32).reshape(-1)
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 3))
+    n = pairs.shape[0]
+    boxes = torch.empty((n, max_path + 1, 4), dtype=torch.int32, device=sims.device)
+    counts = torch.empty(n, dtype=torch.int32, device=sims.device)
+    maxsim = torch.empty((n, max_path + 1), dtype=torch.float32, device=sims.device)
+    check(lib.vsc_tn_align_f32(ptr(sims) if sims.numel() else None, sims.numel(), pairs.ctypes.data, n, float(bias),
+                               int(max_step), int(top_k), int(max_path), float(min_sim), int(min_length), float(max_iou),
+                               ptr(boxes), ptr(counts), ptr(maxsim), current_stream()))
+    return boxes, counts, maxsim
+
+
 def video_pair_max(q, q_video, n_q_videos: int, r, r_video, n_r_videos: int, threshold: float, capacity: int = 1 << 20):
     """Largest frame score above ``threshold`` per (query video, reference video).
     q [nq, d], r [nr, d] float32; q_video [nq], r_video [nr] int32 video index of every row.
