@@ -313,6 +313,49 @@ int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const int64_t *pai
                      int32_t max_step, int32_t top_k, int32_t max_path, double min_sim, int32_t min_length, double max_iou,
                      int32_t *boxes_dev, int32_t *counts_dev, float *maxsim_dev, void *stream);
 
+/* Query view preprocessing -- the reference's image_process (VSC22-Descriptor-Track-1st/infer/src/image_preprocess.py:252-275,
+ * applied to every query video by infer/src/dataset.py:82-88): the two per-video maps its border / split decisions read, and the
+ * crop + resize of every view.  The decisions themselves run on the host (src/image_preprocess.py).  frames_dev: uint8
+ * [n][h][w][3] (RGB, row-major) on the device.
+ *
+ * Variance map, image_preprocess.py:255-256 (np.stack(frames).var(axis=0).sum(-1)), bit-identical to numpy: out_dev float64
+ * [h][w]; per channel mean = (frame-order sum, exact) / n, var = (frame-order sum of (x - mean)^2, each product rounded, no FMA)
+ * / n, all fp64; out = (var0 + var1) + var2.  Limits: 1 <= n < 2^24, h * w <= 2^28. */
+int vsc_frame_var_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, double *out_dev, void *stream);
+
+/* Canny edge counts, image_preprocess.py:263-264 (cv2.Canny(frame, low, high) > 0 over the sampled frames): out_dev uint16
+ * [h][w] = the number of frames frames_dev[idx_host[j]], j < m, where Canny marks the pixel an edge (idx_host: HOST memory, each
+ * in [0, n)).  Contract: OpenCV 4.x's non-IPP Canny for 3-channel 8-bit input with the L1 gradient, restated from its algorithm
+ * (not pinned against cv2; tests/canny_cpu.py is the same contract in numpy):
+ *   Sobel 3x3 per channel, CV_16S, replicated border: dx = right - left column (1 2 1), dy = bottom - top row (1 2 1);
+ *   per pixel the channel with the largest |dx| + |dy| (a tie goes to the lower channel), its dx, dy and m = |dx| + |dy|;
+ *   only m > floor(low) enters non-maximum suppression, in fixed point: TG22 = 13573, x = |dx|, y = |dy| << 15,
+ *     y < x * TG22: horizontal, kept if m > left && m >= right;  y > x * TG22 + (x << 16): vertical, m > up && m >= down;
+ *     else diagonal with s = (dx ^ dy) < 0 ? -1 : 1, kept if m > prev_row[j - s] && m > next_row[j + s];
+ *     magnitude outside the image counts as 0;
+ *   a kept pixel is strong if m > floor(high), else weak; hysteresis: a weak or strong pixel is an edge exactly when its
+ *   8-connected component of weak | strong pixels holds a strong pixel.
+ * Hysteresis is union-find connected components in a fixed number of launches (five per chunk of up to 32 frames, no host
+ * polling); labels may differ from run to run, the output does not.  Limits: h * w <= 2^25, 0 <= low <= high < 4096, m <= 65535.
+ * Scratch: the search path's grow-only per-device buffers (8 bytes per pixel of a chunk). */
+int vsc_canny_count_u8(const uint8_t *frames_dev, int64_t n, const int32_t *idx_host, int32_t m, int32_t h, int32_t w, double low,
+                       double high, uint16_t *out_dev, void *stream);
+
+/* Crop + bicubic resize of every view, PIL-exact: the reference resizes each view's frames with Resize([S, S], BICUBIC)
+ * (infer/extract_query_feats.py:110-128) after image_process cut them (image_preprocess.py:267-271).  boxes_host int32 [k][4] =
+ * {y0, y1, x0, x1} (HOST memory, 0 <= y0 < y1 <= h, 0 <= x0 < x1 <= w); out_dev uint8 [k * n][size][size][3]:
+ * out[b * n + i] == Image.fromarray(frame_i[y0:y1, x0:x1]).resize((size, size), Image.BICUBIC), bit for bit.  That is Pillow's
+ * 8-bit resample: bicubic a = -0.5, support 2 x max(1, in / out); coefficients in fp64 per (in length, out length), normalised,
+ * rounded half away from zero to 22 fractional bits; horizontal pass first, then vertical, each clipped to 0..255 -- except, as
+ * in Pillow 12's Image.resize, a crop more than 100 times taller than wide that shrinks in height: vertical first; taps clamp to
+ * the CROP's edges (not the frame's: crop-then-resize differs from PIL's box= resize of the whole frame).  A whole-frame box is
+ * src/dataset.py:vit_transform_u8(size, size).  Coefficient tables are built on the host and cached on the device for the life of
+ * the process, never freed (a synchronous upload the first time a (device, length, size) triple is seen; ~21 KiB per length at
+ * 1080p, at most ~150 MiB per size even if every length up to 4096 occurs).  Limits: 1 <= size <= 4096; n * h_crop * size and n * size^2 < 2^31.
+ * Scratch: the search path's grow-only per-device buffers (n * max crop height * size * 3 bytes). */
+int vsc_resize_bicubic_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, const int32_t *boxes_host, int32_t k,
+                          int32_t size, uint8_t *out_dev, void *stream);
+
 /* sklearn.preprocessing.normalize(x) in place (l2, axis=1; zero rows untouched):
  * infer/extract_query_feats.py:178, infer/vsc/baseline/score_normalization.py:84-88. */
 int vsc_l2_normalize_f32(float *x_dev, int64_t n, int32_t d, void *stream);

@@ -162,6 +162,20 @@ extern "C" int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const i
                            boxes_dev, counts_dev, maxsim_dev, (hipStream_t)stream);
 }
 
+extern "C" int vsc_frame_var_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, double *out_dev, void *stream) {
+    return launch_frame_var_u8(frames_dev, n, h, w, out_dev, (hipStream_t)stream);
+}
+
+extern "C" int vsc_canny_count_u8(const uint8_t *frames_dev, int64_t n, const int32_t *idx_host, int32_t m, int32_t h, int32_t w,
+                                  double low, double high, uint16_t *out_dev, void *stream) {
+    return launch_canny_count_u8(frames_dev, n, idx_host, m, h, w, low, high, out_dev, (hipStream_t)stream);
+}
+
+extern "C" int vsc_resize_bicubic_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, const int32_t *boxes_host, int32_t k,
+                                     int32_t size, uint8_t *out_dev, void *stream) {
+    return launch_resize_bicubic_u8(frames_dev, n, h, w, boxes_host, k, size, out_dev, (hipStream_t)stream);
+}
+
 extern "C" int vsc_merge_gather_bf16(const uint16_t *xb, uint16_t *out, int64_t frames, int32_t res, int32_t c,
                                      void *stream) {
     return launch_merge_gather(xb, out, frames, res, c, (hipStream_t)stream);

@@ -4,13 +4,18 @@
         --models swinv2_base_256:swin_ref:ckpt/swinv2_v115.pth swinv2_base_256:swin_ref:ckpt/swinv2_v107.pth \
                  swinv2_base_256:swin_ref:ckpt/swinv2_v106.pth vit_v68:timm_vit:ckpt/vit_v68.pth \
         --pca_model ckpt/pca_model.pkl --zip_prefix ../data/jpg_zips --input_file ../data/meta/test/query_ids.txt \
-        --norm_refs outputs/train_refs.npz --output_dir outputs [--video_scores video_scores.csv]
+        --norm_refs outputs/train_refs.npz --output_dir outputs [--video_scores video_scores.csv] [--preprocess hip]
 
 Outputs, as the reference: ``<output_dir>/<model name>/<split>_query.npz`` per backbone (:238-245) and
 ``<output_dir>/<split>_query_sn.npz`` after query score normalisation (:247-252).  The video-score gate
 (CLIP ViT-L/14 [CLS] features -> ``MS`` head, :163-174) runs on the HIP path when ``--clip_checkpoint`` and
 ``--vsm_checkpoint`` (the state dicts torch2scripts.py traces) are given; otherwise scores are read from
-``--video_scores`` (csv: video_id,score) and every video passes when neither is given."""
+``--video_scores`` (csv: video_id,score) and every video passes when neither is given.
+
+``--preprocess hip`` adds the reference's query preprocessing (infer/src/image_preprocess.py ``image_process``, applied by
+infer/src/dataset.py:82-88): static borders are cropped and stacked compositions split into views on the GPU
+(src/image_preprocess.py), and every view's frames are encoded -- k views of n frames give k * n descriptor rows, timestamps
+repeated view-major.  The video-score gate keeps the original frames.  The default, ``none``, encodes whole frames."""
 from __future__ import annotations
 
 import argparse
@@ -26,7 +31,8 @@ import torch
 from src.dataset import CLIP_MEAN, CLIP_STD, clip_transform_u8, vit_transform_u8
 from src.matching import calclualte_low_var_dim
 from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
-from src.query_pipeline import VideoScorer, run_query_videos
+from src.image_preprocess import HipViews
+from src.query_pipeline import RAW_KEY, VideoScorer, run_query_videos
 from src.query_postprocess import HipPCA, SCORE_THRESHOLD
 from vsc.baseline.score_normalization import query_score_normalize
 from vsc.metrics import Dataset
@@ -40,10 +46,14 @@ class QueryVideos(torch.utils.data.Dataset):
     <prefix>/<vid[-2:]>/<vid>.zip decoded once and resized per input size (bicubic, as vit_transform / the CLIP
     transform do).  Frames stay uint8 until they are on the GPU: ToTensor + Normalize run inside the encoders'
     patchify kernels.  Decoding is the slow part of the whole pipeline, so main() reads this through a DataLoader with
-    worker processes, as the reference does (extract_query_feats.py:138-140)."""
+    worker processes, as the reference does (extract_query_feats.py:138-140).
+    ``preprocess="hip"``: the frames stay at the zip's own resolution, uint8 [S,H,W,3] under ``RAW_KEY`` (run_query_videos cuts
+    and resizes the views on the GPU), next to the unchanged CLIP frames.  A video whose frames differ in size is resized here as
+    with ``none``: the reference's preprocessing fails on it (np.stack) and leaves it unprocessed."""
 
-    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False):
-        self.zip_prefix = zip_prefix
+    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False, preprocess="none"):
+        assert preprocess in ("none", "hip"), preprocess
+        self.zip_prefix, self.preprocess = zip_prefix, preprocess
         self.video_ids = [v for v in video_ids if os.path.exists(self._path(v))]
         self.transforms = {s: vit_transform_u8(s, s) for s in sizes}
         if with_clip:
@@ -65,11 +75,16 @@ class QueryVideos(torch.utils.data.Dataset):
         # store_features to concatenate them
         n = len(images)
         stamps = np.stack([np.arange(n, dtype=np.float32), np.arange(n, dtype=np.float32) + 1.0], axis=1)
+        if self.preprocess == "hip" and len({im.size for im in images}) == 1:
+            frames = {RAW_KEY: torch.from_numpy(np.stack([np.asarray(im, dtype=np.uint8) for im in images]))}
+            if VideoScorer.KEY in self.transforms:
+                frames[VideoScorer.KEY] = torch.stack([self.transforms[VideoScorer.KEY](im) for im in images])
+            return vid, frames, stamps
         return vid, {s: torch.stack([t(im) for im in images]) for s, t in self.transforms.items()}, stamps
 
 
-def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0):
-    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip)
+def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0, preprocess="none"):
+    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip, preprocess)
     kw = {"prefetch_factor": 4} if workers > 0 else {}
     return torch.utils.data.DataLoader(data, batch_size=1, shuffle=False, num_workers=workers, collate_fn=lambda b: b[0], **kw)
 
@@ -100,9 +115,9 @@ def main(args):
         from src.model_zoo import _state_dict      # a plain / training checkpoint or the TorchScript archive the reference ships (vsm.torchscript.pt)
         scorer = VideoScorer(clip, VideoScoreHead("vsm_roberta_base", from_reference_state(_state_dict(args.vsm_checkpoint))), device)
     videos = zip_videos(vids, args.zip_prefix, sorted({size for _, size in encoders}), with_clip=scorer is not None,
-                        workers=args.workers)
+                        workers=args.workers, preprocess=args.preprocess)
     finals, per_model = run_query_videos(videos, encoders, pca.transform, scores, device, score_threshold=args.score_threshold,
-                                         scorer=scorer)
+                                         scorer=scorer, views=HipViews(device) if args.preprocess == "hip" else None)
     for i, (_, _, path) in enumerate(specs):
         key = os.path.split(path)[-1].split(".")[0]
         os.makedirs(os.path.join(args.output_dir, key), exist_ok=True)
@@ -133,6 +148,8 @@ def build_parser():
     ap.add_argument("--precision", default=DEFAULT_PRECISION, choices=["fp16", "bf16"],
                     help="16-bit type of the encoders' MFMA operands (same speed; fp16 = 8 x smaller rounding, DESIGN.md 3a)")
     ap.add_argument("--workers", type=int, default=6, help="decode / resize worker processes (the reference uses 6)")
+    ap.add_argument("--preprocess", default="none", choices=["none", "hip"],
+                    help="hip: crop static borders and split stacked views on the GPU before encoding (the reference's image_process)")
     return ap
 
 

@@ -1,0 +1,205 @@
+"""Query frame preprocessing: static-border removal and split views (reference: infer/src/image_preprocess.py, ``image_process``
+and the ``remove_edges`` / ``split_imgs`` / ``clean_imgs`` it calls; applied to every query video by infer/src/dataset.py:82-88).
+
+The reference crops and splits the frames themselves.  Here the decisions are taken on the two per-video maps they depend on --
+the per-pixel variance over all frames and the Canny edge frequency over up to 20 sampled frames -- and come out as boxes
+``(y0, y1, x0, x1)`` in frame coordinates, in the reference's view order.  The GPU computes the maps (``detect_views``:
+vsc_frame_var_u8 and vsc_canny_count_u8) and cuts and resizes the views (vsc_resize_bicubic_u8); only the decisions run here.
+
+Every threshold, scan order and quirk is the reference's, on the same numpy slices of the same maps, so the floating-point
+results match too.  Where the reference raises inside its ``try`` (frames of different sizes, a sample index past the last
+frame), the video is unchanged."""
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+
+Box = Tuple[int, int, int, int]          # y0, y1, x0, x1 (half-open, frame coordinates)
+
+MIN_FRAMES = 5          # clean_imgs: fewer frames -> unchanged
+CANNY_SAMPLES = 20      # image_process: Canny runs on ~20 evenly spaced frames of a longer video
+CANNY_LOW, CANNY_HIGH = 50, 400
+MIN_SIDE = 20           # clean_imgs: a cut under 20 px on a side leaves the region as it was
+MIN_VIEW = 80           # clean_imgs -> split_imgs(min_size=80)
+GAP = 5                 # split_imgs: width of the static band that separates two stacked views
+
+
+def canny_frames(n: int) -> Optional[List[int]]:
+    """Indices of the frames the reference runs Canny on (image_process:259-261): all of them up to 20, else the float range
+    ``np.arange(0, n, n / 20)`` rounded half to even.  Should rounding of the float range give a 21st sample that rounds to ``n``,
+    the reference indexes past its list and its ``try`` returns the video unchanged -- None here.  (numpy 2.2 gives exactly 20
+    samples for every n from 21 to 200 000.)"""
+    if n <= CANNY_SAMPLES:
+        return list(range(n))
+    idx = [int(np.round(i)) for i in np.arange(0, n, n / CANNY_SAMPLES)]
+    return None if idx[-1] >= n else idx
+
+
+def _static_side(var_p, edge_p, edge_at) -> bool:
+    """remove_edges: the band beyond a candidate edge line is a static border"""
+    level = np.median(var_p) + var_p.mean()
+    calm = edge_p.mean() < 0.0225
+    return bool((level < 75 and calm) or (level < 250 and calm and edge_at > 0.65))
+
+
+def _trim(var_p, edge_p, size: int) -> Tuple[int, int]:
+    """remove_edges along one axis: (first, end) kept, from the per-line variance and edge profiles of the region"""
+    lines = [i for i in np.where(edge_p > 0.125 + edge_p.mean())[0] if i not in (0, size - 1)]
+    first, end = 0, size
+    for i in lines:
+        if i - first < 5:
+            continue
+        extra = round((i - first) * 0.3)
+        if _static_side(var_p[first:i - extra], edge_p[first:i - extra], edge_p[i]):
+            first = i + 1
+    for i in reversed(lines):
+        if end - i < 5:
+            continue
+        extra = round((end - i) * 0.3)
+        if _static_side(var_p[i + extra:end], edge_p[i + extra:end], edge_p[i]):
+            end = i
+    return first, end
+
+
+def _borders(var, avg) -> Tuple[int, int, int, int]:
+    """remove_edges -> the kept (y0, y1, x0, x1) inside the region"""
+    threshold = min(max(np.quantile(avg, 0.95), 0.2), avg.mean() + 0.35)
+    edges = (avg > threshold).astype(np.float32)
+    h, w = var.shape
+    y0, y1 = _trim(var.mean(1), edges.mean(1), h)
+    x0, x1 = _trim(var.mean(0), edges.mean(0), w)
+    return y0, y1, x0, x1
+
+
+def _bands(profile, size: int, start: int, min_size: int) -> Tuple[List[Tuple[int, int]], int]:
+    """split_imgs' scan of one axis: pieces that end at a static band, and where the scan's last piece started"""
+    half = GAP // 2
+    pieces, inside = [], False
+    # profile[i:i + GAP].mean() for every i at once, in numpy's own order for a 5-element sum (sequential) and division
+    p = np.asarray(profile, dtype=np.float64)
+    n = max(size - GAP, 0)
+    levels = ((((p[0:n] + p[1:n + 1]) + p[2:n + 2]) + p[3:n + 3]) + p[4:n + 4]) / GAP
+    for i, level in enumerate(levels.tolist()):
+        if not inside and (level > 0.1 or i - start > 50):
+            inside = True
+        elif inside and level < 0.1:
+            if i + half - start > min_size:
+                pieces.append((start, i + half))
+            inside = False
+            start = i + half
+    return pieces, start
+
+
+def _line_cuts(lines: Sequence[int], size: int, min_size: int) -> List[Tuple[int, int]]:
+    """split_imgs' cut_h / cut_w: pieces between strong edge lines, from the far end back"""
+    pieces, end = [], size
+    for i in lines:
+        if end - i > min_size:
+            pieces.append((i, end))
+            end = i
+    if pieces and end > min_size:
+        pieces.append((0, end))
+    return pieces
+
+
+def _split(var, avg, min_size: int) -> Optional[List[Box]]:
+    """split_imgs -> boxes inside the region, or None when it stays whole"""
+    h, w = var.shape
+    rows, start = _bands(var.mean(1), h, 0, min_size)
+    if rows or start != 0:
+        if h - start > min_size:
+            rows.append((start, h))
+        if rows:
+            return [(a, b, 0, w) for a, b in rows]
+    # the reference's width scan starts from where the height scan left `start`
+    cols, start = _bands(var.mean(0), w, start, min_size)
+    if cols or start != 0:
+        if w - start > min_size:
+            cols.append((start, w))
+        if cols:
+            return [(0, h, a, b) for a, b in cols]
+    threshold = min(max(np.quantile(avg, 0.95), 0.2), avg.mean() + 0.3)
+    edges = (avg > threshold).astype(np.float32)
+    level = 0.45 + edges.mean()
+    row_lines = list(np.where(edges.mean(1) > level)[0])[::-1]
+    col_lines = list(np.where(edges.mean(0) > level)[0])[::-1]
+    by_rows = lambda: [(a, b, 0, w) for a, b in _line_cuts(row_lines, h, min_size)]     # noqa: E731
+    by_cols = lambda: [(0, h, a, b) for a, b in _line_cuts(col_lines, w, min_size)]     # noqa: E731
+    for cut in ((by_cols, by_rows) if w > h else (by_rows, by_cols)):
+        pieces = cut()
+        if pieces:
+            return pieces
+    return None
+
+
+def _clean(var, avg, box: Box, n: int) -> List[Box]:
+    """clean_imgs on the region ``box`` of the maps -> its views"""
+    if n < MIN_FRAMES:
+        return [box]
+    y0, y1, x0, x1 = box
+    b0, b1, a0, a1 = _borders(var[y0:y1, x0:x1], avg[y0:y1, x0:x1])
+    cut = (y0 + b0, y0 + b1, x0 + a0, x0 + a1)
+    if min(b1 - b0, a1 - a0) < MIN_SIDE:
+        return [box]
+    pieces = _split(var[cut[0]:cut[1], cut[2]:cut[3]], avg[cut[0]:cut[1], cut[2]:cut[3]], MIN_VIEW)
+    if pieces is None or (len(pieces) == 1 and (pieces[0][1] - pieces[0][0], pieces[0][3] - pieces[0][2]) == (b1 - b0, a1 - a0)):
+        return [cut]
+    views = []
+    for p0, p1, q0, q1 in pieces:
+        views.extend(_clean(var, avg, (cut[0] + p0, cut[0] + p1, cut[2] + q0, cut[2] + q1), n))
+    return views
+
+
+def decide_views(var: np.ndarray, count: np.ndarray, m: int, n: int) -> Tuple[bool, List[Box]]:
+    """image_process on the maps of one video of ``n`` frames: ``var`` float64 [H, W] (np.stack(frames).var(0).sum(-1)) and
+    ``count`` [H, W], the number of the ``m`` sampled frames where Canny marks an edge.  -> (changed, boxes): the views in the
+    reference's order, or (False, [whole frame])."""
+    h, w = var.shape
+    whole = (0, h, 0, w)
+    if n < MIN_FRAMES:
+        return False, [whole]
+    avg = np.asarray(count).astype(np.float64) / m
+    with np.errstate(all="ignore"):
+        views = _clean(np.asarray(var, dtype=np.float64), avg, whole, n)
+    if len(views) > 1 or (views[0][1] - views[0][0], views[0][3] - views[0][2]) != (h, w):
+        return True, views
+    return False, [whole]
+
+
+def detect_views(frames_dev) -> Tuple[bool, List[Box]]:
+    """The views of one video whose uint8 frames [n, H, W, 3] are on the GPU: one vsc_frame_var_u8 and one vsc_canny_count_u8
+    launch, one device -> host copy of both maps, then ``decide_views``.  Launch and device errors propagate."""
+    n, h, w = (int(s) for s in frames_dev.shape[:3])
+    whole = (0, h, 0, w)
+    idx = canny_frames(n)
+    if n < MIN_FRAMES or idx is None:
+        return False, [whole]
+    from vsc_hip import ops
+    var, count = ops.view_maps(frames_dev, idx, CANNY_LOW, CANNY_HIGH)
+    return decide_views(var, count, len(idx), n)
+
+
+class HipViews:
+    """``run_query_videos(views=HipViews(device))`` for ``--preprocess hip``: uploads a video's full-resolution uint8 frames,
+    ``detect_views`` on them, then one vsc_resize_bicubic_u8 per encoder input size -> (boxes, {size: uint8 [k * n, size, size, 3]
+    on the device}).  The work runs on a side stream, so the host's wait for the two maps does not wait for the encoders queued
+    on the caller's stream; the caller's stream is ordered behind the resized views."""
+
+    def __init__(self, device):
+        import torch
+        self.device = torch.device(device)
+        self.stream = torch.cuda.Stream(device=self.device)
+
+    def __call__(self, raw, sizes):
+        import torch
+        from vsc_hip import ops
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.stream):
+            frames = raw.to(self.device)
+            _, boxes = detect_views(frames)
+            out = {size: ops.resize_bicubic(frames, boxes, size) for size in sizes}
+        main.wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(main)
+        return boxes, out

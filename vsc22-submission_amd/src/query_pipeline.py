@@ -14,6 +14,8 @@ import torch
 from src.query_postprocess import HipOps, SCORE_THRESHOLD, process_query_group, process_query_video
 from vsc.index import VideoFeature
 
+RAW_KEY = "raw"   # frames_by_size key of a video's full-resolution uint8 frames [n, H, W, 3] (--preprocess hip)
+
 
 def encode_frames(model, frames: torch.Tensor, device, chunk: int = 256) -> np.ndarray:
     """``single_infer`` (:150-161): frames of one video through one backbone, ``chunk`` at a time."""
@@ -153,14 +155,16 @@ def encode_group(models: Sequence, frames_list: Sequence[torch.Tensor], device, 
     every chunk is uploaded once and goes through all of them.  -> per model, per video arrays (``as_numpy=False``: device
     tensors -- the video-score head takes them where they are).  ``chunk`` = None: ``preferred_chunk(models)``.
     On a GPU the chunks go through pinned staging buffers and a copy stream (``_Stager``); the per-model outputs of the whole
-    group come back in ONE device -> host copy each."""
+    group come back in ONE device -> host copy each.  Frames already on the device (the views of ``--preprocess hip``) skip the
+    staging: a chunk is a slice of them, or their concatenation on the device."""
     if not chunk:
         f0 = frames_list[0] if len(frames_list) else None
         chunk = preferred_call(models, int(f0[0].numel() * f0.element_size()) if f0 is not None and f0.shape[0] else 1)
     lens = [f.shape[0] for f in frames_list]
     total = sum(lens)
     outs = [[] for _ in models]
-    staged = torch.device(device).type == "cuda" and total > 0
+    on_device = any(f.is_cuda for f in frames_list)
+    staged = torch.device(device).type == "cuda" and total > 0 and not on_device
     st = _Stager.get(device, chunk, frames_list[0].shape[1:], frames_list[0].dtype) if staged else None
     # walk the videos chunk by chunk without materialising the concatenation on the host
     buf, have, k = [], 0, 0
@@ -171,6 +175,9 @@ def encode_group(models: Sequence, frames_list: Sequence[torch.Tensor], device, 
             return
         if staged:
             x = st.upload(k & 1, buf)
+        elif on_device:    # (a video whose frames differ in size comes from the host, resized there, among the device views)
+            pieces = [f[lo:lo + take].to(device) for f, lo, take in buf]
+            x = pieces[0] if len(pieces) == 1 else torch.cat(pieces)
         else:   # host-logic tests (fake encoders on the CPU); the HIP encoders refuse CPU tensors
             x = torch.cat([f[lo:lo + take] for f, lo, take in buf]).to(device)
         for i, model in enumerate(models):
@@ -204,6 +211,23 @@ def encode_group(models: Sequence, frames_list: Sequence[torch.Tensor], device, 
     return result
 
 
+def _with_views(videos, sizes: Sequence[int], views):
+    """``--preprocess hip``: a video that carries its full-resolution frames under ``RAW_KEY`` becomes its views -- ``views``
+    detects them and cuts and resizes them once per encoder input size -> {size: [k * n, size, size, 3]}, view-major, with the
+    timestamps tiled the same way (the reference's ``timestamp * split_ratio``, extract_query_feats.py:176-179).  Other videos
+    (frames of different sizes: the reference leaves them unprocessed) pass through as they are."""
+    for vid, frames_by_size, stamps in videos:
+        raw = frames_by_size.get(RAW_KEY)
+        if raw is None:
+            yield vid, frames_by_size, stamps
+            continue
+        boxes, by_size = views(raw, sizes)
+        out = {key: f for key, f in frames_by_size.items() if key != RAW_KEY}
+        out.update(by_size)
+        stamps = np.asarray(stamps)
+        yield vid, out, np.tile(stamps, (len(boxes),) + (1,) * (stamps.ndim - 1))
+
+
 def _video_groups(videos, min_frames: int):
     """Consecutive videos grouped until a group holds at least ``min_frames`` frames."""
     group, n = [], 0
@@ -221,8 +245,10 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
                      pca_transform: Callable[[np.ndarray], np.ndarray], video_scores: Dict[str, float], device,
                      ops=HipOps, score_threshold: float = SCORE_THRESHOLD, chunk: int = None,
                      scorer: Callable[[torch.Tensor], float] = None,
-                     group_frames: int = 4096) -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
+                     group_frames: int = 4096, views=None) -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
     """videos yields (video_id, {image_size: frames [S,3,size,size]}, timestamps); encoders = [(model, image_size)].
+    ``views`` (``--preprocess hip``, src.image_preprocess.HipViews): videos that carry full-resolution frames under ``RAW_KEY``
+    are replaced by their views first (border removal and split views, ``_with_views``): k views of n frames encode as k * n rows.
     The video score comes from ``scorer(frames_by_size[VideoScorer.KEY])`` when a scorer is given (and is recorded
     in ``video_scores``), else from ``video_scores``; a video missing there is treated as accepted (score 1.0).
     Backbones run over groups of consecutive videos (>= ``group_frames`` frames) so their launches stay large and the ragged last chunk of a
@@ -231,6 +257,8 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
     -> (final descriptors per video, per-model VideoFeatures per video), in input order."""
     finals, per_model = [], []
     rnd_idx = 0
+    if views is not None:
+        videos = _with_views(videos, list(dict.fromkeys(sz for _, sz in encoders)), views)
     # on the GPU with the library's own ops the per-video post-processing is batched per group and the features stay on the device
     # in between (process_query_group); anything else (the host-logic tests' numpy ops) takes the reference's per-video steps
     batched = ops is HipOps and torch.device(device).type == "cuda"

@@ -232,6 +232,71 @@ def tn_align(sims, pairs, bias: float, max_step: int, top_k: int, max_path: int,
     return boxes, counts, maxsim
 
 
+def _frames_u8(frames):
+    assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3, \
+        "frames must be uint8 [n, H, W, 3] on the GPU"
+    return frames.contiguous()
+
+
+def frame_var(frames):
+    """np.stack(frames).var(axis=0).sum(-1) of uint8 device frames [n, H, W, 3], bit-identical -> float64 [H, W] on the device
+    (vsc_frame_var_u8)."""
+    lib = _rd()
+    frames = _frames_u8(frames)
+    n, h, w = frames.shape[:3]
+    out = torch.empty((h, w), dtype=torch.float64, device=frames.device)
+    check(lib.vsc_frame_var_u8(ptr(frames), n, h, w, ptr(out), current_stream()))
+    return out
+
+
+def canny_count(frames, idx, low: float = 50, high: float = 400):
+    """Per pixel, the number of frames[idx] where Canny(low, high) marks an edge -> uint16 [H, W] on the device.
+    Contract: vsc_canny_count_u8."""
+    import numpy as np
+    lib = _rd()
+    frames = _frames_u8(frames)
+    n, h, w = frames.shape[:3]
+    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+    out = torch.empty((h, w), dtype=torch.uint16, device=frames.device)
+    check(lib.vsc_canny_count_u8(ptr(frames), n, idx.ctypes.data, idx.size, h, w, float(low), float(high), ptr(out), current_stream()))
+    return out
+
+
+def view_maps(frames, idx, low: float = 50, high: float = 400):
+    """Both maps the view decisions read (src/image_preprocess.py), with ONE device -> host copy: -> (variance float64 [H, W],
+    edge count uint16 [H, W]) as numpy arrays."""
+    import numpy as np
+    lib = _rd()
+    frames = _frames_u8(frames)
+    n, h, w = frames.shape[:3]
+    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+    buf = torch.empty(h * w * 10, dtype=torch.uint8, device=frames.device)     # float64 map, then the uint16 map
+    var, count = buf[:h * w * 8], buf[h * w * 8:]
+    check(lib.vsc_frame_var_u8(ptr(frames), n, h, w, ptr(var), current_stream()))
+    check(lib.vsc_canny_count_u8(ptr(frames), n, idx.ctypes.data, idx.size, h, w, float(low), float(high), ptr(count),
+                                 current_stream()))
+    host = buf.cpu().numpy()
+    return host[:h * w * 8].view(np.float64).reshape(h, w), host[h * w * 8:].view(np.uint16).reshape(h, w)
+
+
+def resize_bicubic(frames, boxes, size: int, out=None):
+    """Crop every box (y0, y1, x0, x1) out of every uint8 device frame [n, H, W, 3] and resize it to size x size, PIL-exact
+    (Image.fromarray(crop).resize((size, size), Image.BICUBIC)) -> uint8 [len(boxes) * n, size, size, 3], view-major
+    (vsc_resize_bicubic_u8)."""
+    import numpy as np
+    lib = _rd()
+    frames = _frames_u8(frames)
+    n, h, w = frames.shape[:3]
+    boxes = np.ascontiguousarray(np.asarray(boxes, dtype=np.int32).reshape(-1, 4))
+    k = boxes.shape[0]
+    if out is None:
+        out = torch.empty((k * n, size, size, 3), dtype=torch.uint8, device=frames.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and tuple(out.shape) == (k * n, size, size, 3)
+    check(lib.vsc_resize_bicubic_u8(ptr(frames) if n else None, n, h, w, boxes.ctypes.data, k, int(size), ptr(out) if out.numel() else None,
+                                    current_stream()))
+    return out
+
+
 def video_pair_max(q, q_video, n_q_videos: int, r, r_video, n_r_videos: int, threshold: float, capacity: int = 1 << 20):
     """Largest frame score above ``threshold`` per (query video, reference video).
     q [nq, d], r [nr, d] float32; q_video [nq], r_video [nr] int32 video index of every row.
