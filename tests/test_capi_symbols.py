@@ -36,6 +36,12 @@ def test_every_declared_symbol_is_exported(lib):
     exported = set(re.findall(r" T (vsc_[a-z0-9_]+)", nm))
     assert declared <= exported, f"declared but not exported: {sorted(declared - exported)}"
     assert exported <= declared, f"exported but undeclared: {sorted(exported - declared)}"
+    # ... and nothing else of any symbol type: the two libraries define the same internal C++ names with different operand
+    # semantics, so an exported launcher, kernel stub or global could bind across them (csrc/Makefile: EXPORTS)
+    listing = [line.split() for line in nm.splitlines() if line.strip()]
+    extra = sorted(f"{f[-2]} {f[-1]}" for f in listing if f[-2] != "T" or f[-1] not in declared)
+    assert not extra, f"{len(extra)} dynamic symbols beside the C ABI: {extra[:20]}"
+    assert sorted(f[-1] for f in listing) == sorted(declared)
     assert set(_lib.SIGNATURES) == declared, "python binding and header disagree"
 
 
@@ -79,7 +85,7 @@ def test_option_table_is_read_once_and_set_through_the_api(lib, monkeypatch):
     src = "".join(open(p).read() for p in glob.glob(os.path.join(ROOT, "vsc22-submission_amd", "csrc", "*.hip")) +
                   glob.glob(os.path.join(ROOT, "vsc22-submission_amd", "csrc", "*.h")))
     assert len(re.findall(r"\bgetenv\(", src)) == 1, "getenv outside the once-per-process loader in capi.hip"
-    for name in set(re.findall(r"vsc_opt\(OPT_([A-Z0-9_]+)\)", src)):
+    for name in set(re.findall(r"vsc_opt(?:_is|_int)?\(OPT_([A-Z0-9_]+)\b", src)):
         assert lib.vsc_set_option(("VSC_" + name).encode(), None) == 0, name
 
 

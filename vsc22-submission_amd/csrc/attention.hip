@@ -458,32 +458,21 @@ int launch_kt(const uint16_t *qkv, uint16_t *out, int frames, int tokens, int he
               hipStream_t stream) {
     constexpr int TP = KT * 32;
     constexpr int smem = TP * 128 + 64 * (TP * 2 + 32) + 8 * 2048;
-    static bool attr_set[16] = {};   // per device (one process may drive several)
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)attention_kernel<KT, 1>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)attention_kernel<KT, 2>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        if (dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(attention_kernel<KT, 1>, smem));
+    VSC_TRY(vsc_allow_dynamic_lds(attention_kernel<KT, 2>, smem));
     // start skew of each CU's second resident (see the kernel): half a workgroup lifetime.  Measured at 197 tokens (lifetime
     // ~32 k cycles): 0 / 4 / 8 / 12 / 16 / 24 / 32 k cycles -> 148.6 / 140.3 / 137.6 / 132.4 / 121.8 / 136.4 / 139.4 us cold,
     // 116.9 / 114.1 / 107.6 / 104.9 / 104.2 / 116.9 / 114.7 us warm (tools/micro/attn_bench.py).  Two workgroups are resident
     // from 5 key tiles up (LDS); the lifetime goes with the square of the token count.
-    static int cus_of[16] = {};
-    if (dev < 16 && !cus_of[dev]) VSC_CHECK_HIP(hipDeviceGetAttribute(&cus_of[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    const int ncu = dev < 16 && cus_of[dev] > 0 ? cus_of[dev] : 256;
-    int skew = KT >= 5 && frames * heads > 2 * ncu ? 16000 * KT * KT / 49 : 0;
-    if (const char *e = vsc_opt(OPT_ATTN_SKEW)) skew = atoi(e);
+    int cus = 0;
+    VSC_TRY(vsc_device_cus(&cus));
+    const int ncu = cus > 0 ? cus : 256;
+    const int skew = vsc_opt_int(OPT_ATTN_SKEW, KT >= 5 && frames * heads > 2 * ncu ? 16000 * KT * KT / 49 : 0);
 #ifdef VSC_ATTN_ABLATION
-    if (KT == 7)
-        if (const char *e = vsc_opt(OPT_ATTN_ABL)) {
-            const int abl = atoi(e);
-#define VSC_ABL_CASE(A) case A: { auto k = attention_kernel<7, 1, A>; VSC_CHECK_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); \
+    if (KT == 7) {
+#define VSC_ABL_CASE(A) case A: { auto k = attention_kernel<7, 1, A>; VSC_TRY(vsc_allow_dynamic_lds(k, smem)); \
             hipLaunchKernelGGL(k, dim3(frames * heads), dim3(512), smem, stream, qkv, out, tokens, heads, frames * heads, skew, ncu); VSC_CHECK_LAUNCH(); return VSC_OK; }
-            switch (abl) { VSC_ABL_CASE(1) VSC_ABL_CASE(2) VSC_ABL_CASE(4) VSC_ABL_CASE(6) VSC_ABL_CASE(7) VSC_ABL_CASE(8) VSC_ABL_CASE(16) VSC_ABL_CASE(24) VSC_ABL_CASE(31) default: break; }
+            switch (vsc_opt_int(OPT_ATTN_ABL, 0)) { VSC_ABL_CASE(1) VSC_ABL_CASE(2) VSC_ABL_CASE(4) VSC_ABL_CASE(6) VSC_ABL_CASE(7) VSC_ABL_CASE(8) VSC_ABL_CASE(16) VSC_ABL_CASE(24) VSC_ABL_CASE(31) default: break; }
         }
 #endif
     const int total = frames * heads;
@@ -492,14 +481,9 @@ int launch_kt(const uint16_t *qkv, uint16_t *out, int frames, int tokens, int he
     // ViT-B step (four alternating runs, same box) -- with all loads off the critical path the item time is the compute phase's
     // instruction stream (MFMA + softmax VALU + LDS issue add up on a SIMD), which 13 waves side by side do not shorten.
     if constexpr (KT <= 8) {
-        const char *dm = vsc_opt(OPT_ATTN_DMA);
-        if (tokens <= 256 && dm && dm[0] == '1') {
+        if (tokens <= 256 && vsc_opt_is(OPT_ATTN_DMA, '1')) {
             constexpr int smem_dma = 4 * TP * 128 + 16 * 2048;
-            static bool dma_attr[16] = {};
-            if (dev >= 16 || !dma_attr[dev]) {
-                VSC_CHECK_HIP(hipFuncSetAttribute((const void *)attention_dma_kernel<KT>, hipFuncAttributeMaxDynamicSharedMemorySize, smem_dma));
-                if (dev < 16) dma_attr[dev] = true;
-            }
+            VSC_TRY(vsc_allow_dynamic_lds(attention_dma_kernel<KT>, smem_dma));
             const int grid = total < ncu ? total : ncu;
             hipLaunchKernelGGL((attention_dma_kernel<KT>), dim3(grid), dim3(1024), smem_dma, stream, qkv, out, tokens, heads, total);
             VSC_CHECK_LAUNCH();
@@ -509,9 +493,7 @@ int launch_kt(const uint16_t *qkv, uint16_t *out, int frames, int tokens, int he
     // items per workgroup: 1.  Two (the second one's K / V rows requested into registers before the first is computed) were
     // measured again on this kernel (tools/micro/attn_ni.py): 166 VGPRs, i.e. one resident workgroup per CU, or capped at
     // 128 VGPRs 120 bytes of scratch -- 160 us per launch against 110-119.  VSC_ATTN_NI=2 keeps the variant reachable.
-    int ni = 1;
-    if (const char *e = vsc_opt(OPT_ATTN_NI)) ni = atoi(e) == 2 ? 2 : 1;
-    if (ni == 2)
+    if (vsc_opt_int(OPT_ATTN_NI, 1) == 2)
         hipLaunchKernelGGL((attention_kernel<KT, 2>), dim3((total + 1) / 2), dim3(512), smem, stream, qkv, out, tokens, heads,
                            total, 2 * skew, ncu);
     else

@@ -58,6 +58,14 @@ const char *vsc_opt(VscOpt o) {
     std::call_once(g_opt_once, opt_load_env);
     return g_opt_values[o].load(std::memory_order_acquire);
 }
+bool vsc_opt_is(VscOpt o, char c) {
+    const char *e = vsc_opt(o);
+    return e && e[0] == c;
+}
+int vsc_opt_int(VscOpt o, int dflt) {
+    const char *e = vsc_opt(o);
+    return e ? atoi(e) : dflt;
+}
 // value == NULL (or "") clears the switch.  Superseded strings are not freed: a reader may still hold them, and switches
 // change a handful of times per process (tests, A/B tools).
 extern "C" int vsc_set_option(const char *name, const char *value) {
@@ -80,6 +88,36 @@ extern "C" const char *vsc_get_option(const char *name) {
         if (!strcmp(name, g_opt_names[i]) || !strcmp(name, g_opt_names[i] + 4))
             return g_opt_values[i].load(std::memory_order_acquire);
     return nullptr;
+}
+
+// ---- per-device launch plumbing (common.h) ---------------------------------------------------------------------------
+#include <map>
+static std::atomic<int> g_cus[VSC_MAX_DEVICES];   // 0: not asked yet
+int vsc_device_cus(int *cus, int *dev_out) {
+    int dev = 0;
+    VSC_CHECK_HIP(hipGetDevice(&dev));
+    if (dev_out) *dev_out = dev;
+    const bool cached = dev >= 0 && dev < VSC_MAX_DEVICES;
+    *cus = cached ? g_cus[dev].load(std::memory_order_relaxed) : 0;
+    if (*cus <= 0) {
+        VSC_CHECK_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, dev));
+        if (cached) g_cus[dev].store(*cus, std::memory_order_relaxed);
+    }
+    return VSC_OK;
+}
+
+static std::mutex g_lds_mutex;
+static std::map<std::pair<const void *, int>, int> g_lds_bytes;   // (kernel, device ordinal) -> the limit set so far
+int vsc_allow_dynamic_lds_ptr(const void *kernel, int bytes) {
+    int dev = 0;
+    VSC_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_lds_mutex);
+    int &have = g_lds_bytes[{kernel, dev}];
+    if (have < bytes) {
+        VSC_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        have = bytes;
+    }
+    return VSC_OK;
 }
 
 extern "C" int vsc_gemm_bf16(const uint16_t *a, const uint16_t *w, const float *bias, const float *aux,

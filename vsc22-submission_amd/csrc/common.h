@@ -37,6 +37,12 @@ void vsc_set_error(const char *fmt, ...);
 
 #define VSC_CHECK_LAUNCH() VSC_CHECK_HIP(hipGetLastError())
 
+// a call that has already reported its own error: pass its return code on
+#define VSC_TRY(expr)                     \
+    do {                                  \
+        if (int _rc = (expr)) return _rc; \
+    } while (0)
+
 // ---- diagnostic / test switches ------------------------------------------------------------------
 // Every switch that used to be an environment lookup on the launch path.  The environment is read ONCE per process (first use of any
 // switch); afterwards a switch changes only through vsc_set_option() (include/vsc_hip.h).  vsc_opt() is an array read.
@@ -52,6 +58,20 @@ enum VscOpt {
     OPT_COUNT
 };
 const char *vsc_opt(VscOpt o);   // value of VSC_<name> (environment at first use, or the last vsc_set_option), nullptr when unset
+bool vsc_opt_is(VscOpt o, char c);     // set, and its first character is c ('0' = off, '1' = on for most switches)
+int vsc_opt_int(VscOpt o, int dflt);   // atoi of the value, dflt when unset
+
+// ---- per-device launch plumbing (capi.hip) ---------------------------------------------------------
+// One copy for the whole library, callable from several threads, valid for any device ordinal.  Both return VSC_OK or
+// VSC_ERR_HIP (with the error text set).
+constexpr int VSC_MAX_DEVICES = 16;   // extent of every per-device array of the library
+// number of CUs of the current device (and, if asked for, its ordinal): asked of the runtime once per device (ordinals from
+// VSC_MAX_DEVICES up: on every call)
+int vsc_device_cus(int *cus, int *dev = nullptr);
+// `kernel` may be launched with up to `bytes` of dynamic LDS on the current device: hipFuncSetAttribute once per (kernel, device)
+int vsc_allow_dynamic_lds_ptr(const void *kernel, int bytes);
+template <class... Args>
+inline int vsc_allow_dynamic_lds(void (*kernel)(Args...), int bytes) { return vsc_allow_dynamic_lds_ptr((const void *)kernel, bytes); }
 
 // ---- bf16 <-> f32 ------------------------------------------------------------
 __device__ __host__ inline float bf16_to_f32(uint16_t h) {

@@ -1643,10 +1643,10 @@ struct Scratch {
     void *ptr = nullptr;
     size_t bytes = 0;
 };
-Scratch g_patch[16];   // per device, grow-only: the packed patch matrix of the convolution in flight
+Scratch g_patch[VSC_MAX_DEVICES];   // per device, grow-only: the packed patch matrix of the convolution in flight
 std::mutex g_conv_mutex;
-float *g_zero_line[16] = {};   // per device: 256 bytes of zeros (implicit gathering points padding taps at it)
-Scratch g_x3[16];               // per device, grow-only: split-bf16 planes (activations | weights) of the implicit GEMM in flight
+float *g_zero_line[VSC_MAX_DEVICES] = {};   // per device: 256 bytes of zeros (implicit gathering points padding taps at it)
+Scratch g_x3[VSC_MAX_DEVICES];               // per device, grow-only: split-bf16 planes (activations | weights) of the implicit GEMM in flight
 
 inline int blocks_for(int64_t items) {
     int64_t b = (items + 255) / 256;
@@ -1683,25 +1683,25 @@ extern "C" int vsc_conv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_t 
     VSC_REQUIRE(ho > 0 && wo > 0, "conv2d: empty output");
     const int64_t rows = n * ho * wo;
     const int k = cin * kh * kw, kpad = (k + KS - 1) / KS * KS;
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    VSC_REQUIRE(dev >= 0 && dev < 16, "conv2d: device %d out of range", dev);
+    int dev = 0, cus = 0;
+    VSC_TRY(vsc_device_cus(&cus, &dev));
+    VSC_REQUIRE(dev >= 0 && dev < VSC_MAX_DEVICES, "conv2d: device %d out of range", dev);   // (the per-device scratch below)
     // thin 3 x 3 / stride 1 / pad 1 layers: direct convolution from a halo tile in LDS (conv3x3_direct_kernel)
     {
-        const char *de = vsc_opt(OPT_CONV_DIRECT);   // diagnostic / test switch: 0 = the implicit-GEMM path
+        const bool no_direct = vsc_opt_is(OPT_CONV_DIRECT, '0');   // diagnostic / test switch: 0 = the implicit-GEMM path
         const int64_t xbytes = n * (int64_t)h * w * ldx * 4;
-        const char *x3e = vsc_opt(OPT_CONV_X3);
+        const bool no_x3 = vsc_opt_is(OPT_CONV_X3, '0');   // diagnostic / test switch: 0 = the fp32-pipe kernels everywhere
         // the epilogues of the direct / tap / plane kernels move out, res and bias 16 bytes at a time whenever ldo and ldr are multiples
         // of 4: an output window at an offset (Conv.__call__(out=..., coff=...)) or a caller's unaligned buffer takes the tile kernels
         // (with ldo or ldr not a multiple of 4 those epilogues use scalar accesses anyway: any alignment is fine then)
         const bool vec_io = ((ldo | (res_dev ? ldr : 0)) & 3) == 0;
         const bool io16 = !vec_io || (((uintptr_t)out_dev | (uintptr_t)(res_dev ? res_dev : out_dev) | (uintptr_t)(bias_dev ? bias_dev : out_dev)) & 15) == 0;
-        const bool tap_x3 = io16 && !(de && de[0] == '0') && !(x3e && x3e[0] == '0') && kh == 3 && kw == 3 && stride == 1 && pad == 1 && ((cin == 64 && cout <= 64) || (cin == 256 && cout <= 32)) && ldx == cin &&
+        const bool tap_x3 = io16 && !no_direct && !no_x3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && ((cin == 64 && cout <= 64) || (cin == 256 && cout <= 32)) && ldx == cin &&
                             (((uintptr_t)x_dev | (uintptr_t)w_packed_dev) & 15) == 0 && xbytes < (1ll << 31) && (!res_dev || ldr >= cout) &&
                             n * (int64_t)h * w * (ldo > ldr ? ldo : ldr) * 4 < (1ll << 31) && n * (int64_t)h * w >= 65536;
         // wide 3 x 3 layers on small maps: both operands split into planes once, implicit GEMM on the bf16 pipe (conv_x3_gemm_kernel)
         const int64_t in_elems = n * (int64_t)h * w * cin;
-        const bool x3gemm = io16 && !(de && de[0] == '0') && !(x3e && x3e[0] == '0') && kh == 3 && kw == 3 && stride == 1 && pad == 1 && (cin == 72 || cin == 144) &&
+        const bool x3gemm = io16 && !no_direct && !no_x3 && kh == 3 && kw == 3 && stride == 1 && pad == 1 && (cin == 72 || cin == 144) &&
                             ldx == cin && cout >= 48 && cout <= 160 && (((uintptr_t)x_dev | (uintptr_t)w_packed_dev) & 15) == 0 && in_elems * 6 < (1ll << 31) &&
                             in_elems <= (16ll << 20) && (!res_dev || ldr >= cout) && n * (int64_t)h * w >= 8192 && n * (int64_t)h * w < (1ll << 31);
         if (x3gemm) {
@@ -1741,39 +1741,34 @@ extern "C" int vsc_conv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_t 
             DirectArgs a{x_dev, w_packed_dev, bias_dev, res_dev, out_dev, (int)n, h, w, ldx, cout, kpad, ldo, ldr, act,
                          (w + 31) / 32, (h + 3) / 4, 0, (unsigned)xbytes, cin / 4};
             a.ntiles = (int64_t)a.tiles_x * a.tiles_y * n;
-            static int cus_tap[16] = {};
-            if (!cus_tap[dev]) VSC_CHECK_HIP(hipDeviceGetAttribute(&cus_tap[dev], hipDeviceAttributeMultiprocessorCount, dev));
-            const unsigned grid = (unsigned)(a.ntiles < cus_tap[dev] ? a.ntiles : cus_tap[dev]);
+            const unsigned grid = (unsigned)(a.ntiles < cus ? a.ntiles : cus);
             g_conv_last_pipe = 1;
             if (cin == 256) hipLaunchKernelGGL((conv3x3_tap_x3_kernel<8, 2, 4>), dim3(grid), dim3(512), 0, stream, a);
             else hipLaunchKernelGGL((conv3x3_tap_x3_kernel<8, 4, 1>), dim3(grid), dim3(512), 0, stream, a);
             VSC_CHECK_LAUNCH();
             return VSC_OK;
         }
-        const bool direct = io16 && !(de && de[0] == '0') && kh == 3 && kw == 3 && stride == 1 && pad == 1 && cout <= 40 && (cin == 20 || cin == 36) &&
+        const bool direct = io16 && !no_direct && kh == 3 && kw == 3 && stride == 1 && pad == 1 && cout <= 40 && (cin == 20 || cin == 36) &&
                             (ldx & 3) == 0 && (((uintptr_t)x_dev | (uintptr_t)w_packed_dev) & 15) == 0 && xbytes < (1ll << 31) &&
                             (!res_dev || ldr >= cout);
         if (direct) {
             DirectArgs a{x_dev, w_packed_dev, bias_dev, res_dev, out_dev, (int)n, h, w, ldx, cout, kpad, ldo, ldr, act,
                          (w + 31) / 32, (h + 7) / 8, 0, (unsigned)xbytes, cin / 4};
             a.ntiles = (int64_t)a.tiles_x * a.tiles_y * n;
-            static int cus_direct[16] = {};
-            if (!cus_direct[dev]) VSC_CHECK_HIP(hipDeviceGetAttribute(&cus_direct[dev], hipDeviceAttributeMultiprocessorCount, dev));
             const bool two = cin == 20 && cout <= 32;   // workgroups per CU (LDS)
-            const int64_t resident = (two ? 2ll : 1ll) * cus_direct[dev];
+            const int64_t resident = (two ? 2ll : 1ll) * cus;
             const unsigned grid = (unsigned)(a.ntiles < resident ? a.ntiles : resident);
-            const char *x3 = vsc_opt(OPT_CONV_X3);   // diagnostic / test switch: 0 = the fp32-pipe kernels everywhere
-            if (!(x3 && x3[0] == '0') && cin == 36 && cout <= 36 && n * (int64_t)h * w * (ldo > ldr ? ldo : ldr) * 4 < (1ll << 31)) {
+            if (!no_x3 && cin == 36 && cout <= 36 && n * (int64_t)h * w * (ldo > ldr ? ldo : ldr) * 4 < (1ll << 31)) {
                 DirectArgs b = a;   // 4 x 32 tiles, one workgroup per CU
                 b.tiles_y = (h + 3) / 4;
                 b.ntiles = (int64_t)b.tiles_x * b.tiles_y * n;
-                const unsigned g36 = (unsigned)(b.ntiles < cus_direct[dev] ? b.ntiles : cus_direct[dev]);
+                const unsigned g36 = (unsigned)(b.ntiles < cus ? b.ntiles : cus);
                 g_conv_last_pipe = 1;
                 hipLaunchKernelGGL((conv3x3_direct_x3_kernel<5, 36, 3, 1>), dim3(g36), dim3(512), 0, stream, b);
                 VSC_CHECK_LAUNCH();
                 return VSC_OK;
             }
-            if (!(x3 && x3[0] == '0') && cin == 20 && cout <= 20 && n * (int64_t)h * w * (ldo > ldr ? ldo : ldr) * 4 < (1ll << 31)) {
+            if (!no_x3 && cin == 20 && cout <= 20 && n * (int64_t)h * w * (ldo > ldr ? ldo : ldr) * 4 < (1ll << 31)) {
                 g_conv_last_pipe = 1;
                 hipLaunchKernelGGL((conv3x3_direct_x3_kernel<3, 20, 2, 2>), dim3(grid), dim3(512), 0, stream, a);
             }
@@ -1787,8 +1782,8 @@ extern "C" int vsc_conv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_t 
     }
     // 3 -> 8 / 16 / 32 channels, 3 x 3: the direct stem kernel (conv_stem3_kernel)
     {
-        const char *se = vsc_opt(OPT_CONV_STEM);   // diagnostic / test switch: 0 = the GEMM path
-        const bool stem = !(se && se[0] == '0') && cin == 3 && ldx == 3 && kh == 3 && kw == 3 && (cout == 8 || cout == 16 || cout == 32) && !res_dev &&
+        // diagnostic / test switch VSC_CONV_STEM: 0 = the GEMM path
+        const bool stem = !vsc_opt_is(OPT_CONV_STEM, '0') && cin == 3 && ldx == 3 && kh == 3 && kw == 3 && (cout == 8 || cout == 16 || cout == 32) && !res_dev &&
                           (ldo & 3) == 0 && (((uintptr_t)out_dev | (uintptr_t)(bias_dev ? bias_dev : out_dev)) & 15) == 0 && rows < (1ll << 31) * 256;
         if (stem) {
             const dim3 grid((unsigned)((rows + 255) / 256));
@@ -1801,15 +1796,13 @@ extern "C" int vsc_conv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_t 
     }
     // 1 x 1 expansion from 64 channels: the streaming kernel (conv1x1_expand64_kernel)
     {
-        const char *ee = vsc_opt(OPT_CONV_EXPAND);   // diagnostic / test switch: 0 = the tile kernels
-        const bool expand = !(ee && ee[0] == '0') && kh == 1 && kw == 1 && stride == 1 && pad == 0 && cin == 64 && ldx == 64 && cout >= 128 &&
+        // diagnostic / test switch VSC_CONV_EXPAND: 0 = the tile kernels
+        const bool expand = !vsc_opt_is(OPT_CONV_EXPAND, '0') && kh == 1 && kw == 1 && stride == 1 && pad == 0 && cin == 64 && ldx == 64 && cout >= 128 &&
                             cout <= 256 && (cout & 31) == 0 && rows >= 128 * 256 && rows * (int64_t)ldo * 4 < (1ll << 31) &&
                             (!res_dev || rows * (int64_t)ldr * 4 < (1ll << 31)) && (((uintptr_t)x_dev | (uintptr_t)w_packed_dev) & 15) == 0;
         if (expand) {
-            static int cus_expand[16] = {};
-            if (!cus_expand[dev]) VSC_CHECK_HIP(hipDeviceGetAttribute(&cus_expand[dev], hipDeviceAttributeMultiprocessorCount, dev));
             ExpandArgs a{x_dev, w_packed_dev, bias_dev, res_dev, out_dev, rows, (rows + 127) / 128, cout, ldo, ldr, act};
-            const unsigned grid = (unsigned)(a.ntiles < cus_expand[dev] ? a.ntiles : cus_expand[dev]);
+            const unsigned grid = (unsigned)(a.ntiles < cus ? a.ntiles : cus);
             hipLaunchKernelGGL(conv1x1_expand64_kernel, dim3(grid), dim3(512), 0, stream, a);
             VSC_CHECK_LAUNCH();
             return VSC_OK;
@@ -1817,19 +1810,16 @@ extern "C" int vsc_conv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_t 
     }
     // pointwise layers with <= 96 input channels and >= 2 x as many outputs on many pixels: the streaming kernel for any cin % 4 == 0
     {
-        const char *ee = vsc_opt(OPT_CONV_EXPAND);
-        const char *nm2 = vsc_opt(OPT_CONV_STREAM_MIN_COUT);   // diagnostic: smallest cout taken (default 2 cin)
+        const int min_cout = vsc_opt_int(OPT_CONV_STREAM_MIN_COUT, 2 * cin);   // diagnostic: smallest cout taken
         const int cp = (cin + 7) / 8;
-        const bool strm = !(ee && ee[0] == '0') && kh == 1 && kw == 1 && stride == 1 && pad == 0 && ldx == cin && (cin & 3) == 0 && cin >= 16 && cin <= 96 &&
-                          cout >= (nm2 ? atoi(nm2) : 2 * cin) && rows >= 128 * 256 && rows * (int64_t)ldo * 4 < (1ll << 31) && rows * (int64_t)cin * 4 < (1ll << 31) &&
+        const bool strm = !vsc_opt_is(OPT_CONV_EXPAND, '0') && kh == 1 && kw == 1 && stride == 1 && pad == 0 && ldx == cin && (cin & 3) == 0 && cin >= 16 && cin <= 96 &&
+                          cout >= min_cout && rows >= 128 * 256 && rows * (int64_t)ldo * 4 < (1ll << 31) && rows * (int64_t)cin * 4 < (1ll << 31) &&
                           (!res_dev || rows * (int64_t)ldr * 4 < (1ll << 31)) && (((uintptr_t)x_dev | (uintptr_t)w_packed_dev) & 15) == 0 &&
                           (cp == 2 || cp == 3 || cp == 5 || cp == 6 || cp == 11 || cp == 12);
         if (strm) {
-            static int cus_strm[16] = {};
-            if (!cus_strm[dev]) VSC_CHECK_HIP(hipDeviceGetAttribute(&cus_strm[dev], hipDeviceAttributeMultiprocessorCount, dev));
             const int tp = cp <= 6 ? 128 : 64, groups = (cout + 127) / 128;
             ExpandArgs a{x_dev, w_packed_dev, bias_dev, res_dev, out_dev, rows, (rows + tp - 1) / tp, cout, ldo, ldr, act};
-            const int resident = cus_strm[dev] * (cp <= 3 ? 4 : 3);
+            const int resident = cus * (cp <= 3 ? 4 : 3);
             const int per = resident / groups > 0 ? resident / groups : 1;
             const dim3 grid((unsigned)(a.ntiles < per ? a.ntiles : per), groups);
 #define VSC_STRM(C) hipLaunchKernelGGL(conv1x1_stream_kernel<C>, grid, dim3(256), 0, stream, a, cin, kpad)
@@ -1842,11 +1832,9 @@ extern "C" int vsc_conv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_t 
     }
     // 1 x 1, stride 1, dense rows of a multiple of 32 channels: the input IS the patch matrix
     const bool in_place = kh == 1 && kw == 1 && stride == 1 && pad == 0 && ldx == cin && (cin % KS) == 0 && (((uintptr_t)x_dev) & 15) == 0;
-    const char *nm = vsc_opt(OPT_CONV_NARROW_MAX);
-    const bool narrow = cout <= (nm ? atoi(nm) : 160);   // <= 5 channel tiles of 32 (VSC_CONV_NARROW_MAX): the thin and the 144-wide layers (see conv_gemm_narrow_kernel)
+    const bool narrow = cout <= vsc_opt_int(OPT_CONV_NARROW_MAX, 160);   // <= 5 channel tiles of 32 (VSC_CONV_NARROW_MAX): the thin and the 144-wide layers (see conv_gemm_narrow_kernel)
     // patches gathered inside the GEMM's staging (narrow kernel): 4-channel chunks, table-sized K, 16-bit image coordinates
-    const char *imp_env = vsc_opt(OPT_CONV_IMPLICIT);   // diagnostic / test switch, read per call
-    const bool no_implicit = imp_env && imp_env[0] == '0';
+    const bool no_implicit = vsc_opt_is(OPT_CONV_IMPLICIT, '0');   // diagnostic / test switch, read per call
     const bool implicit = !in_place && narrow && !no_implicit && (cin & 3) == 0 && (ldx & 3) == 0 && (((uintptr_t)x_dev) & 15) == 0 &&
                           kpad <= IM2COL_TABLE && kh < 16 && kw < 16 && h < 32000 && w < 32000 && pad < 1000;
     // The per-device scratch (zero line, patch matrix, CU count) is guarded; the patch matrix itself is ONE buffer per
@@ -1888,29 +1876,25 @@ extern "C" int vsc_conv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_t 
                            h, w, cin, ldx, kh, kw, stride, pad, ho, wo, k, kpad);
     }
     VSC_CHECK_LAUNCH();
-    static int cus_of[16] = {};
-    if (!cus_of[dev]) VSC_CHECK_HIP(hipDeviceGetAttribute(&cus_of[dev], hipDeviceAttributeMultiprocessorCount, dev));
-    const char *pe = vsc_opt(OPT_CONV_PERSIST);   // diagnostic: 0 = one tile per workgroup
-    const char *se = vsc_opt(OPT_CONV_STAGES);    // diagnostic: 3 = three LDS stages, one workgroup per CU
-    const char *we = vsc_opt(OPT_CONV_WAVES);     // diagnostic: 4 = four waves per workgroup
+    const bool no_persist = vsc_opt_is(OPT_CONV_PERSIST, '0');   // diagnostic: 0 = one tile per workgroup
+    const int stages = vsc_opt_is(OPT_CONV_STAGES, '3') ? 3 : 2;   // diagnostic: 3 = three LDS stages, one workgroup per CU
+    const int nw = vsc_opt_is(OPT_CONV_WAVES, '4') ? 4 : 8;        // diagnostic: 4 = four waves per workgroup
     const char *te = vsc_opt(OPT_CONV_NARROW_NT); // diagnostic: 1 / 2 = 128- / 256-pixel tiles for every narrow layer
-    const int stages = se && se[0] == '3' ? 3 : 2;
-    const int nw = we && we[0] == '4' ? 4 : 8;
     const int tiles_c = narrow ? (cout + NARROW_C - 1) / NARROW_C : (cout + TR - 1) / TR;
     // 128-pixel tiles (four waves, three workgroups per CU) when the 256-pixel list spills a partial second round over the chip's
     // 2 x CUs slots (72 @ 56 x 56: 588 tiles, 100 -> 95 us) or leaves most CUs without a workgroup (144 -> 20 @ 28 x 28: 49 tiles,
     // 18 -> 13 us); measured worse for lists of 245 / 392 (one round either way) and >= 1568 tiles
     const int64_t tiles256 = ((rows + 255) / 256) * tiles_c;
     const bool small = narrow && nw == 8 &&
-                       (te ? te[0] == '1' : ((tiles256 > 2ll * cus_of[dev] && tiles256 < 4ll * cus_of[dev]) || 2 * tiles256 <= cus_of[dev]));
+                       (te ? te[0] == '1' : ((tiles256 > 2ll * cus && tiles256 < 4ll * cus) || 2 * tiles256 <= cus));
     const int narrow_p = small ? 128 : 256;
     const int64_t tiles_p = narrow ? (rows + narrow_p - 1) / narrow_p : (rows + TQ - 1) / TQ;
     VSC_REQUIRE(tiles_p * tiles_c < (1ll << 31), "conv2d: grid too large");
     ConvGemmArgs a{w_packed_dev, in_place ? x_dev : (const float *)s.ptr, bias_dev, res_dev, out_dev, rows, cout, kpad, ldo, ldr, act, tiles_c, tiles_p,
                    x_dev, g_zero_line[dev], h, w, cin, ldx, kh, kw, stride, pad, ho, wo, k, 0};
-    if (const char *e = vsc_opt(OPT_CONV_REMAP)) a.no_remap = e[0] == '0';
-    const int64_t resident = (small ? (stages == 3 ? 2ll : 3ll) : stages == 2 ? 2ll : 1ll) * cus_of[dev];   // LDS per workgroup: 44 / 64 KiB (128 pixels), 76 / 112 KiB
-    const unsigned ngrid = (unsigned)((pe && pe[0] == '0') || tiles_p * tiles_c < resident ? tiles_p * tiles_c : resident);
+    a.no_remap = vsc_opt_is(OPT_CONV_REMAP, '0');
+    const int64_t resident = (small ? (stages == 3 ? 2ll : 3ll) : stages == 2 ? 2ll : 1ll) * cus;   // LDS per workgroup: 44 / 64 KiB (128 pixels), 76 / 112 KiB
+    const unsigned ngrid = (unsigned)(no_persist || tiles_p * tiles_c < resident ? tiles_p * tiles_c : resident);
     if (narrow) {
 #define VSC_NARROW(I, S, W) hipLaunchKernelGGL((conv_gemm_narrow_kernel<I, S, W>), dim3(ngrid), dim3(W * 64), 0, stream, a)
         if (small && stages == 3) { if (implicit) hipLaunchKernelGGL((conv_gemm_narrow_kernel<true, 3, 4, 1>), dim3(ngrid), dim3(256), 0, stream, a);
@@ -1939,8 +1923,8 @@ extern "C" int vsc_dwconv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_
     const size_t wbytes = (size_t)kh * kw * c * 4;
     const bool aligned = ((((uintptr_t)x_dev) | ((uintptr_t)out_dev) | (bias_dev ? (uintptr_t)bias_dev : 0)) & 15) == 0;
     const size_t small_bytes = ((size_t)kh * kw + (size_t)h * w) * DW_SLAB * 4;
-    const char *se = vsc_opt(OPT_DWCONV_SMALL);   // diagnostic / test switch: 0 = the row kernel
-    if ((c & 3) == 0 && aligned && small_bytes <= 40 * 1024 && n < (1ll << 31) && !(se && se[0] == '0')) {
+    // diagnostic / test switch VSC_DWCONV_SMALL: 0 = the row kernel
+    if ((c & 3) == 0 && aligned && small_bytes <= 40 * 1024 && n < (1ll << 31) && !vsc_opt_is(OPT_DWCONV_SMALL, '0')) {
         // small maps: a workgroup per (64-channel slab, image group), about eight workgroups per CU in flight
         const int slabs = (c + DW_SLAB - 1) / DW_SLAB;
         int64_t gy = 2048 / slabs;
@@ -1948,13 +1932,7 @@ extern "C" int vsc_dwconv2d_f32(const float *x_dev, int64_t n, int32_t h, int32_
         hipLaunchKernelGGL(dwconv_small_kernel, dim3(slabs, (unsigned)gy), dim3(256), small_bytes, (hipStream_t)stream_, x_dev, w_dev, bias_dev,
                            out_dev, (int)n, h, w, c, kh, kw, stride, pad, ho, wo, act);
     } else if ((c & 3) == 0 && aligned && wbytes <= 64 * 1024 && n * ho < (1ll << 31)) {
-        static bool attr_set[16] = {};
-        int dev = 0;
-        VSC_CHECK_HIP(hipGetDevice(&dev));
-        if (dev >= 16 || !attr_set[dev]) {
-            VSC_CHECK_HIP(hipFuncSetAttribute((const void *)dwconv_rows_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024));
-            if (dev < 16) attr_set[dev] = true;
-        }
+        VSC_TRY(vsc_allow_dynamic_lds(dwconv_rows_kernel, 64 * 1024));
         int bx = (wo * (c / 4) + 255) / 256;
         bx = bx > 64 ? 64 : bx;
         hipLaunchKernelGGL(dwconv_rows_kernel, dim3((unsigned)(n * ho), bx), dim3(256), wbytes, (hipStream_t)stream_, x_dev, w_dev, bias_dev,
@@ -1988,13 +1966,7 @@ extern "C" int vsc_se_block_f32(float *x_dev, int64_t n, int32_t hw, int32_t c, 
     VSC_REQUIRE((c & 3) == 0 && (((uintptr_t)x_dev) & 15) == 0, "se_block: channels must be a multiple of 4 and x 16-byte aligned");
     const size_t lds = ((size_t)hw * c + 2 * c + cr) * 4;
     VSC_REQUIRE(lds <= 150 * 1024, "se_block: a %d x %d map does not fit LDS (%zu bytes): use avgpool + conv2d + channel_scale", hw, c, lds);
-    static bool attr_set[16] = {};
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)se_block_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-        if (dev >= 0 && dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(se_block_kernel, 150 * 1024));
     const int kpad1 = vsc_conv_packed_k(c, 1, 1), kpad2 = vsc_conv_packed_k(cr, 1, 1);
     hipLaunchKernelGGL(se_block_kernel, dim3((unsigned)n), dim3(512), lds, (hipStream_t)stream_, x_dev, w1_packed_dev, b1_dev, kpad1, w2_packed_dev, b2_dev,
                        kpad2, hw, c, cr, act1, act2);

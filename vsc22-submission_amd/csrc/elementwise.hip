@@ -517,8 +517,8 @@ int launch_layernorm(const float *x, const float *g, const float *b, void *out, 
     VSC_REQUIRE(x && g && b && out && rows > 0, "layernorm: null/empty");
     VSC_REQUIRE(width % 4 == 0 && width <= MAXV * 256, "layernorm: width %d unsupported", width);
     VSC_REQUIRE((rows + 3) / 4 < (1ll << 31), "layernorm: too many rows");
-    const char *lt = vsc_opt(OPT_LN_LIGHT);   // diagnostic: 0 = the 50-register kernel for every width
-    if ((width == 768 || width == 1024) && rows < (1ll << 31) && !(lt && lt[0] == '0')) {
+    // diagnostic: VSC_LN_LIGHT=0 = the 50-register kernel for every width
+    if ((width == 768 || width == 1024) && rows < (1ll << 31) && !vsc_opt_is(OPT_LN_LIGHT, '0')) {
         const dim3 grid1((unsigned)rows);
         if (width == 768) {
             if (out_f32) hipLaunchKernelGGL((layernorm_light_kernel<true, 3>), grid1, dim3(64), 0, stream, x, g, b, out, eps);
@@ -543,14 +543,8 @@ int launch_ln_pool(const float *x, const float *g, const float *b, float *pooled
                    int64_t frames, int tokens, int width, float eps, int pool, float gem_p,
                    hipStream_t stream) {
     VSC_REQUIRE(width % 4 == 0 && width <= 2048, "ln_pool: width %d unsupported", width);
-    static bool attr_set[16] = {};
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)ln_pool_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * 1024 * 4));
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)ln_pool_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 8 * 2048 * 4));
-        if (dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(ln_pool_kernel<16>, 16 * 1024 * 4));
+    VSC_TRY(vsc_allow_dynamic_lds(ln_pool_kernel<8>, 8 * 2048 * 4));
     if (width <= 1024)
         hipLaunchKernelGGL(ln_pool_kernel<16>, dim3((unsigned)frames), dim3(1024), 16 * width * 4, stream, x, g, b, pooled, tokens_out,
                            tokens, width, eps, pool, gem_p);

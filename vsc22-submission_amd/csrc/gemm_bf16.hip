@@ -737,15 +737,7 @@ template <int EPI>
 int launch_v3(GemmArgs p, hipStream_t stream) {
     constexpr int smem = ml64::RING_BYTES + 4096;   // ring (== 8 waves x 16 KiB of write-out staging) + the epilogue constants
     auto kern = gemm_bf16_v3_kernel<EPI>;
-    static bool attr_set[16] = {};
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 16 && !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        attr_set[dev] = true;
-    } else if (dev >= 16) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
     p.tiles_m = (int)((p.m + 255) / 256);
     p.tiles_n = (p.n + 255) / 256;
     // N-group width (tile order): groups of 4 N-tiles whatever K is.  Swept on the ViT shapes with this loop (G = 1..12,
@@ -754,7 +746,7 @@ int launch_v3(GemmArgs p, hipStream_t stream) {
     // groups of 4 N-tiles; of 3 where that divides the row of tiles and 4 does not (qkv: 9 = 3 + 3 + 3 instead of 4 + 4 + 1:
     // 204 -> 199.5 us on the persistent kernel, tools/micro/gemm_v4_groups.py)
     int g = (p.tiles_n % 4 != 0 && p.tiles_n % 3 == 0) ? 3 : 4;
-    if (const char *e = vsc_opt(OPT_GEMM_GROUP_N)) g = atoi(e);
+    g = vsc_opt_int(OPT_GEMM_GROUP_N, g);
     p.group_n = g < 1 ? 1 : (g > p.tiles_n ? p.tiles_n : g);
     p.skew = 0;
     hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(512), smem, stream, p);
@@ -1236,17 +1228,11 @@ int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
     constexpr int smem_max = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + 12 * 2048 : 2048);
     const int smem = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + p.ex.nslices * 2048 : 2048);
     auto kern = gemm_bf16_v4_kernel<EPI>;
-    static bool attr_set[16] = {};
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem_max));
-        if (dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(kern, smem_max));
     // groups of 4 N-tiles; of 3 where that divides the row of tiles and 4 does not (qkv: 9 = 3 + 3 + 3 instead of 4 + 4 + 1:
     // 204 -> 199.5 us on the persistent kernel, tools/micro/gemm_v4_groups.py)
     int g = (p.tiles_n % 4 != 0 && p.tiles_n % 3 == 0) ? 3 : 4;
-    if (const char *e = vsc_opt(OPT_GEMM_GROUP_N)) g = atoi(e);
+    g = vsc_opt_int(OPT_GEMM_GROUP_N, g);
     p.group_n = g < 1 ? 1 : (g > p.tiles_n ? p.tiles_n : g);
     p.skew = 0;
     p.skew_groups = 1;
@@ -1255,9 +1241,8 @@ int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
         // the row's two tiles (t, t ^ 1) must land on workgroups (b, b ^ 8) of the same round: N-groups spanning the whole row
         // of tiles, no diagnostic regrouping, one workgroup on every CU, whole pairs per round
         p.group_n = p.tiles_n;
-        int dev_cus = 0, dev = 0;
-        VSC_CHECK_HIP(hipGetDevice(&dev));
-        VSC_CHECK_HIP(hipDeviceGetAttribute(&dev_cus, hipDeviceAttributeMultiprocessorCount, dev));
+        int dev_cus = 0;
+        VSC_TRY(vsc_device_cus(&dev_cus));
         // (grid < CUs -- the VSC_GEMM_V4_GRID diagnostic -- keeps every workgroup resident as well; the exchange slots are sized for 256)
         VSC_REQUIRE(cus <= dev_cus && cus <= 256 && cus % 16 == 0, "gemm LN_RES: the pair exchange needs every workgroup resident, in whole pairs per XCD (grid %d, device %d CUs)", cus, dev_cus);
         VSC_REQUIRE(p.tiles_n == 1 || (p.tiles_n == 2 && ((int64_t)p.tiles_m * p.tiles_n) % 16 == 0),
@@ -1302,16 +1287,9 @@ int launch_v34(GemmArgs p, hipStream_t stream) {
     p.tiles_m = (int)((p.m + 255) / 256);
     p.tiles_n = (p.n + 255) / 256;
     if constexpr (epi_v4(EPI)) {
-        const char *v4e = vsc_opt(OPT_GEMM_V4);   // diagnostic A/B switch, read per launch
-        const bool off = v4e && v4e[0] == '0';
-        static int cus_of[16] = {};
-        int dev = 0;
-        VSC_CHECK_HIP(hipGetDevice(&dev));
-        int cus = dev < 16 ? cus_of[dev] : 0;
-        if (!cus) {
-            VSC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            if (dev < 16) cus_of[dev] = cus;
-        }
+        const bool off = vsc_opt_is(OPT_GEMM_V4, '0');   // diagnostic A/B switch, read per launch
+        int cus = 0;
+        VSC_TRY(vsc_device_cus(&cus));
         const int64_t a_span = (int64_t)p.tiles_m * 256 * p.k * 2, w_span = (int64_t)p.tiles_n * 256 * p.k * 2;
         // (K > 3072: the per-tile costs v4 removes are < 1 % of a tile and its lockstep costs ~3 % -- 8192^3 680 vs 701 us)
         // fp32 write-outs address [m, n] by 32-bit byte offsets from the matrix origin, rows of the last (ragged) tile included
@@ -1323,10 +1301,8 @@ int launch_v34(GemmArgs p, hipStream_t stream) {
             int grid = cus;
             // diagnostic: persistent workgroups per launch (a multiple of 8).  Measured with two lanes, so that the two chunks' GEMMs run
             // side by side on half the chip each instead of one after the other: 128 -> 23.4 k, 192 -> 23.4 k, 256 -> 23.9 k frames/s
-            if (const char *e = vsc_opt(OPT_GEMM_V4_GRID)) {
-                const int g = atoi(e);
-                if (g >= 8 && g <= cus && g % 8 == 0) grid = g;
-            }
+            const int g = vsc_opt_int(OPT_GEMM_V4_GRID, 0);
+            if (g >= 8 && g <= cus && g % 8 == 0) grid = g;
             if constexpr (epi_lnf(EPI)) {
                 // statistics given as slice partials: merged per tile inside the kernel when they fit behind the ring (<= 12 slices)
                 if (p.ex.slices && p.ex.nslices > 12) {
@@ -1354,9 +1330,7 @@ int launch_v34(GemmArgs p, hipStream_t stream) {
 // first 256 workgroups.  Re-measured in the ViT step with skews from 0.6 us to a whole tile time: 0 is as fast as any
 // (19.7 k frames/s), a tile time costs 6 % -- the start-up delay is never recovered.
 inline int skew_cycles(int k) {
-    const char *e = vsc_opt(OPT_GEMM_SKEW_NS_PER_K);
-    const int ns_per_k = e ? atoi(e) : 0;
-    return (int)((int64_t)ns_per_k * k / 10);
+    return (int)((int64_t)vsc_opt_int(OPT_GEMM_SKEW_NS_PER_K, 0) * k / 10);
 }
 
 template <int EPI, int WAVES_M, int WAVES_N, int TM, int TN, int STAGES>
@@ -1366,13 +1340,7 @@ int launch_v2(GemmArgs p, hipStream_t stream) {
     constexpr int ring = STAGES * (BM2 + BN2) * 64;
     constexpr int smem = ring > NW * 16384 ? ring : NW * 16384;
     auto kern = gemm_bf16_v2_kernel<EPI, WAVES_M, WAVES_N, TM, TN, STAGES>;
-    static bool attr_set[16] = {};   // per device
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        if (dev >= 0 && dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
     p.tiles_m = (int)((p.m + BM2 - 1) / BM2);
     p.tiles_n = (p.n + BN2 - 1) / BN2;
     // W panel of one N-group (G tiles x K) should sit in a 4 MiB XCD L2 next to the A panels: every N-group is one
@@ -1380,7 +1348,7 @@ int launch_v2(GemmArgs p, hipStream_t stream) {
     // 3 passes over its 402 MB A (larger than the Infinity Cache) under the L2 rule: 395 -> 330 us with one.
     int g = (int)((int64_t)(3 << 19) / ((int64_t)BN2 * p.k * 2));
     if (p.tiles_n <= 4) g = p.tiles_n;
-    if (const char *e = vsc_opt(OPT_GEMM_GROUP_N)) g = atoi(e);
+    g = vsc_opt_int(OPT_GEMM_GROUP_N, g);
     p.group_n = g < 1 ? 1 : (g > p.tiles_n ? p.tiles_n : g);
     p.skew = skew_cycles(p.k);
 #ifdef VSC_GEMM_TIMING
@@ -1435,8 +1403,7 @@ int launch_v2_pick(const GemmArgs &p, hipStream_t stream) {
         if (epi_v4(EPI) && p.k % 128 == 0 && p.k >= 128 && p.n % 256 == 0 && ((p.m + 255) / 256) * (p.n / 256) > 256) cfg = 'A';
     }
     if (force) cfg = force[0];
-    const char *v3e = vsc_opt(OPT_GEMM_V3);   // diagnostic A/B switch, read per launch
-    const bool no_v3 = v3e && v3e[0] == '0';
+    const bool no_v3 = vsc_opt_is(OPT_GEMM_V3, '0');   // diagnostic A/B switch, read per launch
     if (cfg == 'A' && p.k % 64 == 0 && !no_v3) return launch_v34<EPI>(p, stream);
     switch (cfg) {
         case 'A': return launch_v2<EPI, 2, 4, 8, 4, 4>(p, stream);
@@ -1699,13 +1666,7 @@ int launch_ln_t(const GemmLnArgs &p, hipStream_t stream) {
     constexpr int ring = STAGES * (WAVES_M * 64 + WAVES_N * 128) * 64;
     constexpr int smem = ring > 8 * 16384 + 8192 ? ring : 8 * 16384 + 8192;
     auto kern = gemm_ln_kernel<WAVES_M, WAVES_N, STAGES>;
-    static bool attr_set[16] = {};   // per device
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        if (dev >= 0 && dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
     const int64_t blocks = (p.m + WAVES_M * 64 - 1) / (WAVES_M * 64);
     VSC_REQUIRE(blocks < (1ll << 31), "gemm_ln: grid too large");
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), smem, stream, p);
@@ -1741,9 +1702,8 @@ int launch_gemm_bf16_ex(const uint16_t *a, const uint16_t *w, const float *bias,
     const int tiles_n = (n + BN - 1) / BN;
     VSC_REQUIRE(tiles_m * tiles_n < (1ll << 31), "gemm: grid too large");
     GemmArgs p{a, w, bias, aux, out, m, n, k, tokens, tiles_n, (int)tiles_m, 1, 0};
-    p.abl = 0;
+    p.abl = vsc_opt_int(OPT_GEMM_ABL, 0);
     p.ex = ex;
-    if (const char *e = vsc_opt(OPT_GEMM_ABL)) p.abl = atoi(e);
     const bool force_v1 = vsc_opt(OPT_GEMM_V1) != nullptr;
     const bool force_v2 = vsc_opt(OPT_GEMM_CFG) != nullptr;
     // A launch that cannot put a 256-row tile on at least half the CUs runs the 128 x 128 kernel instead (four times
@@ -1844,26 +1804,19 @@ int launch_gemm_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias,
     {
         const int64_t tiles_m = (m + 255) / 256;
         const int tiles_n = n / 256;
-        const char *opt = vsc_opt(OPT_GEMM_LN_V4);
         int dev = 0, cus = 0;
-        VSC_CHECK_HIP(hipGetDevice(&dev));
-        static int cus_of[16] = {};
-        if (dev >= 0 && dev < 16 && cus_of[dev]) cus = cus_of[dev];
-        else {
-            VSC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-            if (dev >= 0 && dev < 16) cus_of[dev] = cus;
-        }
+        VSC_TRY(vsc_device_cus(&cus, &dev));
         const bool shape_ok = (n == 256 || (n == 512 && tiles_m % 8 == 0)) && k % 128 == 0 && k >= 128 && k <= 3072 && cus == 256 &&
                               tiles_m * tiles_n > cus && tiles_m * 256 * k * 2 < (1ll << 32) && tiles_m * 256 * n * 4 < (1ll << 32) &&
-                              dev >= 0 && dev < 16;
+                              dev >= 0 && dev < VSC_MAX_DEVICES;   // (dev_ws below)
         // Where it pays (tools/micro/gemm_ln_ab.py, 256 Swin-V2-B frames; round 4, with the write-out on buffer operations and no
         // spill left): N = 512 from K = 512 on -- s2 proj 96 vs 100 us, s2 fc2 166 vs 195, the un-gathered merge shape 114 vs
         // 128; at N = 256 the short-K launch ties (s1 proj 168 vs 168: bound by its bytes whichever kernel runs it) and stays
         // on the row-owning tile.  VSC_GEMM_LN_V4=1 forces the persistent kernel on every shape it supports (tests), 0
         // switches it off.
         const bool pays = n == 512 && k >= 512;
-        if (shape_ok && merge_res == 0 && !(opt && opt[0] == '0') && (pays || (opt && opt[0] == '1'))) {
-            static void *dev_ws[16] = {};   // callers without a workspace of their own: one call at a time per device
+        if (shape_ok && merge_res == 0 && !vsc_opt_is(OPT_GEMM_LN_V4, '0') && (pays || vsc_opt_is(OPT_GEMM_LN_V4, '1'))) {
+            static void *dev_ws[VSC_MAX_DEVICES] = {};   // callers without a workspace of their own: one call at a time per device
             if (!pair_ws) {
                 if (!dev_ws[dev]) VSC_CHECK_HIP(hipMalloc(&dev_ws[dev], VSC_GEMM_LN_WS_BYTES));
                 pair_ws = dev_ws[dev];
@@ -1877,10 +1830,8 @@ int launch_gemm_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias,
             p.ex.xch = (float *)pair_ws;
             p.ex.xflags = (int *)((char *)pair_ws + 2 * 256 * 256 * 2 * 4);
             int grid = cus;
-            if (const char *e = vsc_opt(OPT_GEMM_V4_GRID)) {   // diagnostic, as in launch_v34
-                const int g = atoi(e);
-                if (g >= 16 && g <= cus && g % 16 == 0 && tiles_m * tiles_n >= g) grid = g;
-            }
+            const int g = vsc_opt_int(OPT_GEMM_V4_GRID, 0);   // diagnostic, as in launch_v34
+            if (g >= 16 && g <= cus && g % 16 == 0 && tiles_m * tiles_n >= g) grid = g;
             if (tiles_n == 2) {
                 // The epoch lives on the host and is baked into the kernel arguments: a captured launch replayed from a HIP graph would
                 // wait for flag values of the capture, not of the replay -- refuse stream capture (common.h: the workspace contract).

@@ -1312,14 +1312,14 @@ struct Scratch {
     void *ptr = nullptr;
     size_t bytes = 0;
 };
-constexpr int MAX_DEVICES = 16, SCRATCH_SLOTS = 24;
-Scratch g_scratch[MAX_DEVICES][SCRATCH_SLOTS];
+constexpr int SCRATCH_SLOTS = 24;
+Scratch g_scratch[VSC_MAX_DEVICES][SCRATCH_SLOTS];
 std::mutex g_scratch_mutex;
 
 int scratch_get(int slot, size_t bytes, void **out) {
     int dev = 0;
     VSC_CHECK_HIP(hipGetDevice(&dev));
-    VSC_REQUIRE(dev >= 0 && dev < MAX_DEVICES && slot < SCRATCH_SLOTS, "knn: device %d / slot %d out of range", dev, slot);
+    VSC_REQUIRE(dev >= 0 && dev < VSC_MAX_DEVICES && slot < SCRATCH_SLOTS, "knn: device %d / slot %d out of range", dev, slot);
     std::lock_guard<std::mutex> lock(g_scratch_mutex);
     Scratch &s = g_scratch[dev][slot];
     if (bytes < 16) bytes = 16;
@@ -1345,7 +1345,7 @@ int scratch_get(int slot, size_t bytes, void **out) {
 // frees every grow-only scratch buffer of the current device (waits for the device first); -> bytes released
 int64_t scratch_release() {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAX_DEVICES) return 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= VSC_MAX_DEVICES) return 0;
     std::lock_guard<std::mutex> lock(g_scratch_mutex);
     (void)hipDeviceSynchronize();
     int64_t freed = 0;
@@ -1477,14 +1477,8 @@ static int sweep_plan(int64_t nq, int64_t nr, int dp, SweepPlan *out) {
     pl.nqb = (int)((nq + SQ - 1) / SQ);
     pl.total_tiles = (nr + SR - 1) / SR;
     int64_t want = 1;
-    int dev = 0, cus = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    static int cus_of[MAX_DEVICES] = {};
-    if (dev >= 0 && dev < MAX_DEVICES && cus_of[dev]) cus = cus_of[dev];
-    else {
-        VSC_CHECK_HIP(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-        if (dev >= 0 && dev < MAX_DEVICES) cus_of[dev] = cus;
-    }
+    int cus = 0;
+    VSC_TRY(vsc_device_cus(&cus));
     // The number of reference splits by a cost model, in units of "one workgroup sweeps the whole bank":
     //   plain order     nqb * w items dealt in rounds of 256, an item = 1 / w of the bank:   ceil(nqb w / 256) / w
     //   XCD-aware order super-items of 8 query blocks x 4 splits, one per XCD at a time (see the kernel), w = 4 c:
@@ -1501,11 +1495,10 @@ static int sweep_plan(int64_t nq, int64_t nr, int dp, SweepPlan *out) {
         const double c = (double)((pl.nqb * w + 255) / 256) / (double)w * (1.0 + alpha * (double)(w - 1));
         if (c < best - 1e-9) { best = c; want = w; }
     }
-    const char *xe = vsc_opt(OPT_KNN_XCD_MAP);
     // XCD-aware order: only for calls of 8 .. 64 query blocks (VSC_KNN_XCD_MAP=1: any size from 8 blocks; =0: never)
-    const bool forced = xe && xe[0] == '1';
+    const bool forced = vsc_opt_is(OPT_KNN_XCD_MAP, '1');
     bool xmap = false;
-    if (cus == 256 && pl.nqb >= 8 && pl.total_tiles >= 32 && !(xe && xe[0] == '0') && (pl.nqb <= 64 || forced)) {
+    if (cus == 256 && pl.nqb >= 8 && pl.total_tiles >= 32 && !vsc_opt_is(OPT_KNN_XCD_MAP, '0') && (pl.nqb <= 64 || forced)) {
         const int nqg = (pl.nqb + 7) / 8;
         double xbest = 1e30;
         int64_t xwant = 0;
@@ -1541,11 +1534,11 @@ static int launch_sweep_t(const SweepArgs &a, int grid, hipStream_t stream) {
     constexpr int smem = ml64::RING_BYTES + 5120 + 8 * 4 * 64 * 12;
     if (a.abl) {   // diagnostics requested (VSC_KNN_ABL): the instrumented build of the kernel
         auto kern = knn_sweep_bf16_kernel<EPL, STREAM, true>;
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, a);
     } else {
         auto kern = knn_sweep_bf16_kernel<EPL, STREAM, false>;
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+        VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
         hipLaunchKernelGGL(kern, dim3(grid), dim3(512), smem, stream, a);
     }
     VSC_CHECK_LAUNCH();
@@ -1609,12 +1602,12 @@ static int knn_prefilter(const float *q_dev, int64_t nq, const float *r_dev, int
         hipLaunchKernelGGL(knn_set_floor_kernel, dim3(blocks_for(nq)), dim3(256), 0, stream, floor_dev, (float *)qstats, nq);
         VSC_CHECK_LAUNCH();
     }
-    if (const char *e = vsc_opt(OPT_KNN_TRIG)) { const int t = atoi(e); if (t >= k && t <= cap - 2 * SR) a.trig = t; }
+    if (const int t = vsc_opt_int(OPT_KNN_TRIG, 0); t >= k && t <= cap - 2 * SR) a.trig = t;
     a.delta = cap;   // measured (tools/micro/knn_trig.py, 65536 x 1M, k = 100): 64 / 100 / 150 / 200 / 400 appends between compactions -> 79.6 / 73.4 / 71.0 / 68.7 / 66.8 ms: the
                      // appends are already within 25 % of their floor (the 2 eps band doubles the effective k), rounds stall the workgroup
-    if (const char *e = vsc_opt(OPT_KNN_DELTA)) { const int t = atoi(e); if (t >= 16 && t <= cap) a.delta = t; }
+    if (const int t = vsc_opt_int(OPT_KNN_DELTA, 0); t >= 16 && t <= cap) a.delta = t;
     a.dbg = (unsigned long long *)(((uintptr_t)(fb_dev + 1 + nqb) + 7) & ~(uintptr_t)7);
-    if (const char *e = vsc_opt(OPT_KNN_ABL)) a.abl = atoi(e);
+    a.abl = vsc_opt_int(OPT_KNN_ABL, 0);
     if ((rc = epl == 16 ? launch_sweep<16>(a, grid, stream) : launch_sweep<32>(a, grid, stream))) return rc;
     knn_mark(2, stream);
     // re-scoring and the merge across splits: per (query, split) list, or -- after the union -- per query
@@ -1634,8 +1627,8 @@ static int knn_prefilter(const float *q_dev, int64_t nq, const float *r_dev, int
         lstride = splits;
     }
     const unsigned rgrid = (unsigned)((rlists + 3) / 4);
-    VSC_CHECK_HIP(hipFuncSetAttribute((const void *)knn_rescore_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 64 * 36 * 4));
-    VSC_CHECK_HIP(hipFuncSetAttribute((const void *)knn_rescore_kernel<16>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 64 * 36 * 4));
+    VSC_TRY(vsc_allow_dynamic_lds(knn_rescore_kernel<8>, 4 * 2 * 64 * 36 * 4));
+    VSC_TRY(vsc_allow_dynamic_lds(knn_rescore_kernel<16>, 4 * 2 * 64 * 36 * 4));
     if (epl == 16)
         hipLaunchKernelGGL(knn_rescore_kernel<8>, dim3(rgrid), dim3(256), 4 * 2 * 64 * 36 * 4, stream, q_dev, r_dev, rlists, d, rsplits,
                            k, (const unsigned long long *)cand, (const int *)ncand, (unsigned long long *)part, PairMaxOut{}, lstride);
@@ -1796,10 +1789,9 @@ static int knn_ip_impl(const float *q_dev, int64_t nq, const float *r_dev, int64
         // (Round 5, second step: from 257 blocks on -- 70 000 x 1M ran two rounds, 107 ms, for 1.07 rounds of work -- and decided by the
         // plan's cost model instead of a fixed window of remainders.)
         const int64_t nqb = (nq + SQ - 1) / SQ, rem = nqb % 256;
-        const char *tb = vsc_opt(OPT_KNN_TAIL);
         g_knn_set = 0;
         bool split_tail = false;
-        if (!(tb && tb[0] == '0') && nqb > 256 && rem != 0) {
+        if (!vsc_opt_is(OPT_KNN_TAIL, '0') && nqb > 256 && rem != 0) {
             // by the plan's own cost model: whole rounds at one split + the tail's best plan + a second pack of the bank and the
             // launches (~0.05 of a round), against the best plan for the call as a whole
             const int dp = prefilter_dp(d);
@@ -1890,7 +1882,7 @@ static int range_prefilter(const float *q_dev, int64_t nq, const float *r_dev, i
     if ((rc = launch_sweep<EPL>(a, grid, stream))) return rc;
     const unsigned rgrid = (unsigned)((nlists + 3) / 4);
     auto rk = knn_rescore_kernel<EPL / 2, 2>;
-    VSC_CHECK_HIP(hipFuncSetAttribute((const void *)rk, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 64 * 36 * 4));
+    VSC_TRY(vsc_allow_dynamic_lds(rk, 4 * 2 * 64 * 36 * 4));
     PairMaxOut pm{};
     pm.thr = radius;
     pm.counts = (long long *)counts;
@@ -2106,7 +2098,7 @@ static int pair_max_prefilter(const float *q_dev, int64_t nq, const int32_t *qvi
     if ((rc = launch_sweep<EPL>(a, grid, stream))) return rc;
     const unsigned rgrid = (unsigned)((nlists + 3) / 4);
     auto rk = knn_rescore_kernel<EPL / 2, 1>;
-    VSC_CHECK_HIP(hipFuncSetAttribute((const void *)rk, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * 2 * 64 * 36 * 4));
+    VSC_TRY(vsc_allow_dynamic_lds(rk, 4 * 2 * 64 * 36 * 4));
     hipLaunchKernelGGL(rk, dim3(rgrid), dim3(256), 4 * 2 * 64 * 36 * 4, stream, q_dev, r_dev, nlists, d, splits, cap,
                        (const unsigned long long *)cand, (const int *)ncand, (unsigned long long *)nullptr,
                        PairMaxOut{qvid, rvid, table, (int64_t)n_r_videos, threshold}, 1);

@@ -922,16 +922,15 @@ int launch_window_attention(const uint16_t *qkv, uint16_t *out, const float *bia
     const int64_t grid = (int64_t)frames * nw * heads;
     VSC_REQUIRE(grid > 0 && grid < (1ll << 31), "window_attention: grid");
 #ifdef VSC_ATTN_ABLATION
-    if (ws == 16)
-        if (const char *e = vsc_opt(OPT_WATTN_ABL)) {
+    if (ws == 16) {
 #define VSC_WABL_CASE(A) case A: hipLaunchKernelGGL((window_attention_kernel<16, A>), dim3((unsigned)grid), dim3(512), 0, stream, qkv, out, bias, scale, res, ws, shift, heads); VSC_CHECK_LAUNCH(); return VSC_OK;
-            switch (atoi(e)) { VSC_WABL_CASE(1) VSC_WABL_CASE(2) VSC_WABL_CASE(3) VSC_WABL_CASE(8) VSC_WABL_CASE(16) VSC_WABL_CASE(24) VSC_WABL_CASE(27) default: break; }
+            switch (vsc_opt_int(OPT_WATTN_ABL, 0)) { VSC_WABL_CASE(1) VSC_WABL_CASE(2) VSC_WABL_CASE(3) VSC_WABL_CASE(8) VSC_WABL_CASE(16) VSC_WABL_CASE(24) VSC_WABL_CASE(27) default: break; }
         }
 #endif
-    const char *so = vsc_opt(OPT_WATTN_STREAM);   // diagnostic: 0 = the row-in-registers kernel for unshifted windows as well
-    if (ws == 16 && shift == 0 && !(so && so[0] == '0'))
+    const bool stream_off = vsc_opt_is(OPT_WATTN_STREAM, '0');   // diagnostic: 0 = the row-in-registers kernel for unshifted windows as well
+    if (ws == 16 && shift == 0 && !stream_off)
         hipLaunchKernelGGL(window_attention_stream_kernel, dim3((unsigned)grid), dim3(512), 0, stream, qkv, out, bias, scale, res, heads);
-    else if (ws == 16 && !(so && so[0] == '0')) {   // shifted 16 x 16 windows: the streamed kernel with masks (eight waves, 52 KiB: three workgroups per CU)
+    else if (ws == 16 && !stream_off) {   // shifted 16 x 16 windows: the streamed kernel with masks (eight waves, 52 KiB: three workgroups per CU)
         constexpr int n = 256, side = 31, tstride = (side + 3 + 3) & ~3;
         constexpr int smem = n * 64 + HD * (n * 2 + 32) + n * 4 + n + (4 * side * tstride + 4) * 4;
         hipLaunchKernelGGL((window_attention_wide_stream_kernel<16, 8>), dim3((unsigned)grid), dim3(512), smem, stream, qkv, out, bias, scale, res, shift, heads);
@@ -941,16 +940,10 @@ int launch_window_attention(const uint16_t *qkv, uint16_t *out, const float *bia
     else if (ws == 8)
         hipLaunchKernelGGL(window_attention_kernel<4>, dim3((unsigned)grid), dim3(128), 0, stream, qkv, out, bias,
                            scale, res, ws, shift, heads);
-    else if (ws == 24 && !(so && so[0] == '0')) {
+    else if (ws == 24 && !stream_off) {
         constexpr int n = 576, side = 47, tstride = (side + 3 + 3) & ~3;
         constexpr int smem = n * 64 + HD * (n * 2 + 32) + n * 4 + n + (4 * side * tstride + 4) * 4;
-        static bool attr_set[16] = {};
-        int dev = 0;
-        VSC_CHECK_HIP(hipGetDevice(&dev));
-        if (dev < 0 || dev >= 16 || !attr_set[dev]) {
-            VSC_CHECK_HIP(hipFuncSetAttribute((const void *)window_attention_wide_stream_kernel<24, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            if (dev >= 0 && dev < 16) attr_set[dev] = true;
-        }
+        VSC_TRY(vsc_allow_dynamic_lds(window_attention_wide_stream_kernel<24, 12>, smem));
         hipLaunchKernelGGL((window_attention_wide_stream_kernel<24, 12>), dim3((unsigned)grid), dim3(768), smem, stream, qkv, out, bias, scale, res, shift, heads);
     } else if (ws == 24 || ws == 12) {
         auto smem_of = [](int w) {
@@ -958,15 +951,8 @@ int launch_window_attention(const uint16_t *qkv, uint16_t *out, const float *bia
             return np * 64 + HD * (np * 2 + 32) + n * 4 + side * side * 4 + n + 16;
         };
         const int smem = smem_of(ws);
-        static bool attr_set[16][2] = {};
-        int dev = 0;
-        VSC_CHECK_HIP(hipGetDevice(&dev));
-        const int wi = ws == 24;
-        if (dev < 0 || dev >= 16 || !attr_set[dev][wi]) {
-            if (wi) VSC_CHECK_HIP(hipFuncSetAttribute((const void *)window_attention_wide_kernel<24>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            else VSC_CHECK_HIP(hipFuncSetAttribute((const void *)window_attention_wide_kernel<12>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            if (dev >= 0 && dev < 16) attr_set[dev][wi] = true;
-        }
+        const bool wi = ws == 24;
+        VSC_TRY(wi ? vsc_allow_dynamic_lds(window_attention_wide_kernel<24>, smem) : vsc_allow_dynamic_lds(window_attention_wide_kernel<12>, smem));
         if (wi) hipLaunchKernelGGL(window_attention_wide_kernel<24>, dim3((unsigned)grid), dim3(256), smem, stream, qkv, out, bias, scale, res, shift, heads);
         else hipLaunchKernelGGL(window_attention_wide_kernel<12>, dim3((unsigned)grid), dim3(256), smem, stream, qkv, out, bias, scale, res, shift, heads);
     } else

@@ -404,8 +404,7 @@ extern "C" int64_t vsc_swin_workspace_bytes(const vsc_swin *e) { return e ? e->w
 static int gemm_ln(vsc_swin *e, vsc_swin::Workspace &ws, const uint16_t *a, const uint16_t *w, const float *bias, const float *g, const float *b,
                    const float *x_in, float *x_out, uint16_t *xb_out, int64_t m, int n, int k, hipStream_t st) {
     const bool split = vsc_opt(OPT_SWIN_SPLIT_LN) != nullptr;
-    const char *split_k_opt = vsc_opt(OPT_SWIN_SPLIT_K);
-    const int split_k = split_k_opt ? atoi(split_k_opt) : 1 << 30;
+    const int split_k = vsc_opt_int(OPT_SWIN_SPLIT_K, 1 << 30);
     if (!split && k < split_k && gemm_ln_supported(n, k))
         return launch_gemm_ln_bf16(a, w, bias, g, b, x_in, x_out, xb_out, m, n, k, e->cfg.ln_eps, st, ws.lnws);
     int rc = launch_gemm_bf16(a, w, bias, nullptr, ws.t, m, n, k, VSC_EPI_F32, 0, st);
@@ -423,22 +422,16 @@ static int swin_run_chunks(vsc_swin *e, const float *frames, const uint8_t *fram
     int rc;
 #define TRY(x) do { if ((rc = (x))) return rc; } while (0)
 #define PROF(cls) SwinProfScope _ps(e, (cls), st)
-    const char *fm = vsc_opt(OPT_SWIN_FUSED_MLP);   // diagnostic / test switch: 0 = fc1 and fc2 as two GEMM launches
-    const bool unfused_mlp = fm && fm[0] == '0';
-    const char *f5 = vsc_opt(OPT_SWIN_MLP512);      // diagnostic / test switch: 0 = the 512-wide stage keeps fc1 and fc2 as two GEMM launches,
-    const bool unfused_mlp512 = f5 && f5[0] == '0';  // 1 = the fused kernel at every size (default: where its 128-row tiles fill the chip)
-    const bool forced_mlp512 = f5 && f5[0] == '1';
-    int cus512 = 256, dev512 = 0;
-    if (hipGetDevice(&dev512) != hipSuccess || hipDeviceGetAttribute(&cus512, hipDeviceAttributeMultiprocessorCount, dev512) != hipSuccess || cus512 <= 0)
-        cus512 = 256;
-    const char *f6 = vsc_opt(OPT_SWIN_PROJ512);     // diagnostic / test switch: 0 = the 512-wide stage keeps proj + LayerNorm as their own launch
-    const bool unfused_proj512 = f6 && f6[0] == '0';
-    const char *f7 = vsc_opt(OPT_SWIN_QKV512);      // diagnostic / test switch: 0 = every block of the 512-wide stage launches its own qkv GEMM
-    const bool unfused_qkv512 = f7 && f7[0] == '0';
-    const char *fp = vsc_opt(OPT_SWIN_FUSED_PROJ);   // diagnostic / test switch: 0 = proj + LayerNorm as their own launch
-    const bool unfused_proj = fp && fp[0] == '0';
-    const char *fg = vsc_opt(OPT_SWIN_FUSED_MERGE);   // diagnostic / test switch: 0 = PatchMerging as a gather kernel + GEMM
-    const bool unfused_merge = fg && fg[0] == '0';
+    // diagnostic / test switches
+    const bool unfused_mlp = vsc_opt_is(OPT_SWIN_FUSED_MLP, '0');        // 0 = fc1 and fc2 as two GEMM launches
+    const bool unfused_mlp512 = vsc_opt_is(OPT_SWIN_MLP512, '0');        // 0 = the 512-wide stage keeps fc1 and fc2 as two GEMM launches,
+    const bool forced_mlp512 = vsc_opt_is(OPT_SWIN_MLP512, '1');         // 1 = the fused kernel at every size (default: where its 128-row tiles fill the chip)
+    int cus512 = 0;
+    if (vsc_device_cus(&cus512) != VSC_OK || cus512 <= 0) cus512 = 256;
+    const bool unfused_proj512 = vsc_opt_is(OPT_SWIN_PROJ512, '0');      // 0 = the 512-wide stage keeps proj + LayerNorm as their own launch
+    const bool unfused_qkv512 = vsc_opt_is(OPT_SWIN_QKV512, '0');        // 0 = every block of the 512-wide stage launches its own qkv GEMM
+    const bool unfused_proj = vsc_opt_is(OPT_SWIN_FUSED_PROJ, '0');      // 0 = proj + LayerNorm as their own launch
+    const bool unfused_merge = vsc_opt_is(OPT_SWIN_FUSED_MERGE, '0');    // 0 = PatchMerging as a gather kernel + GEMM
     int chunk = 0;
     for (int64_t off = 0; off < n; off += c.max_batch, ++chunk) {
         const int lane = fork ? (chunk & 1) : 0;

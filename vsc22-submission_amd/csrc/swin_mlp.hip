@@ -451,13 +451,7 @@ int launch_proj_c(const MlpArgs &a, hipStream_t stream) {
     constexpr int NW = 8, R = NW * (C == 128 ? 32 : 16);
     constexpr int smem = 2 * (2 * 64 * C * 2) + (4 * C + 3 * C + 3 * C) * 4 + (C * C * 2 > 32 * 1024 ? 0 : C * C * 2);
     static_assert(smem <= 160 * 1024 && C * C * 2 <= 2 * (2 * 64 * C * 2), "Wp fits neither beside the ring nor in it");
-    static bool attr_set[16] = {};
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)swin_mlp_kernel<C, NW, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        if (dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(swin_mlp_kernel<C, NW, 0, true>, smem));
     const int64_t grid = (a.m + R - 1) / R;
     VSC_REQUIRE(grid < (1ll << 31), "swin_mlp: grid too large");
     // C = 128 (round 6): two 4-wave workgroups per CU instead of one 8-wave one -- Wp rides in ring slot 1 (2 x 69 KiB of LDS), 128 rows per
@@ -466,27 +460,17 @@ int launch_proj_c(const MlpArgs &a, hipStream_t stream) {
     // stagger between the two (VSC_SWIN_MLP_NW4=<n> x 8 128 cycles) changes nothing: they are not in lockstep to begin with.  In the
     // encoder's two-lane step the other lane's launches were already filling those gaps: frames/s unchanged there; one-lane calls gain.
     // VSC_SWIN_MLP_NW4=-1: the 8-wave form.
-    const char *nw4 = vsc_opt(OPT_SWIN_MLP_NW4);
-    if (C == 128 && !(nw4 && nw4[0] == '-')) {
+    if (C == 128 && !vsc_opt_is(OPT_SWIN_MLP_NW4, '-')) {
         constexpr int R4 = 4 * 32, smem4 = 2 * (2 * 64 * C * 2) + (4 * C + 3 * C + 3 * C) * 4;
-        static bool a4[16] = {};
-        if (dev >= 16 || !a4[dev]) {
-            VSC_CHECK_HIP(hipFuncSetAttribute((const void *)swin_mlp_kernel<128, 4, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem4));
-            if (dev < 16) a4[dev] = true;
-        }
+        VSC_TRY(vsc_allow_dynamic_lds(swin_mlp_kernel<128, 4, 0, true>, smem4));
         MlpArgs b = a;
-        b.stagger = nw4 ? atoi(nw4) : 0;
+        b.stagger = vsc_opt_int(OPT_SWIN_MLP_NW4, 0);
         hipLaunchKernelGGL((swin_mlp_kernel<128, 4, 0, true>), dim3((unsigned)((a.m + R4 - 1) / R4)), dim3(256), smem4, stream, b);
         VSC_CHECK_LAUNCH();
         return VSC_OK;
     }
-    const char *sq = vsc_opt(OPT_SWIN_MLP_SEQ);   // diagnostic: 1 = the vector work of a chunk as one run (SEQ)
-    if (sq && sq[0] == '1') {
-        static bool seq_attr[16] = {};
-        if (dev >= 16 || !seq_attr[dev]) {
-            VSC_CHECK_HIP(hipFuncSetAttribute((const void *)swin_mlp_kernel<C, NW, 0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-            if (dev < 16) seq_attr[dev] = true;
-        }
+    if (vsc_opt_is(OPT_SWIN_MLP_SEQ, '1')) {   // diagnostic: 1 = the vector work of a chunk as one run (SEQ)
+        VSC_TRY(vsc_allow_dynamic_lds(swin_mlp_kernel<C, NW, 0, true, true>, smem));
         hipLaunchKernelGGL((swin_mlp_kernel<C, NW, 0, true, true>), dim3((unsigned)grid), dim3(NW * 64), smem, stream, a);
     } else
         hipLaunchKernelGGL((swin_mlp_kernel<C, NW, 0, true>), dim3((unsigned)grid), dim3(NW * 64), smem, stream, a);
@@ -498,21 +482,13 @@ template <int C>
 int launch_c(const MlpArgs &a, hipStream_t stream) {
     constexpr int NW = 8, R = NW * (C == 128 ? 32 : 16);
     constexpr int smem = 2 * (2 * 64 * C * 2) + (4 * C + 3 * C) * 4;
-    static bool attr_set[16] = {};
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)swin_mlp_kernel<C, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        if (dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(swin_mlp_kernel<C, NW>, smem));
     const int64_t grid = (a.m + R - 1) / R;
     VSC_REQUIRE(grid < (1ll << 31), "swin_mlp: grid too large");
 #ifdef VSC_MLP_ABLATION
-    if (const char *e = vsc_opt(OPT_SWIN_MLP_ABL)) {
-#define VSC_MLP_CASE(A) case A: { auto k = swin_mlp_kernel<C, NW, A>; VSC_CHECK_HIP(hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, smem)); \
-        hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), smem, stream, a); VSC_CHECK_LAUNCH(); return VSC_OK; }
-        switch (atoi(e)) { VSC_MLP_CASE(1) VSC_MLP_CASE(2) VSC_MLP_CASE(3) VSC_MLP_CASE(4) VSC_MLP_CASE(8) VSC_MLP_CASE(16) VSC_MLP_CASE(20) VSC_MLP_CASE(31) default: break; }
-    }
+#define VSC_MLP_CASE(A) case A: { auto k = swin_mlp_kernel<C, NW, A>; VSC_TRY(vsc_allow_dynamic_lds(k, smem)); \
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(NW * 64), smem, stream, a); VSC_CHECK_LAUNCH(); return VSC_OK; }
+    switch (vsc_opt_int(OPT_SWIN_MLP_ABL, 0)) { VSC_MLP_CASE(1) VSC_MLP_CASE(2) VSC_MLP_CASE(3) VSC_MLP_CASE(4) VSC_MLP_CASE(8) VSC_MLP_CASE(16) VSC_MLP_CASE(20) VSC_MLP_CASE(31) default: break; }
 #endif
     hipLaunchKernelGGL((swin_mlp_kernel<C, NW>), dim3((unsigned)grid), dim3(NW * 64), smem, stream, a);
     VSC_CHECK_LAUNCH();

@@ -176,13 +176,7 @@ uint32_t *g_mlp512_dbg = nullptr;   // vsc_debug_mlp512_timing
 
 template <int V>
 int launch_k(const Mlp512Args &a, hipStream_t stream) {
-    static bool attr_set[16] = {};
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    if (dev >= 16 || !attr_set[dev]) {
-        VSC_CHECK_HIP(hipFuncSetAttribute((const void *)swin_mlp512_kernel<V>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-        if (dev < 16) attr_set[dev] = true;
-    }
+    VSC_TRY(vsc_allow_dynamic_lds(swin_mlp512_kernel<V>, LDS_BYTES));
     int64_t grid = (a.m + R - 1) / R;
     VSC_REQUIRE(grid < (1ll << 31), "swin_mlp512: grid too large");
     if (const char *g = vsc_opt(OPT_SWIN_MLP512_GRID)) {   // experiment: persistent workgroups (e.g. 128: half the chip per launch, the other lane's kernel beside it)
@@ -215,17 +209,15 @@ int launch_swin_mlp512(const uint16_t *w1, const float *b1, const uint16_t *w2c,
     VSC_REQUIRE(m < (1ll << 21), "swin_mlp512: %lld rows (x is addressed through one 4-GiB buffer descriptor: < 2^21 rows per call)", (long long)m);
     const Mlp512Args a{w1, b1, w2c, b2, gamma, beta, x, xb, m, eps, g_mlp512_dbg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 #ifdef VSC_MLP_ABLATION
-    if (const char *e = vsc_opt(OPT_SWIN_MLP_ABL)) {   // diagnostic build: another variant of the generated body (ablations give wrong results)
-        switch (atoi(e)) {
-            case 2: return launch_k<2>(a, stream);
-            case 3: return launch_k<3>(a, stream);
-            case 4: return launch_k<4>(a, stream);
-            case 5: return launch_k<5>(a, stream);
-            case 6: return launch_k<6>(a, stream);
-            case 7: return launch_k<7>(a, stream);
-            case 8: return launch_k<8>(a, stream);
-            default: break;
-        }
+    switch (vsc_opt_int(OPT_SWIN_MLP_ABL, 0)) {   // diagnostic build: another variant of the generated body (ablations give wrong results)
+        case 2: return launch_k<2>(a, stream);
+        case 3: return launch_k<3>(a, stream);
+        case 4: return launch_k<4>(a, stream);
+        case 5: return launch_k<5>(a, stream);
+        case 6: return launch_k<6>(a, stream);
+        case 7: return launch_k<7>(a, stream);
+        case 8: return launch_k<8>(a, stream);
+        default: break;
     }
 #endif
     return launch_k<0>(a, stream);
@@ -253,19 +245,17 @@ int launch_swin_proj_mlp_qkv512(const uint16_t *att, const uint16_t *wp, const f
     VSC_REQUIRE(m * 3072 < (1ll << 32), "swin_proj_mlp_qkv512: %lld rows (the qkv rows are addressed through one 4-GiB buffer descriptor)", (long long)m);
     const Mlp512Args a{w1, b1, w2c, b2, gamma2, beta2, x, nullptr, m, eps, nullptr, att, wp, bp, gamma1, beta1, wq, bq, qkv_next};
 #if defined(VSC_MLP_ABLATION) && VSC_MLP512_VARIANTS == 19
-    if (const char *e = vsc_opt(OPT_SWIN_MLP_ABL)) {   // diagnostic build: the QKV phase's ablations (wrong results)
-        switch (atoi(e)) {
-            case 10: return launch_k<10>(a, stream);
-            case 11: return launch_k<11>(a, stream);
-            case 12: return launch_k<12>(a, stream);
-            case 13: return launch_k<13>(a, stream);
-            case 14: return launch_k<14>(a, stream);
-            case 15: return launch_k<15>(a, stream);
-            case 16: return launch_k<16>(a, stream);
-            case 17: return launch_k<17>(a, stream);
-            case 18: return launch_k<18>(a, stream);
-            default: break;
-        }
+    switch (vsc_opt_int(OPT_SWIN_MLP_ABL, 0)) {   // diagnostic build: the QKV phase's ablations (wrong results)
+        case 10: return launch_k<10>(a, stream);
+        case 11: return launch_k<11>(a, stream);
+        case 12: return launch_k<12>(a, stream);
+        case 13: return launch_k<13>(a, stream);
+        case 14: return launch_k<14>(a, stream);
+        case 15: return launch_k<15>(a, stream);
+        case 16: return launch_k<16>(a, stream);
+        case 17: return launch_k<17>(a, stream);
+        case 18: return launch_k<18>(a, stream);
+        default: break;
     }
 #endif
     return launch_k<9>(a, stream);

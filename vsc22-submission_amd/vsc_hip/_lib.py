@@ -160,7 +160,8 @@ def load(precision: str = "bf16") -> ctypes.CDLL:
             raise HipPathUnavailable(
                 f"{path} is not built -- run `python -c 'import __graft_entry__ as g; g.build()'` "
                 "or `make -C vsc22-submission_amd/csrc`; there is no CPU fallback")
-        lib = ctypes.CDLL(path)
+        # RTLD_LOCAL: both builds live in one process and share nothing (each exports only the vsc_* C ABI and binds its own calls itself)
+        lib = ctypes.CDLL(path, mode=os.RTLD_LOCAL)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(lib, name)
             fn.restype = res
