@@ -9,13 +9,9 @@
 //   pooled  f32  [B, D]
 // Weights: matrices as bf16 [out, in] (PyTorch Linear layout == the GEMM's W[N,K]),
 // biases / LayerNorm / cls / pos / head as f32.
-#include <map>
-#include <string>
-#include <vector>
-
 #include <string.h>
 
-#include "common.h"
+#include "model_host.h"
 
 struct LayerW {
     uint16_t *qkv_w, *proj_w, *fc1_w, *fc2_w;
@@ -26,13 +22,10 @@ struct LayerW {
     float *qkv_cs = nullptr, *qkv_bf = nullptr, *fc1_cs = nullptr, *fc1_bf = nullptr;
 };
 
-struct vsc_encoder {
+struct vsc_encoder : ModelHost {
+    vsc_encoder() : ModelHost("encoder", "") {}
     vsc_encoder_config cfg;
     int tokens = 0, grid = 0, kpatch = 0, kpad = 0, desc_dim = 0;
-    bool finalized = false;
-    std::map<std::string, std::vector<float>> host_w;
-    std::map<std::string, size_t> expect;
-    std::vector<void *> allocs;
     std::vector<LayerW> layers;
     uint16_t *patch_w = nullptr;
     float *patch_b = nullptr, *cls = nullptr, *pos = nullptr, *lnpre_g = nullptr, *lnpre_b = nullptr,
@@ -48,56 +41,11 @@ struct vsc_encoder {
         uint16_t *xb = nullptr;                       //                    bf16(x) [M, D]
     } ws[2];
     int lanes = 1;
-    hipStream_t lane_stream[2] = {nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
     int64_t ws_bytes = 0;
-    // optional per-kernel-class timing (HIP events on the caller's stream)
-    bool profile = false;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    struct Span { int cls; size_t e0, e1; };
-    std::vector<Span> spans;
-    double prof_ms[VSC_PROF_CLASSES] = {0};
-    int64_t prof_n[VSC_PROF_CLASSES] = {0};
 };
+static_assert(VSC_PROF_CLASSES <= ModelHost::MAX_CLASSES, "profile classes");
 
 namespace {
-
-int dev_alloc(vsc_encoder *e, size_t bytes, void **out) {
-    hipError_t err = hipMalloc(out, bytes);
-    if (err != hipSuccess) {
-        vsc_set_error("encoder: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(err));
-        return VSC_ERR_NOMEM;
-    }
-    e->allocs.push_back(*out);
-    return VSC_OK;
-}
-
-int upload_f32(vsc_encoder *e, const std::string &name, float **out) {
-    const std::vector<float> &v = e->host_w.at(name);
-    int rc = dev_alloc(e, v.size() * 4, (void **)out);
-    if (rc) return rc;
-    VSC_CHECK_HIP(hipMemcpy(*out, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return VSC_OK;
-}
-
-// f32 host matrix [rows, cols] -> bf16 device [rows, cols_pad] (zero padded)
-int upload_bf16(vsc_encoder *e, const std::string &name, int64_t rows, int cols, int cols_pad,
-                uint16_t **out) {
-    const std::vector<float> &v = e->host_w.at(name);
-    float *tmp = nullptr;
-    VSC_CHECK_HIP(hipMalloc((void **)&tmp, v.size() * 4));
-    hipError_t err = hipMemcpy(tmp, v.data(), v.size() * 4, hipMemcpyHostToDevice);
-    int rc = err == hipSuccess ? dev_alloc(e, (size_t)rows * cols_pad * 2, (void **)out) : VSC_ERR_HIP;
-    if (!rc) rc = launch_f32_to_bf16(tmp, *out, rows, cols, cols_pad, nullptr);
-    hipError_t e2 = hipDeviceSynchronize();
-    (void)hipFree(tmp);
-    if (err != hipSuccess || e2 != hipSuccess) {
-        vsc_set_error("encoder: uploading %s failed", name.c_str());
-        return VSC_ERR_HIP;
-    }
-    return rc;
-}
 
 // round-to-nearest-even f32 -> operand type -> f32, as the device packing / launch_f32_to_bf16 do
 inline float bf16_round(float v) { return lp_to_f32(f32_to_lp(v)); }
@@ -125,33 +73,10 @@ int fold_ln(vsc_encoder *e, const std::string &wname, const std::string &bname, 
         colsum[r] = (float)s;
         biasf[r] = (float)((double)b[r] + t);
     }
-    int rc;
-    if ((rc = upload_bf16(e, wname + ".folded", n, k, k, wf))) return rc;
-    if ((rc = upload_f32(e, wname + ".colsum", cs))) return rc;
-    return upload_f32(e, bname + ".folded", bf);
+    VSC_TRY(e->upload_bf16(wname + ".folded", n, k, k, wf));
+    VSC_TRY(e->upload_f32(wname + ".colsum", cs));
+    return e->upload_f32(bname + ".folded", bf);
 }
-
-struct ProfScope {
-    vsc_encoder *e;
-    hipStream_t st;
-    size_t e0 = 0;
-    int cls;
-    ProfScope(vsc_encoder *enc, int c, hipStream_t s) : e(enc), st(s), cls(c) {
-        if (e->profile) e0 = rec();
-    }
-    ~ProfScope() {
-        if (e->profile) e->spans.push_back({cls, e0, rec()});
-    }
-    size_t rec() {
-        if (e->ev_used == e->ev_pool.size()) {
-            hipEvent_t ev;
-            (void)hipEventCreate(&ev);
-            e->ev_pool.push_back(ev);
-        }
-        (void)hipEventRecord(e->ev_pool[e->ev_used], st);
-        return e->ev_used++;
-    }
-};
 
 }  // namespace
 
@@ -187,117 +112,98 @@ extern "C" int vsc_encoder_create(const vsc_encoder_config *cfg, vsc_encoder **o
     e->kpad = (e->kpatch + 63) / 64 * 64;
     e->desc_dim = c.out_dim ? c.out_dim : c.width;
     const size_t D = c.width, Mlp = c.mlp_dim;
-    e->expect["patch.weight"] = D * e->kpatch;
-    if (c.patch_bias) e->expect["patch.bias"] = D;
-    e->expect["cls"] = D;
-    e->expect["pos"] = (size_t)tokens * D;
-    if (c.pre_ln) e->expect["ln_pre.weight"] = e->expect["ln_pre.bias"] = D;
+    e->expect("patch.weight", D * e->kpatch);
+    if (c.patch_bias) e->expect("patch.bias", D);
+    e->expect("cls", D);
+    e->expect("pos", (size_t)tokens * D);
+    if (c.pre_ln) {
+        e->expect("ln_pre.weight", D);
+        e->expect("ln_pre.bias", D);
+    }
     for (int i = 0; i < c.layers; ++i) {
         const std::string b = "blocks." + std::to_string(i) + ".";
-        e->expect[b + "ln1.weight"] = e->expect[b + "ln1.bias"] = D;
-        e->expect[b + "ln2.weight"] = e->expect[b + "ln2.bias"] = D;
-        e->expect[b + "qkv.weight"] = 3 * D * D;
-        e->expect[b + "qkv.bias"] = 3 * D;
-        e->expect[b + "proj.weight"] = D * D;
-        e->expect[b + "proj.bias"] = D;
-        e->expect[b + "fc1.weight"] = Mlp * D;
-        e->expect[b + "fc1.bias"] = Mlp;
-        e->expect[b + "fc2.weight"] = D * Mlp;
-        e->expect[b + "fc2.bias"] = D;
+        e->expect(b + "ln1.weight", D);
+        e->expect(b + "ln1.bias", D);
+        e->expect(b + "ln2.weight", D);
+        e->expect(b + "ln2.bias", D);
+        e->expect(b + "qkv.weight", 3 * D * D);
+        e->expect(b + "qkv.bias", 3 * D);
+        e->expect(b + "proj.weight", D * D);
+        e->expect(b + "proj.bias", D);
+        e->expect(b + "fc1.weight", Mlp * D);
+        e->expect(b + "fc1.bias", Mlp);
+        e->expect(b + "fc2.weight", D * Mlp);
+        e->expect(b + "fc2.bias", D);
     }
-    e->expect["ln_post.weight"] = e->expect["ln_post.bias"] = D;
+    e->expect("ln_post.weight", D);
+    e->expect("ln_post.bias", D);
     if (c.head_conv_dim) {
-        e->expect["head_conv.weight"] = (size_t)c.head_conv_dim * D;
-        e->expect["head_conv.bias"] = c.head_conv_dim;
+        e->expect("head_conv.weight", (size_t)c.head_conv_dim * D);
+        e->expect("head_conv.bias", c.head_conv_dim);
     }
     if (c.out_dim) {
-        e->expect["head.weight"] = (size_t)c.out_dim * (c.head_conv_dim ? c.head_conv_dim : D);
-        e->expect["head.bias"] = c.out_dim;
+        e->expect("head.weight", (size_t)c.out_dim * (c.head_conv_dim ? c.head_conv_dim : D));
+        e->expect("head.bias", c.out_dim);
     }
     *out = e;
     return VSC_OK;
 }
 
-extern "C" void vsc_encoder_destroy(vsc_encoder *e) {
-    if (!e) return;
-    for (void *p : e->allocs) (void)hipFree(p);
-    for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
-    for (int l = 0; l < 2; ++l) {
-        if (e->lane_stream[l]) (void)hipStreamDestroy(e->lane_stream[l]);
-        if (e->ev_join[l]) (void)hipEventDestroy(e->ev_join[l]);
-    }
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    delete e;
-}
+extern "C" void vsc_encoder_destroy(vsc_encoder *e) { delete e; }
 
 extern "C" int vsc_encoder_set_weight(vsc_encoder *e, const char *name, const float *host,
                                       size_t count) {
     VSC_REQUIRE(e && name && host, "set_weight: null argument");
-    if (e->finalized) {
-        vsc_set_error("set_weight(%s) after finalize", name);
-        return VSC_ERR_STATE;
-    }
-    auto it = e->expect.find(name);
-    VSC_REQUIRE(it != e->expect.end(), "set_weight: unknown tensor '%s' for this config", name);
-    VSC_REQUIRE(it->second == count, "set_weight: '%s' has %zu elements, expected %zu", name, count,
-                it->second);
-    e->host_w[name].assign(host, host + count);
-    return VSC_OK;
+    return e->set_weight(name, host, count);
 }
 
 extern "C" int vsc_encoder_finalize(vsc_encoder *e) {
     VSC_REQUIRE(e, "finalize: null encoder");
     if (e->finalized) return VSC_OK;
-    for (auto &kv : e->expect)
-        if (!e->host_w.count(kv.first)) {
-            vsc_set_error("finalize: weight '%s' was never set", kv.first.c_str());
-            return VSC_ERR_STATE;
-        }
+    VSC_TRY(e->all_set());
     const vsc_encoder_config &c = e->cfg;
     const int D = c.width;
-    int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
-    TRY(upload_bf16(e, "patch.weight", D, e->kpatch, e->kpad, &e->patch_w));
-    if (c.patch_bias) TRY(upload_f32(e, "patch.bias", &e->patch_b));
-    TRY(upload_f32(e, "cls", &e->cls));
-    TRY(upload_f32(e, "pos", &e->pos));
+    VSC_TRY(e->upload_bf16("patch.weight", D, e->kpatch, e->kpad, &e->patch_w));
+    if (c.patch_bias) VSC_TRY(e->upload_f32("patch.bias", &e->patch_b));
+    VSC_TRY(e->upload_f32("cls", &e->cls));
+    VSC_TRY(e->upload_f32("pos", &e->pos));
     if (c.pre_ln) {
-        TRY(upload_f32(e, "ln_pre.weight", &e->lnpre_g));
-        TRY(upload_f32(e, "ln_pre.bias", &e->lnpre_b));
+        VSC_TRY(e->upload_f32("ln_pre.weight", &e->lnpre_g));
+        VSC_TRY(e->upload_f32("ln_pre.bias", &e->lnpre_b));
     }
     e->layers.resize(c.layers);
     for (int i = 0; i < c.layers; ++i) {
         const std::string b = "blocks." + std::to_string(i) + ".";
         LayerW &L = e->layers[i];
-        TRY(upload_f32(e, b + "ln1.weight", &L.ln1_g));
-        TRY(upload_f32(e, b + "ln1.bias", &L.ln1_b));
-        TRY(upload_f32(e, b + "ln2.weight", &L.ln2_g));
-        TRY(upload_f32(e, b + "ln2.bias", &L.ln2_b));
-        TRY(upload_bf16(e, b + "qkv.weight", 3 * D, D, D, &L.qkv_w));
-        TRY(upload_f32(e, b + "qkv.bias", &L.qkv_b));
-        TRY(upload_bf16(e, b + "proj.weight", D, D, D, &L.proj_w));
-        TRY(upload_f32(e, b + "proj.bias", &L.proj_b));
-        TRY(upload_bf16(e, b + "fc1.weight", c.mlp_dim, D, D, &L.fc1_w));
-        TRY(upload_f32(e, b + "fc1.bias", &L.fc1_b));
-        TRY(upload_bf16(e, b + "fc2.weight", D, c.mlp_dim, c.mlp_dim, &L.fc2_w));
-        TRY(upload_f32(e, b + "fc2.bias", &L.fc2_b));
+        VSC_TRY(e->upload_f32(b + "ln1.weight", &L.ln1_g));
+        VSC_TRY(e->upload_f32(b + "ln1.bias", &L.ln1_b));
+        VSC_TRY(e->upload_f32(b + "ln2.weight", &L.ln2_g));
+        VSC_TRY(e->upload_f32(b + "ln2.bias", &L.ln2_b));
+        VSC_TRY(e->upload_bf16(b + "qkv.weight", 3 * D, D, D, &L.qkv_w));
+        VSC_TRY(e->upload_f32(b + "qkv.bias", &L.qkv_b));
+        VSC_TRY(e->upload_bf16(b + "proj.weight", D, D, D, &L.proj_w));
+        VSC_TRY(e->upload_f32(b + "proj.bias", &L.proj_b));
+        VSC_TRY(e->upload_bf16(b + "fc1.weight", c.mlp_dim, D, D, &L.fc1_w));
+        VSC_TRY(e->upload_f32(b + "fc1.bias", &L.fc1_b));
+        VSC_TRY(e->upload_bf16(b + "fc2.weight", D, c.mlp_dim, c.mlp_dim, &L.fc2_w));
+        VSC_TRY(e->upload_f32(b + "fc2.bias", &L.fc2_b));
         if (c.fuse_ln > 0) {
-            TRY(fold_ln(e, b + "fc1.weight", b + "fc1.bias", b + "ln2.weight", b + "ln2.bias", c.mlp_dim, D, &L.fc1_wf,
-                        &L.fc1_cs, &L.fc1_bf));
+            VSC_TRY(fold_ln(e, b + "fc1.weight", b + "fc1.bias", b + "ln2.weight", b + "ln2.bias", c.mlp_dim, D, &L.fc1_wf,
+                            &L.fc1_cs, &L.fc1_bf));
             if (i > 0)  // layer 0 reads x from the patch / cls kernels, which emit no statistics: it keeps its LN1 pass
-                TRY(fold_ln(e, b + "qkv.weight", b + "qkv.bias", b + "ln1.weight", b + "ln1.bias", 3 * D, D, &L.qkv_wf,
-                            &L.qkv_cs, &L.qkv_bf));
+                VSC_TRY(fold_ln(e, b + "qkv.weight", b + "qkv.bias", b + "ln1.weight", b + "ln1.bias", 3 * D, D, &L.qkv_wf,
+                                &L.qkv_cs, &L.qkv_bf));
         }
     }
-    TRY(upload_f32(e, "ln_post.weight", &e->lnpost_g));
-    TRY(upload_f32(e, "ln_post.bias", &e->lnpost_b));
+    VSC_TRY(e->upload_f32("ln_post.weight", &e->lnpost_g));
+    VSC_TRY(e->upload_f32("ln_post.bias", &e->lnpost_b));
     if (c.head_conv_dim) {
-        TRY(upload_bf16(e, "head_conv.weight", c.head_conv_dim, D, D, &e->hconv_w));
-        TRY(upload_f32(e, "head_conv.bias", &e->hconv_b));
+        VSC_TRY(e->upload_bf16("head_conv.weight", c.head_conv_dim, D, D, &e->hconv_w));
+        VSC_TRY(e->upload_f32("head_conv.bias", &e->hconv_b));
     }
     if (c.out_dim) {
-        TRY(upload_f32(e, "head.weight", &e->head_w));
-        TRY(upload_f32(e, "head.bias", &e->head_b));
+        VSC_TRY(e->upload_f32("head.weight", &e->head_w));
+        VSC_TRY(e->upload_f32("head.bias", &e->head_b));
     }
     // workspace for max_batch frames
     const size_t B = c.max_batch, M = B * e->tokens;
@@ -308,56 +214,35 @@ extern "C" int vsc_encoder_finalize(vsc_encoder *e) {
     e->lanes = c.lanes == 2 ? 2 : 1;
     for (int l = 0; l < e->lanes; ++l) {
         vsc_encoder::Workspace &w = e->ws[l];
-        TRY(dev_alloc(e, sz_patches, (void **)&w.patches));
-        TRY(dev_alloc(e, sz_x, (void **)&w.x));
-        TRY(dev_alloc(e, sz_y, (void **)&w.y));
-        TRY(dev_alloc(e, sz_qkv, (void **)&w.qkv));
-        TRY(dev_alloc(e, sz_h, (void **)&w.h));
-        TRY(dev_alloc(e, sz_pool, (void **)&w.pooled));
+        VSC_TRY(e->alloc(sz_patches, (void **)&w.patches));
+        VSC_TRY(e->alloc(sz_x, (void **)&w.x));
+        VSC_TRY(e->alloc(sz_y, (void **)&w.y));
+        VSC_TRY(e->alloc(sz_qkv, (void **)&w.qkv));
+        VSC_TRY(e->alloc(sz_h, (void **)&w.h));
+        VSC_TRY(e->alloc(sz_pool, (void **)&w.pooled));
         if (c.fuse_ln > 0) {
-            TRY(dev_alloc(e, (size_t)(D / 64) * M * 2 * 4, (void **)&w.stats));
-            TRY(dev_alloc(e, M * 2 * 4, (void **)&w.rowstats));
-            TRY(dev_alloc(e, sz_y, (void **)&w.xb));
+            VSC_TRY(e->alloc((size_t)(D / 64) * M * 2 * 4, (void **)&w.stats));
+            VSC_TRY(e->alloc(M * 2 * 4, (void **)&w.rowstats));
+            VSC_TRY(e->alloc(sz_y, (void **)&w.xb));
         }
         w.hconv_out = w.h;  // [M, head_conv_dim] bf16 fits in the (idle) MLP buffer: head_conv_dim <= mlp_dim
-        if (e->lanes == 2) {
-            VSC_CHECK_HIP(hipStreamCreateWithFlags(&e->lane_stream[l], hipStreamNonBlocking));
-            VSC_CHECK_HIP(hipEventCreateWithFlags(&e->ev_join[l], hipEventDisableTiming));
-        }
     }
-    if (e->lanes == 2) VSC_CHECK_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-#undef TRY
+    if (e->lanes == 2) VSC_TRY(e->make_lanes());
     e->ws_bytes = (int64_t)(sz_patches + sz_x + sz_y + sz_qkv + sz_h + sz_pool + (c.fuse_ln > 0 ? sz_y + ((size_t)(D / 64) + 1) * M * 8 : 0)) * e->lanes;
-    e->host_w.clear();
-    e->finalized = true;
+    e->drop_host();
     return VSC_OK;
 }
 
 extern "C" int64_t vsc_encoder_workspace_bytes(const vsc_encoder *e) { return e ? e->ws_bytes : 0; }
 
-// frames: fp32 [n,C,H,W] already normalised, or (frames == nullptr) frames_u8: uint8 [n,H,W,C] + mean/std
-static int encoder_forward_impl(vsc_encoder *e, const float *frames, const uint8_t *frames_u8, const float *mean,
-                                const float *std, int64_t n, float *desc, float *tokens_out, void *stream_) {
-    VSC_REQUIRE(e && (frames || frames_u8) && desc, "forward: null argument");
-    VSC_REQUIRE(n >= 0, "forward: negative frame count");
-    if (!e->finalized) {
-        vsc_set_error("forward before finalize");
-        return VSC_ERR_STATE;
-    }
-    hipStream_t user = (hipStream_t)stream_;
+// the chunks of one call; `fork`: alternate them over the two lanes.  Returns at the first failing launch (the caller joins
+// the lanes in every case).
+static int encoder_run_chunks(vsc_encoder *e, const float *frames, const uint8_t *frames_u8, const float *mean, const float *std,
+                              int64_t n, float *desc, float *tokens_out, hipStream_t user, bool fork) {
     const vsc_encoder_config &c = e->cfg;
-    // >= 2 chunks: alternate them over the two lanes.  Not while profiling: the per-launch events are meant to time one kernel
-    // at a time (bench.py's kernels{} / roofline loop), so the chunks then run back to back on the caller's stream.
-    const bool fork = e->lanes == 2 && n > c.max_batch && !e->profile;
-    if (fork) {
-        VSC_CHECK_HIP(hipEventRecord(e->ev_fork, user));
-        for (int l = 0; l < 2; ++l) VSC_CHECK_HIP(hipStreamWaitEvent(e->lane_stream[l], e->ev_fork, 0));
-    }
     const int D = c.width, T = e->tokens;
     const int act_epi = c.act == 0 ? VSC_EPI_GELU_BF16 : VSC_EPI_QGELU_BF16;
     const int64_t frame_elems = (int64_t)c.channels * c.image_size * c.image_size;
-    int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
     int chunk = 0;
     for (int64_t off = 0; off < n; off += c.max_batch, ++chunk) {
         const int lane = fork ? (chunk & 1) : 0;
@@ -368,17 +253,17 @@ static int encoder_forward_impl(vsc_encoder *e, const float *frames, const uint8
         {
             ProfScope _ps(e, VSC_PROF_PATCHIFY, st);
             if (frames)
-                TRY(launch_patchify(frames + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size, e->kpad, st));
+                VSC_TRY(launch_patchify(frames + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size, e->kpad, st));
             else
-                TRY(launch_patchify_u8(frames_u8 + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size,
-                                       e->kpad, mean, std, st));
+                VSC_TRY(launch_patchify_u8(frames_u8 + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size,
+                                           e->kpad, mean, std, st));
         }
-        { ProfScope _ps(e, VSC_PROF_GEMM_PATCH, st); TRY(launch_gemm_bf16(w.patches, e->patch_w, e->patch_b, e->pos, w.x, Mp, D, e->kpad,
-                             VSC_EPI_PATCH_F32, T, st)); }
-        { ProfScope _ps(e, VSC_PROF_MISC, st); TRY(launch_cls_rows(w.x, e->cls, e->pos, B, T, D, st)); }
+        { ProfScope _ps(e, VSC_PROF_GEMM_PATCH, st); VSC_TRY(launch_gemm_bf16(w.patches, e->patch_w, e->patch_b, e->pos, w.x, Mp, D, e->kpad,
+                                 VSC_EPI_PATCH_F32, T, st)); }
+        { ProfScope _ps(e, VSC_PROF_MISC, st); VSC_TRY(launch_cls_rows(w.x, e->cls, e->pos, B, T, D, st)); }
         if (c.pre_ln) {
             ProfScope _ps(e, VSC_PROF_LAYERNORM, st);
-            TRY(launch_layernorm(w.x, e->lnpre_g, e->lnpre_b, w.x, M, D, c.ln_eps, 1, st));
+            VSC_TRY(launch_layernorm(w.x, e->lnpre_g, e->lnpre_b, w.x, M, D, c.ln_eps, 1, st));
         }
         // LayerNorm folding (opt-in): from the first residual GEMM on, bf16(x) and x's row statistics
         // come out of the proj / fc2 write-out (into w.xb / w.stats) and LN2 / the next layer's LN1 are applied inside
@@ -399,51 +284,59 @@ static int encoder_forward_impl(vsc_encoder *e, const float *frames, const uint8
             if (fold && l > 0) {
                 take.colsum = L.qkv_cs;
                 ProfScope _ps(e, VSC_PROF_GEMM_QKV, st);
-                TRY(launch_gemm_bf16_ex(w.xb, L.qkv_wf, L.qkv_bf, nullptr, w.qkv, M, 3 * D, D, VSC_EPI_LNF_BF16, 0, take, st));
+                VSC_TRY(launch_gemm_bf16_ex(w.xb, L.qkv_wf, L.qkv_bf, nullptr, w.qkv, M, 3 * D, D, VSC_EPI_LNF_BF16, 0, take, st));
             } else {
-                { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); TRY(launch_layernorm(w.x, L.ln1_g, L.ln1_b, w.y, M, D, c.ln_eps, 0, st)); }
-                { ProfScope _ps(e, VSC_PROF_GEMM_QKV, st); TRY(launch_gemm_bf16(w.y, L.qkv_w, L.qkv_b, nullptr, w.qkv, M, 3 * D, D, VSC_EPI_BF16, 0, st)); }
+                { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); VSC_TRY(launch_layernorm(w.x, L.ln1_g, L.ln1_b, w.y, M, D, c.ln_eps, 0, st)); }
+                { ProfScope _ps(e, VSC_PROF_GEMM_QKV, st); VSC_TRY(launch_gemm_bf16(w.y, L.qkv_w, L.qkv_b, nullptr, w.qkv, M, 3 * D, D, VSC_EPI_BF16, 0, st)); }
             }
-            { ProfScope _ps(e, VSC_PROF_ATTENTION, st); TRY(launch_attention_bf16(w.qkv, w.y, (int)B, T, c.heads, st)); }
+            { ProfScope _ps(e, VSC_PROF_ATTENTION, st); VSC_TRY(launch_attention_bf16(w.qkv, w.y, (int)B, T, c.heads, st)); }
             if (fold) {
-                { ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st); TRY(launch_gemm_bf16_ex(w.y, L.proj_w, L.proj_b, w.x, w.x, M, D, D, VSC_EPI_RESADD_STATS_F32, 0, emit, st)); }
+                { ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st); VSC_TRY(launch_gemm_bf16_ex(w.y, L.proj_w, L.proj_b, w.x, w.x, M, D, D, VSC_EPI_RESADD_STATS_F32, 0, emit, st)); }
                 take.colsum = L.fc1_cs;
-                { ProfScope _ps(e, VSC_PROF_GEMM_FC1, st); TRY(launch_gemm_bf16_ex(w.xb, L.fc1_wf, L.fc1_bf, nullptr, w.h, M, c.mlp_dim, D, act_lnf, 0, take, st)); }
-                { ProfScope _ps(e, VSC_PROF_GEMM_FC2, st); TRY(launch_gemm_bf16_ex(w.h, L.fc2_w, L.fc2_b, w.x, w.x, M, D, c.mlp_dim, l + 1 < c.layers ? VSC_EPI_RESADD_STATS_F32 : VSC_EPI_RESADD_F32, 0, emit, st)); }
+                { ProfScope _ps(e, VSC_PROF_GEMM_FC1, st); VSC_TRY(launch_gemm_bf16_ex(w.xb, L.fc1_wf, L.fc1_bf, nullptr, w.h, M, c.mlp_dim, D, act_lnf, 0, take, st)); }
+                { ProfScope _ps(e, VSC_PROF_GEMM_FC2, st); VSC_TRY(launch_gemm_bf16_ex(w.h, L.fc2_w, L.fc2_b, w.x, w.x, M, D, c.mlp_dim, l + 1 < c.layers ? VSC_EPI_RESADD_STATS_F32 : VSC_EPI_RESADD_F32, 0, emit, st)); }
             } else {
-                { ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st); TRY(launch_gemm_bf16(w.y, L.proj_w, L.proj_b, w.x, w.x, M, D, D, VSC_EPI_RESADD_F32, 0, st)); }
-                { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); TRY(launch_layernorm(w.x, L.ln2_g, L.ln2_b, w.y, M, D, c.ln_eps, 0, st)); }
-                { ProfScope _ps(e, VSC_PROF_GEMM_FC1, st); TRY(launch_gemm_bf16(w.y, L.fc1_w, L.fc1_b, nullptr, w.h, M, c.mlp_dim, D, act_epi, 0, st)); }
-                { ProfScope _ps(e, VSC_PROF_GEMM_FC2, st); TRY(launch_gemm_bf16(w.h, L.fc2_w, L.fc2_b, w.x, w.x, M, D, c.mlp_dim, VSC_EPI_RESADD_F32, 0, st)); }
+                { ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st); VSC_TRY(launch_gemm_bf16(w.y, L.proj_w, L.proj_b, w.x, w.x, M, D, D, VSC_EPI_RESADD_F32, 0, st)); }
+                { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); VSC_TRY(launch_layernorm(w.x, L.ln2_g, L.ln2_b, w.y, M, D, c.ln_eps, 0, st)); }
+                { ProfScope _ps(e, VSC_PROF_GEMM_FC1, st); VSC_TRY(launch_gemm_bf16(w.y, L.fc1_w, L.fc1_b, nullptr, w.h, M, c.mlp_dim, D, act_epi, 0, st)); }
+                { ProfScope _ps(e, VSC_PROF_GEMM_FC2, st); VSC_TRY(launch_gemm_bf16(w.h, L.fc2_w, L.fc2_b, w.x, w.x, M, D, c.mlp_dim, VSC_EPI_RESADD_F32, 0, st)); }
             }
         }
         if (c.head_conv_dim) {
             // SSCD head: final LN -> bf16 tokens -> Conv1d(D, C, 1) as a GEMM -> GeM over tokens
             ProfScope _ps(e, VSC_PROF_POOL_HEAD, st);
             if (tokens_out)
-                TRY(launch_layernorm(w.x, e->lnpost_g, e->lnpost_b, tokens_out + off * T * D, M, D, c.ln_eps, 1, st));
-            TRY(launch_layernorm(w.x, e->lnpost_g, e->lnpost_b, w.y, M, D, c.ln_eps, 0, st));
-            TRY(launch_gemm_bf16(w.y, e->hconv_w, e->hconv_b, nullptr, w.hconv_out, M, c.head_conv_dim, D,
-                                 VSC_EPI_BF16, 0, st));
-            TRY(launch_gem_pool_bf16(w.hconv_out, w.pooled, B, T, c.head_conv_dim, c.gem_p, st));
-            TRY(launch_head(w.pooled, e->head_w, e->head_b, desc + off * e->desc_dim, B, c.head_conv_dim,
-                            c.out_dim, c.l2_normalize, st));
+                VSC_TRY(launch_layernorm(w.x, e->lnpost_g, e->lnpost_b, tokens_out + off * T * D, M, D, c.ln_eps, 1, st));
+            VSC_TRY(launch_layernorm(w.x, e->lnpost_g, e->lnpost_b, w.y, M, D, c.ln_eps, 0, st));
+            VSC_TRY(launch_gemm_bf16(w.y, e->hconv_w, e->hconv_b, nullptr, w.hconv_out, M, c.head_conv_dim, D,
+                                     VSC_EPI_BF16, 0, st));
+            VSC_TRY(launch_gem_pool_bf16(w.hconv_out, w.pooled, B, T, c.head_conv_dim, c.gem_p, st));
+            VSC_TRY(launch_head(w.pooled, e->head_w, e->head_b, desc + off * e->desc_dim, B, c.head_conv_dim,
+                                c.out_dim, c.l2_normalize, st));
         } else {
-        { ProfScope _ps(e, VSC_PROF_POOL_HEAD, st); TRY(launch_ln_pool(w.x, e->lnpost_g, e->lnpost_b, w.pooled,
-                           tokens_out ? tokens_out + off * T * D : nullptr, B, T, D, c.ln_eps, c.pool,
-                           c.gem_p, st)); }
-            { ProfScope _ps(e, VSC_PROF_POOL_HEAD, st); TRY(launch_head(w.pooled, e->head_w, e->head_b, desc + off * e->desc_dim, B, D, c.out_dim,
-                        c.l2_normalize, st)); }
+        { ProfScope _ps(e, VSC_PROF_POOL_HEAD, st); VSC_TRY(launch_ln_pool(w.x, e->lnpost_g, e->lnpost_b, w.pooled,
+                               tokens_out ? tokens_out + off * T * D : nullptr, B, T, D, c.ln_eps, c.pool,
+                               c.gem_p, st)); }
+            { ProfScope _ps(e, VSC_PROF_POOL_HEAD, st); VSC_TRY(launch_head(w.pooled, e->head_w, e->head_b, desc + off * e->desc_dim, B, D, c.out_dim,
+                            c.l2_normalize, st)); }
         }
     }
-    if (fork) {
-        for (int l = 0; l < 2; ++l) {
-            VSC_CHECK_HIP(hipEventRecord(e->ev_join[l], e->lane_stream[l]));
-            VSC_CHECK_HIP(hipStreamWaitEvent(user, e->ev_join[l], 0));
-        }
-    }
-#undef TRY
     return VSC_OK;
+}
+
+// frames: fp32 [n,C,H,W] already normalised, or (frames == nullptr) frames_u8: uint8 [n,H,W,C] + mean/std
+static int encoder_forward_impl(vsc_encoder *e, const float *frames, const uint8_t *frames_u8, const float *mean,
+                                const float *std, int64_t n, float *desc, float *tokens_out, void *stream_) {
+    VSC_REQUIRE(e && (frames || frames_u8) && desc, "forward: null argument");
+    VSC_REQUIRE(n >= 0, "forward: negative frame count");
+    VSC_TRY(e->forward_ready());
+    hipStream_t user = (hipStream_t)stream_;
+    // >= 2 chunks: alternate them over the two lanes.  Not while profiling: the per-launch events are meant to time one kernel
+    // at a time (bench.py's kernels{} / roofline loop), so the chunks then run back to back on the caller's stream.
+    const bool fork = e->lanes == 2 && n > e->cfg.max_batch && !e->profile;
+    if (fork) VSC_TRY(e->fork(user));
+    const int rc = encoder_run_chunks(e, frames, frames_u8, mean, std, n, desc, tokens_out, user, fork);
+    return fork ? e->join(user, rc) : rc;
 }
 
 extern "C" int vsc_encoder_forward_debug(vsc_encoder *e, const float *frames, int64_t n, float *desc,
@@ -465,30 +358,11 @@ extern "C" int vsc_encoder_forward_u8(vsc_encoder *e, const uint8_t *frames_u8, 
 
 extern "C" int vsc_encoder_set_profiling(vsc_encoder *e, int32_t on) {
     VSC_REQUIRE(e, "set_profiling: null encoder");
-    e->profile = on != 0;
-    e->spans.clear();
-    e->ev_used = 0;
-    for (int i = 0; i < VSC_PROF_CLASSES; ++i) {
-        e->prof_ms[i] = 0;
-        e->prof_n[i] = 0;
-    }
+    e->reset(on != 0);
     return VSC_OK;
 }
 
 extern "C" int vsc_encoder_get_profile(vsc_encoder *e, double *ms_out, int64_t *launches_out) {
     VSC_REQUIRE(e && ms_out && launches_out, "get_profile: null argument");
-    VSC_CHECK_HIP(hipDeviceSynchronize());
-    for (const vsc_encoder::Span &sp : e->spans) {
-        float ms = 0.f;
-        VSC_CHECK_HIP(hipEventElapsedTime(&ms, e->ev_pool[sp.e0], e->ev_pool[sp.e1]));
-        e->prof_ms[sp.cls] += ms;
-        e->prof_n[sp.cls] += 1;
-    }
-    e->spans.clear();
-    e->ev_used = 0;
-    for (int i = 0; i < VSC_PROF_CLASSES; ++i) {
-        ms_out[i] = e->prof_ms[i];
-        launches_out[i] = e->prof_n[i];
-    }
-    return VSC_OK;
+    return e->collect(ms_out, launches_out, VSC_PROF_CLASSES);
 }

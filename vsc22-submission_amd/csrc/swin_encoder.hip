@@ -13,11 +13,7 @@
 // fp32 [heads, (2w-1)^2] per block (the kernel applies the relative_position_index map itself).
 #include <math.h>
 
-#include <map>
-#include <string>
-#include <vector>
-
-#include "common.h"
+#include "model_host.h"
 
 struct SwinBlockW {
     uint16_t *qkv_w, *proj_w, *fc1_w, *fc2_w;
@@ -30,12 +26,9 @@ struct SwinStageW {
     float *dn_g = nullptr, *dn_b = nullptr;
 };
 
-struct vsc_swin {
+struct vsc_swin : ModelHost {
+    vsc_swin() : ModelHost("swin", "swin ") {}
     vsc_swin_config cfg;
-    bool finalized = false;
-    std::map<std::string, std::vector<float>> host_w;
-    std::map<std::string, size_t> expect;
-    std::vector<void *> allocs;
     std::vector<SwinStageW> stages;
     uint16_t *pe_w = nullptr;
     float *pe_b = nullptr, *pe_g = nullptr, *pe_beta = nullptr, *norm_g = nullptr, *norm_b = nullptr,
@@ -48,20 +41,9 @@ struct vsc_swin {
         uint16_t *patches = nullptr, *xb = nullptr, *qkv = nullptr, *att = nullptr, *h = nullptr, *merged = nullptr;
         float *x = nullptr, *t = nullptr, *pooled = nullptr;
         void *lnws = nullptr;   // pair-exchange workspace of the persistent gemm_ln (private to the lane's stream)
-    } ws[2];
-    hipStream_t lane_stream[2] = {nullptr, nullptr};
-    hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
+    } ws[2];   // the second one, with the lane streams, is made by the first call that has more than one chunk
     int64_t ws_bytes = 0;
     size_t ws_sizes[9] = {0};
-    bool lanes_ready = false;   // second workspace + lane streams: made by the first call that has more than one chunk
-    // per-launch HIP events (vsc_swin_set_profiling), as in encoder.hip
-    bool profile = false;
-    struct Span { int cls; size_t e0, e1; };
-    std::vector<Span> spans;
-    std::vector<hipEvent_t> ev_pool;
-    size_t ev_used = 0;
-    double prof_ms[VSC_SWIN_PROF_CLASSES] = {0};
-    int64_t prof_n[VSC_SWIN_PROF_CLASSES] = {0};
 
     int res(int s) const { return cfg.image_size / cfg.patch_size >> s; }
     int dim(int s) const { return cfg.embed_dim << s; }
@@ -69,43 +51,9 @@ struct vsc_swin {
     int shift(int s, int b) const { return res(s) <= cfg.window_size ? 0 : ((b & 1) ? cfg.window_size / 2 : 0); }
 };
 
+static_assert(VSC_SWIN_PROF_CLASSES <= ModelHost::MAX_CLASSES, "profile classes");
+
 namespace {
-
-int sw_alloc(vsc_swin *e, size_t bytes, void **out) {
-    hipError_t err = hipMalloc(out, bytes);
-    if (err != hipSuccess) {
-        vsc_set_error("swin: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(err));
-        return VSC_ERR_NOMEM;
-    }
-    e->allocs.push_back(*out);
-    return VSC_OK;
-}
-
-int sw_upload_f32v(vsc_swin *e, const std::vector<float> &v, float **out) {
-    int rc = sw_alloc(e, v.size() * 4, (void **)out);
-    if (rc) return rc;
-    VSC_CHECK_HIP(hipMemcpy(*out, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return VSC_OK;
-}
-int sw_upload_f32(vsc_swin *e, const std::string &name, float **out) { return sw_upload_f32v(e, e->host_w.at(name), out); }
-
-int sw_upload_bf16v(vsc_swin *e, const std::vector<float> &v, const std::string &name, int64_t rows, int cols, int cols_pad, uint16_t **out) {
-    float *tmp = nullptr;
-    VSC_CHECK_HIP(hipMalloc((void **)&tmp, v.size() * 4));
-    hipError_t err = hipMemcpy(tmp, v.data(), v.size() * 4, hipMemcpyHostToDevice);
-    int rc = err == hipSuccess ? sw_alloc(e, (size_t)rows * cols_pad * 2, (void **)out) : VSC_ERR_HIP;
-    if (!rc) rc = launch_f32_to_bf16(tmp, *out, rows, cols, cols_pad, nullptr);
-    hipError_t e2 = hipDeviceSynchronize();
-    (void)hipFree(tmp);
-    if (err != hipSuccess || e2 != hipSuccess) {
-        vsc_set_error("swin: uploading %s failed", name.c_str());
-        return VSC_ERR_HIP;
-    }
-    return rc;
-}
-int sw_upload_bf16(vsc_swin *e, const std::string &name, int64_t rows, int cols, int cols_pad, uint16_t **out) {
-    return sw_upload_bf16v(e, e->host_w.at(name), name, rows, cols, cols_pad, out);
-}
 
 // 16 * sigmoid(cpb_mlp(log-spaced relative coords)) -> compact table [heads, (2w-1)^2]
 // (torch2scripts.py:100-128, 166-171).
@@ -176,37 +124,44 @@ extern "C" int vsc_swin_create(const vsc_swin_config *cfg, vsc_swin **out) {
     const int kp = c.channels * c.patch_size * c.patch_size;
     e->kpad = (kp + 63) / 64 * 64;
     const size_t C0 = c.embed_dim;
-    e->expect["patch_embed.proj.weight"] = C0 * kp;
-    e->expect["patch_embed.proj.bias"] = e->expect["patch_embed.norm.weight"] = e->expect["patch_embed.norm.bias"] = C0;
+    e->expect("patch_embed.proj.weight", C0 * kp);
+    e->expect("patch_embed.proj.bias", C0);
+    e->expect("patch_embed.norm.weight", C0);
+    e->expect("patch_embed.norm.bias", C0);
     for (int s = 0; s < c.stages; ++s) {
         const size_t C = e->dim(s), H = c.heads[s];
         for (int b = 0; b < c.depths[s]; ++b) {
             const std::string p = "layers." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
-            e->expect[p + "attn.qkv.weight"] = 3 * C * C;
-            e->expect[p + "attn.q_bias"] = e->expect[p + "attn.v_bias"] = C;
-            e->expect[p + "attn.logit_scale"] = H;
-            e->expect[p + "attn.cpb_mlp.0.weight"] = 1024;
-            e->expect[p + "attn.cpb_mlp.0.bias"] = 512;
-            e->expect[p + "attn.cpb_mlp.2.weight"] = H * 512;
-            e->expect[p + "attn.proj.weight"] = C * C;
-            e->expect[p + "attn.proj.bias"] = C;
-            e->expect[p + "norm1.weight"] = e->expect[p + "norm1.bias"] = C;
-            e->expect[p + "norm2.weight"] = e->expect[p + "norm2.bias"] = C;
-            e->expect[p + "mlp.fc1.weight"] = 4 * C * C;
-            e->expect[p + "mlp.fc1.bias"] = 4 * C;
-            e->expect[p + "mlp.fc2.weight"] = 4 * C * C;
-            e->expect[p + "mlp.fc2.bias"] = C;
+            e->expect(p + "attn.qkv.weight", 3 * C * C);
+            e->expect(p + "attn.q_bias", C);
+            e->expect(p + "attn.v_bias", C);
+            e->expect(p + "attn.logit_scale", H);
+            e->expect(p + "attn.cpb_mlp.0.weight", 1024);
+            e->expect(p + "attn.cpb_mlp.0.bias", 512);
+            e->expect(p + "attn.cpb_mlp.2.weight", H * 512);
+            e->expect(p + "attn.proj.weight", C * C);
+            e->expect(p + "attn.proj.bias", C);
+            e->expect(p + "norm1.weight", C);
+            e->expect(p + "norm1.bias", C);
+            e->expect(p + "norm2.weight", C);
+            e->expect(p + "norm2.bias", C);
+            e->expect(p + "mlp.fc1.weight", 4 * C * C);
+            e->expect(p + "mlp.fc1.bias", 4 * C);
+            e->expect(p + "mlp.fc2.weight", 4 * C * C);
+            e->expect(p + "mlp.fc2.bias", C);
         }
         if (s + 1 < c.stages) {
             const std::string p = "layers." + std::to_string(s) + ".downsample.";
-            e->expect[p + "reduction.weight"] = 8 * C * C;
-            e->expect[p + "norm.weight"] = e->expect[p + "norm.bias"] = 2 * C;
+            e->expect(p + "reduction.weight", 8 * C * C);
+            e->expect(p + "norm.weight", 2 * C);
+            e->expect(p + "norm.bias", 2 * C);
         }
     }
     const size_t CL = e->dim(c.stages - 1);
-    e->expect["norm.weight"] = e->expect["norm.bias"] = CL;
-    e->expect["output_proj.weight"] = (size_t)c.out_dim * CL;
-    e->expect["output_proj.bias"] = c.out_dim;
+    e->expect("norm.weight", CL);
+    e->expect("norm.bias", CL);
+    e->expect("output_proj.weight", (size_t)c.out_dim * CL);
+    e->expect("output_proj.bias", c.out_dim);
     *out = e;
     return VSC_OK;
 }
@@ -215,27 +170,12 @@ extern "C" void vsc_swin_destroy(vsc_swin *e) {
     if (!e) return;
     for (int l = 0; l < 2; ++l)
         if (e->ws[l].lnws) gemm_ln_workspace_forget(e->ws[l].lnws);   // its flag counters die with the buffer
-    for (void *p : e->allocs) (void)hipFree(p);
-    for (int l = 0; l < 2; ++l) {
-        if (e->lane_stream[l]) (void)hipStreamDestroy(e->lane_stream[l]);
-        if (e->ev_join[l]) (void)hipEventDestroy(e->ev_join[l]);
-    }
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    for (hipEvent_t ev : e->ev_pool) (void)hipEventDestroy(ev);
     delete e;
 }
 
 extern "C" int vsc_swin_set_weight(vsc_swin *e, const char *name, const float *host, size_t count) {
     VSC_REQUIRE(e && name && host, "swin set_weight: null argument");
-    if (e->finalized) {
-        vsc_set_error("swin set_weight(%s) after finalize", name);
-        return VSC_ERR_STATE;
-    }
-    auto it = e->expect.find(name);
-    VSC_REQUIRE(it != e->expect.end(), "swin set_weight: unknown tensor '%s' for this config", name);
-    VSC_REQUIRE(it->second == count, "swin set_weight: '%s' has %zu elements, expected %zu", name, count, it->second);
-    e->host_w[name].assign(host, host + count);
-    return VSC_OK;
+    return e->set_weight(name, host, count);
 }
 
 // one lane's workspace (sizes fixed by finalize)
@@ -246,13 +186,11 @@ static int swin_alloc_workspace(vsc_swin *e, int l) {
     // idempotent per buffer: a call that failed part-way is resumed, not repeated (nothing is allocated or counted twice)
     for (int i = 0; i < 9; ++i) {
         if (*dst[i]) continue;
-        int rc = sw_alloc(e, e->ws_sizes[i], dst[i]);
-        if (rc) return rc;
+        VSC_TRY(e->alloc(e->ws_sizes[i], dst[i]));
         e->ws_bytes += (int64_t)e->ws_sizes[i];
     }
     if (!w.lnws) {
-        int rc = sw_alloc(e, VSC_GEMM_LN_WS_BYTES, &w.lnws);
-        if (rc) return rc;
+        VSC_TRY(e->alloc(VSC_GEMM_LN_WS_BYTES, &w.lnws));
         e->ws_bytes += (int64_t)VSC_GEMM_LN_WS_BYTES;
     }
     return VSC_OK;
@@ -261,67 +199,20 @@ static int swin_alloc_workspace(vsc_swin *e, int l) {
 // chunk on: callers that never exceed max_batch per call hold one workspace only.
 static int swin_make_lanes(vsc_swin *e) {
     if (e->lanes_ready) return VSC_OK;
-    int rc = swin_alloc_workspace(e, 1);
-    if (rc) return rc;
-    for (int l = 0; l < 2; ++l) {
-        if (!e->lane_stream[l]) VSC_CHECK_HIP(hipStreamCreateWithFlags(&e->lane_stream[l], hipStreamNonBlocking));
-        if (!e->ev_join[l]) VSC_CHECK_HIP(hipEventCreateWithFlags(&e->ev_join[l], hipEventDisableTiming));
-    }
-    if (!e->ev_fork) VSC_CHECK_HIP(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
-    e->lanes_ready = true;
-    return VSC_OK;
+    VSC_TRY(swin_alloc_workspace(e, 1));
+    return e->make_lanes();
 }
-
-struct SwinProfScope {
-    vsc_swin *e;
-    hipStream_t st;
-    size_t e0 = 0;
-    int cls;
-    SwinProfScope(vsc_swin *enc, int c, hipStream_t s) : e(enc), st(s), cls(c) {
-        if (e->profile) e0 = rec();
-    }
-    ~SwinProfScope() {
-        if (!e->profile || e0 == BAD) return;
-        const size_t e1 = rec();
-        if (e1 != BAD) e->spans.push_back({cls, e0, e1});
-    }
-    static constexpr size_t BAD = ~(size_t)0;
-    // One event from the pool (recycled by get_profile / set_profiling).  A failed create / record, or a pool that has
-    // grown past MAX_EVENTS because nobody collects the profile, switches profiling off instead of recording garbage.
-    static constexpr size_t MAX_EVENTS = 1 << 16;
-    size_t rec() {
-        if (e->ev_used == e->ev_pool.size()) {
-            hipEvent_t ev;
-            if (e->ev_pool.size() >= MAX_EVENTS || hipEventCreate(&ev) != hipSuccess) {
-                e->profile = false;
-                return BAD;
-            }
-            e->ev_pool.push_back(ev);
-        }
-        if (hipEventRecord(e->ev_pool[e->ev_used], st) != hipSuccess) {
-            e->profile = false;
-            return BAD;
-        }
-        return e->ev_used++;
-    }
-};
 
 extern "C" int vsc_swin_finalize(vsc_swin *e) {
     VSC_REQUIRE(e, "swin finalize: null");
     if (e->finalized) return VSC_OK;
-    for (auto &kv : e->expect)
-        if (!e->host_w.count(kv.first)) {
-            vsc_set_error("swin finalize: weight '%s' was never set", kv.first.c_str());
-            return VSC_ERR_STATE;
-        }
+    VSC_TRY(e->all_set());
     const vsc_swin_config &c = e->cfg;
-    int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
     const int kp = c.channels * c.patch_size * c.patch_size;
-    TRY(sw_upload_bf16(e, "patch_embed.proj.weight", c.embed_dim, kp, e->kpad, &e->pe_w));
-    TRY(sw_upload_f32(e, "patch_embed.proj.bias", &e->pe_b));
-    TRY(sw_upload_f32(e, "patch_embed.norm.weight", &e->pe_g));
-    TRY(sw_upload_f32(e, "patch_embed.norm.bias", &e->pe_beta));
+    VSC_TRY(e->upload_bf16("patch_embed.proj.weight", c.embed_dim, kp, e->kpad, &e->pe_w));
+    VSC_TRY(e->upload_f32("patch_embed.proj.bias", &e->pe_b));
+    VSC_TRY(e->upload_f32("patch_embed.norm.weight", &e->pe_g));
+    VSC_TRY(e->upload_f32("patch_embed.norm.bias", &e->pe_beta));
     e->stages.resize(c.stages);
     for (int s = 0; s < c.stages; ++s) {
         const int C = e->dim(s), H = c.heads[s], W = e->window(s);
@@ -329,14 +220,14 @@ extern "C" int vsc_swin_finalize(vsc_swin *e) {
         for (int b = 0; b < c.depths[s]; ++b) {
             const std::string p = "layers." + std::to_string(s) + ".blocks." + std::to_string(b) + ".";
             SwinBlockW &B = e->stages[s].blocks[b];
-            TRY(sw_upload_bf16(e, p + "attn.qkv.weight", 3 * C, C, C, &B.qkv_w));
+            VSC_TRY(e->upload_bf16(p + "attn.qkv.weight", 3 * C, C, C, &B.qkv_w));
             std::vector<float> qb(3 * (size_t)C, 0.f);  // (q_bias | 0 | v_bias), :151-153
             const std::vector<float> &q = e->host_w.at(p + "attn.q_bias"), &v = e->host_w.at(p + "attn.v_bias");
             for (int i = 0; i < C; ++i) {
                 qb[i] = q[i];
                 qb[2 * C + i] = v[i];
             }
-            TRY(sw_upload_f32v(e, qb, &B.qkv_b));
+            VSC_TRY(e->upload_f32(qb, &B.qkv_b));
             std::vector<float> sc(H);
             const std::vector<float> &ls = e->host_w.at(p + "attn.logit_scale");
             for (int i = 0; i < H; ++i) sc[i] = expf(fminf(ls[i], logf(100.0f)));  // clamp(max = ln(1/0.01)).exp(), :161
@@ -356,44 +247,42 @@ extern "C" int vsc_swin_finalize(vsc_swin *e) {
                 for (size_t i = 0; i < side2; ++i) pb[hh * side2 + i] -= bmax + sc[hh];
                 sc[hh] = -sc[hh];
             }
-            TRY(sw_upload_f32v(e, sc, &B.scale));
-            TRY(sw_upload_f32v(e, pb, &B.bias));
-            TRY(sw_upload_bf16(e, p + "attn.proj.weight", C, C, C, &B.proj_w));
-            TRY(sw_upload_f32(e, p + "attn.proj.bias", &B.proj_b));
-            TRY(sw_upload_f32(e, p + "norm1.weight", &B.n1_g));
-            TRY(sw_upload_f32(e, p + "norm1.bias", &B.n1_b));
-            TRY(sw_upload_bf16(e, p + "mlp.fc1.weight", 4 * C, C, C, &B.fc1_w));
-            TRY(sw_upload_f32(e, p + "mlp.fc1.bias", &B.fc1_b));
-            TRY(sw_upload_bf16(e, p + "mlp.fc2.weight", C, 4 * C, 4 * C, &B.fc2_w));
+            VSC_TRY(e->upload_f32(sc, &B.scale));
+            VSC_TRY(e->upload_f32(pb, &B.bias));
+            VSC_TRY(e->upload_bf16(p + "attn.proj.weight", C, C, C, &B.proj_w));
+            VSC_TRY(e->upload_f32(p + "attn.proj.bias", &B.proj_b));
+            VSC_TRY(e->upload_f32(p + "norm1.weight", &B.n1_g));
+            VSC_TRY(e->upload_f32(p + "norm1.bias", &B.n1_b));
+            VSC_TRY(e->upload_bf16(p + "mlp.fc1.weight", 4 * C, C, C, &B.fc1_w));
+            VSC_TRY(e->upload_f32(p + "mlp.fc1.bias", &B.fc1_b));
+            VSC_TRY(e->upload_bf16(p + "mlp.fc2.weight", C, 4 * C, 4 * C, &B.fc2_w));
             if (swin_mlp_supported(C)) {
                 const std::vector<float> &w2 = e->host_w.at(p + "mlp.fc2.weight");
                 std::vector<float> w2p(w2.size());
                 swin_mlp_permute_hidden(w2.data(), w2p.data(), C);
-                TRY(sw_upload_bf16v(e, w2p, p + "mlp.fc2.weight (hidden axis reordered)", C, 4 * C, 4 * C, &B.fc2_wp));
+                VSC_TRY(e->upload_bf16(w2p, p + "mlp.fc2.weight (hidden axis reordered)", C, 4 * C, 4 * C, &B.fc2_wp));
             }
-            TRY(sw_upload_f32(e, p + "mlp.fc2.bias", &B.fc2_b));
-            TRY(sw_upload_f32(e, p + "norm2.weight", &B.n2_g));
-            TRY(sw_upload_f32(e, p + "norm2.bias", &B.n2_b));
+            VSC_TRY(e->upload_f32(p + "mlp.fc2.bias", &B.fc2_b));
+            VSC_TRY(e->upload_f32(p + "norm2.weight", &B.n2_g));
+            VSC_TRY(e->upload_f32(p + "norm2.bias", &B.n2_b));
         }
         if (s + 1 < c.stages) {
             const std::string p = "layers." + std::to_string(s) + ".downsample.";
-            TRY(sw_upload_bf16(e, p + "reduction.weight", 2 * C, 4 * C, 4 * C, &e->stages[s].red_w));
-            TRY(sw_upload_f32(e, p + "norm.weight", &e->stages[s].dn_g));
-            TRY(sw_upload_f32(e, p + "norm.bias", &e->stages[s].dn_b));
+            VSC_TRY(e->upload_bf16(p + "reduction.weight", 2 * C, 4 * C, 4 * C, &e->stages[s].red_w));
+            VSC_TRY(e->upload_f32(p + "norm.weight", &e->stages[s].dn_g));
+            VSC_TRY(e->upload_f32(p + "norm.bias", &e->stages[s].dn_b));
         }
     }
-    TRY(sw_upload_f32(e, "norm.weight", &e->norm_g));
-    TRY(sw_upload_f32(e, "norm.bias", &e->norm_b));
-    TRY(sw_upload_f32(e, "output_proj.weight", &e->out_w));
-    TRY(sw_upload_f32(e, "output_proj.bias", &e->out_b));
+    VSC_TRY(e->upload_f32("norm.weight", &e->norm_g));
+    VSC_TRY(e->upload_f32("norm.bias", &e->norm_b));
+    VSC_TRY(e->upload_f32("output_proj.weight", &e->out_w));
+    VSC_TRY(e->upload_f32("output_proj.bias", &e->out_b));
     const size_t B = c.max_batch, M0 = B * e->res(0) * e->res(0), MC = M0 * c.embed_dim;
     const size_t sz[] = {M0 * (size_t)e->kpad * 2, MC * 4, MC * 2, MC * 4, MC * 3 * 2, MC * 2, MC * 4 * 2, MC * 2,
                          B * (size_t)e->dim(c.stages - 1) * 4};
     for (int i = 0; i < 9; ++i) e->ws_sizes[i] = sz[i];
-    TRY(swin_alloc_workspace(e, 0));
-#undef TRY
-    e->host_w.clear();
-    e->finalized = true;
+    VSC_TRY(swin_alloc_workspace(e, 0));
+    e->drop_host();
     return VSC_OK;
 }
 
@@ -407,8 +296,7 @@ static int gemm_ln(vsc_swin *e, vsc_swin::Workspace &ws, const uint16_t *a, cons
     const int split_k = vsc_opt_int(OPT_SWIN_SPLIT_K, 1 << 30);
     if (!split && k < split_k && gemm_ln_supported(n, k))
         return launch_gemm_ln_bf16(a, w, bias, g, b, x_in, x_out, xb_out, m, n, k, e->cfg.ln_eps, st, ws.lnws);
-    int rc = launch_gemm_bf16(a, w, bias, nullptr, ws.t, m, n, k, VSC_EPI_F32, 0, st);
-    if (rc) return rc;
+    VSC_TRY(launch_gemm_bf16(a, w, bias, nullptr, ws.t, m, n, k, VSC_EPI_F32, 0, st));
     return launch_ln_residual(ws.t, g, b, x_in, x_out, xb_out, m, n, e->cfg.ln_eps, st);
 }
 
@@ -419,9 +307,7 @@ static int swin_run_chunks(vsc_swin *e, const float *frames, const uint8_t *fram
     const vsc_swin_config &c = e->cfg;
     const int64_t frame_elems = (int64_t)c.channels * c.image_size * c.image_size;
     const int SL = c.stages - 1, TL = e->res(SL) * e->res(SL), CL = e->dim(SL);
-    int rc;
-#define TRY(x) do { if ((rc = (x))) return rc; } while (0)
-#define PROF(cls) SwinProfScope _ps(e, (cls), st)
+#define PROF(cls) ProfScope _ps(e, (cls), st)
     // diagnostic / test switches
     const bool unfused_mlp = vsc_opt_is(OPT_SWIN_FUSED_MLP, '0');        // 0 = fc1 and fc2 as two GEMM launches
     const bool unfused_mlp512 = vsc_opt_is(OPT_SWIN_MLP512, '0');        // 0 = the 512-wide stage keeps fc1 and fc2 as two GEMM launches,
@@ -442,12 +328,12 @@ static int swin_run_chunks(vsc_swin *e, const float *frames, const uint8_t *fram
         {
             PROF(VSC_SWIN_PROF_PATCHIFY);
             if (frames)
-                TRY(launch_patchify(frames + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size, e->kpad, st));
+                VSC_TRY(launch_patchify(frames + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size, e->kpad, st));
             else
-                TRY(launch_patchify_u8(frames_u8 + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size,
-                                       e->kpad, mean, std, st));
+                VSC_TRY(launch_patchify_u8(frames_u8 + off * frame_elems, w.patches, B, c.channels, c.image_size, c.patch_size,
+                                           e->kpad, mean, std, st));
         }
-        { PROF(VSC_SWIN_PROF_PATCH_EMBED); TRY(gemm_ln(e, w, w.patches, e->pe_w, e->pe_b, e->pe_g, e->pe_beta, nullptr, w.x, w.xb, M, c.embed_dim, e->kpad, st)); }
+        { PROF(VSC_SWIN_PROF_PATCH_EMBED); VSC_TRY(gemm_ln(e, w, w.patches, e->pe_w, e->pe_b, e->pe_g, e->pe_beta, nullptr, w.x, w.xb, M, c.embed_dim, e->kpad, st)); }
         for (int s = 0; s < c.stages; ++s) {
             const int C = e->dim(s), R = e->res(s), W = e->window(s), H = c.heads[s];
             const int pc = VSC_SWIN_PROF_STAGE0 + (s < 4 ? s : 3) * VSC_SWIN_PROF_PER_STAGE;
@@ -458,9 +344,9 @@ static int swin_run_chunks(vsc_swin *e, const float *frames, const uint8_t *fram
             bool qkv_ready = false;   // the previous block's kernel already left this block's qkv in w.qkv
             for (int b = 0; b < c.depths[s]; ++b) {
                 const SwinBlockW &K = e->stages[s].blocks[b];
-                if (!qkv_ready) { PROF(pc + VSC_SWIN_PROF_QKV); TRY(launch_gemm_bf16(xb, K.qkv_w, K.qkv_b, nullptr, w.qkv, Ms, 3 * C, C, VSC_EPI_BF16, 0, st)); }
+                if (!qkv_ready) { PROF(pc + VSC_SWIN_PROF_QKV); VSC_TRY(launch_gemm_bf16(xb, K.qkv_w, K.qkv_b, nullptr, w.qkv, Ms, 3 * C, C, VSC_EPI_BF16, 0, st)); }
                 qkv_ready = false;
-                { PROF(pc + VSC_SWIN_PROF_ATTENTION); TRY(launch_window_attention(w.qkv, w.att, K.bias, K.scale, (int)Bs, R, W, e->shift(s, b), H, st)); }
+                { PROF(pc + VSC_SWIN_PROF_ATTENTION); VSC_TRY(launch_window_attention(w.qkv, w.att, K.bias, K.scale, (int)Bs, R, W, e->shift(s, b), H, st)); }
                 // (the 512-wide kernel addresses x through one 4-GiB buffer descriptor: chunks of >= 2^21 rows keep the GEMM launches)
                 // ... and small chunks too: the fused kernel gives a CU one 128-row tile at a time (one workgroup per CU, ~200 us per tile
                 // whatever else the chip does), so 40 frames = 80 tiles keep 80 of 256 CUs busy where the GEMMs' 256 x 256 tiles also split
@@ -477,24 +363,24 @@ static int swin_run_chunks(vsc_swin *e, const float *frames, const uint8_t *fram
                         // ... and the NEXT block's qkv Linear behind it, from the registers that hold the new shadow: the shadow is not
                         // written (the stage's last block writes it for the PatchMerging), the next qkv launch does not happen
                         const SwinBlockW &N = e->stages[s].blocks[b + 1];
-                        TRY(launch_swin_proj_mlp_qkv512(w.att, K.proj_w, K.proj_b, K.n1_g, K.n1_b, K.fc1_w, K.fc1_b, K.fc2_wp, K.fc2_b, K.n2_g, K.n2_b,
-                                                        N.qkv_w, N.qkv_b, x, w.qkv, Ms, e->cfg.ln_eps, st));
+                        VSC_TRY(launch_swin_proj_mlp_qkv512(w.att, K.proj_w, K.proj_b, K.n1_g, K.n1_b, K.fc1_w, K.fc1_b, K.fc2_wp, K.fc2_b, K.n2_g, K.n2_b,
+                                                            N.qkv_w, N.qkv_b, x, w.qkv, Ms, e->cfg.ln_eps, st));
                         qkv_ready = true;
                         continue;
                     }
-                    TRY(launch_swin_proj_mlp(w.att, K.proj_w, K.proj_b, K.n1_g, K.n1_b, K.fc1_w, K.fc1_b, K.fc2_wp, K.fc2_b, K.n2_g, K.n2_b, x, xb,
-                                             Ms, C, e->cfg.ln_eps, st));
+                    VSC_TRY(launch_swin_proj_mlp(w.att, K.proj_w, K.proj_b, K.n1_g, K.n1_b, K.fc1_w, K.fc1_b, K.fc2_wp, K.fc2_b, K.n2_g, K.n2_b, x, xb,
+                                                 Ms, C, e->cfg.ln_eps, st));
                     continue;
                 }
-                { PROF(pc + VSC_SWIN_PROF_PROJ_LN); TRY(gemm_ln(e, w, w.att, K.proj_w, K.proj_b, K.n1_g, K.n1_b, x, x, xb, Ms, C, C, st)); }
+                { PROF(pc + VSC_SWIN_PROF_PROJ_LN); VSC_TRY(gemm_ln(e, w, w.att, K.proj_w, K.proj_b, K.n1_g, K.n1_b, x, x, xb, Ms, C, C, st)); }
                 if (K.fc2_wp && !unfused_mlp && mlp512_ok) {
                     // both Linears, the GELU between them and the LayerNorm behind them in one kernel (swin_mlp.hip); its time is
                     // booked under fc2_ln, fc1 stays empty
                     PROF(pc + VSC_SWIN_PROF_FC2_LN);
-                    TRY(launch_swin_mlp(K.fc1_w, K.fc1_b, K.fc2_wp, K.fc2_b, K.n2_g, K.n2_b, x, xb, Ms, C, e->cfg.ln_eps, st));
+                    VSC_TRY(launch_swin_mlp(K.fc1_w, K.fc1_b, K.fc2_wp, K.fc2_b, K.n2_g, K.n2_b, x, xb, Ms, C, e->cfg.ln_eps, st));
                 } else {
-                    { PROF(pc + VSC_SWIN_PROF_FC1); TRY(launch_gemm_bf16(xb, K.fc1_w, K.fc1_b, nullptr, w.h, Ms, 4 * C, C, VSC_EPI_GELU_BF16, 0, st)); }
-                    { PROF(pc + VSC_SWIN_PROF_FC2_LN); TRY(gemm_ln(e, w, w.h, K.fc2_w, K.fc2_b, K.n2_g, K.n2_b, x, x, xb, Ms, C, 4 * C, st)); }
+                    { PROF(pc + VSC_SWIN_PROF_FC1); VSC_TRY(launch_gemm_bf16(xb, K.fc1_w, K.fc1_b, nullptr, w.h, Ms, 4 * C, C, VSC_EPI_GELU_BF16, 0, st)); }
+                    { PROF(pc + VSC_SWIN_PROF_FC2_LN); VSC_TRY(gemm_ln(e, w, w.h, K.fc2_w, K.fc2_b, K.n2_g, K.n2_b, x, x, xb, Ms, C, 4 * C, st)); }
                 }
             }
             if (s + 1 < c.stages) {
@@ -503,90 +389,53 @@ static int swin_run_chunks(vsc_swin *e, const float *frames, const uint8_t *fram
                     // the 2 x 2 gather inside the GEMM's operand staging (no [M/4, 4C] copy out and back in).  The shadow of the
                     // merged tokens cannot overwrite the tensor other workgroups are still gathering from: it goes to the
                     // buffer the copy used to fill, and the two (equally sized) buffers change roles.
-                    TRY(launch_gemm_ln_bf16(w.xb, e->stages[s].red_w, nullptr, e->stages[s].dn_g, e->stages[s].dn_b, nullptr, w.x, w.merged,
-                                            M / 4, 2 * C, 4 * C, e->cfg.ln_eps, st, w.lnws, R, C));
+                    VSC_TRY(launch_gemm_ln_bf16(w.xb, e->stages[s].red_w, nullptr, e->stages[s].dn_g, e->stages[s].dn_b, nullptr, w.x, w.merged,
+                                                M / 4, 2 * C, 4 * C, e->cfg.ln_eps, st, w.lnws, R, C));
                     uint16_t *t = w.xb;
                     w.xb = w.merged;
                     w.merged = t;
                 } else {
-                    TRY(launch_merge_gather(w.xb, w.merged, B, R, C, st));
-                    TRY(gemm_ln(e, w, w.merged, e->stages[s].red_w, nullptr, e->stages[s].dn_g, e->stages[s].dn_b, nullptr, w.x, w.xb,
-                                M / 4, 2 * C, 4 * C, st));
+                    VSC_TRY(launch_merge_gather(w.xb, w.merged, B, R, C, st));
+                    VSC_TRY(gemm_ln(e, w, w.merged, e->stages[s].red_w, nullptr, e->stages[s].dn_g, e->stages[s].dn_b, nullptr, w.x, w.xb,
+                                    M / 4, 2 * C, 4 * C, st));
                 }
             }
         }
         {
             PROF(VSC_SWIN_PROF_POOL_HEAD);
-            TRY(launch_ln_pool(w.x, e->norm_g, e->norm_b, w.pooled, tokens_out ? tokens_out + off * TL * CL : nullptr, B,
-                               TL, CL, c.ln_eps, 0, c.gem_p, st));
-            TRY(launch_head(w.pooled, e->out_w, e->out_b, desc + off * c.out_dim, B, CL, c.out_dim, c.l2_normalize, st));
+            VSC_TRY(launch_ln_pool(w.x, e->norm_g, e->norm_b, w.pooled, tokens_out ? tokens_out + off * TL * CL : nullptr, B,
+                                   TL, CL, c.ln_eps, 0, c.gem_p, st));
+            VSC_TRY(launch_head(w.pooled, e->out_w, e->out_b, desc + off * c.out_dim, B, CL, c.out_dim, c.l2_normalize, st));
         }
     }
 #undef PROF
-#undef TRY
     return VSC_OK;
 }
 
 static int swin_forward_impl(vsc_swin *e, const float *frames, const uint8_t *frames_u8, const float *mean, const float *std,
                              int64_t n, float *desc, float *tokens_out, void *stream_) {
     VSC_REQUIRE(e && (frames || frames_u8) && desc && n >= 0, "swin forward: bad argument");
-    if (!e->finalized) {
-        vsc_set_error("swin forward before finalize");
-        return VSC_ERR_STATE;
-    }
+    VSC_TRY(e->forward_ready());
     hipStream_t user = (hipStream_t)stream_;
     // >= 2 chunks: alternate them over the two lanes.  Not while profiling: per-launch events are meant to time one kernel alone.
     const bool fork = n > e->cfg.max_batch && !e->profile;
     if (fork) {
-        int rc = swin_make_lanes(e);
-        if (rc) return rc;
-        VSC_CHECK_HIP(hipEventRecord(e->ev_fork, user));
-        for (int l = 0; l < 2; ++l) VSC_CHECK_HIP(hipStreamWaitEvent(e->lane_stream[l], e->ev_fork, 0));
+        VSC_TRY(swin_make_lanes(e));
+        VSC_TRY(e->fork(user));
     }
     const int rc = swin_run_chunks(e, frames, frames_u8, mean, std, n, desc, tokens_out, user, fork);
-    if (fork) {
-        // also after a failed launch: whatever the lanes already hold is ordered before the caller's next work on `user`,
-        // so the caller may free or reuse frames / desc once its stream has drained
-        for (int l = 0; l < 2; ++l) {
-            const hipError_t e1 = hipEventRecord(e->ev_join[l], e->lane_stream[l]);
-            const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(user, e->ev_join[l], 0) : e1;
-            if (e2 != hipSuccess && !rc) {
-                vsc_set_error("swin forward: joining lane %d failed: %s", l, hipGetErrorString(e2));
-                return VSC_ERR_HIP;
-            }
-        }
-    }
-    return rc;
+    return fork ? e->join(user, rc) : rc;
 }
 
 extern "C" int vsc_swin_set_profiling(vsc_swin *e, int32_t on) {
     VSC_REQUIRE(e, "swin set_profiling: null encoder");
-    e->profile = on != 0;
-    e->spans.clear();
-    e->ev_used = 0;
-    for (int i = 0; i < VSC_SWIN_PROF_CLASSES; ++i) {
-        e->prof_ms[i] = 0;
-        e->prof_n[i] = 0;
-    }
+    e->reset(on != 0);
     return VSC_OK;
 }
 
 extern "C" int vsc_swin_get_profile(vsc_swin *e, double *ms_out, int64_t *launches_out) {
     VSC_REQUIRE(e && ms_out && launches_out, "swin get_profile: null argument");
-    VSC_CHECK_HIP(hipDeviceSynchronize());
-    for (const vsc_swin::Span &sp : e->spans) {
-        float ms = 0.f;
-        VSC_CHECK_HIP(hipEventElapsedTime(&ms, e->ev_pool[sp.e0], e->ev_pool[sp.e1]));
-        e->prof_ms[sp.cls] += ms;
-        e->prof_n[sp.cls] += 1;
-    }
-    e->spans.clear();
-    e->ev_used = 0;
-    for (int i = 0; i < VSC_SWIN_PROF_CLASSES; ++i) {
-        ms_out[i] = e->prof_ms[i];
-        launches_out[i] = e->prof_n[i];
-    }
-    return VSC_OK;
+    return e->collect(ms_out, launches_out, VSC_SWIN_PROF_CLASSES);
 }
 
 extern "C" int vsc_swin_forward_debug(vsc_swin *e, const float *frames, int64_t n, float *desc, float *tokens_out,
