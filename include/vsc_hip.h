@@ -313,6 +313,46 @@ int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const int64_t *pai
                      int32_t max_step, int32_t top_k, int32_t max_path, double min_sim, int32_t min_length, double max_iou,
                      int32_t *boxes_dev, int32_t *counts_dev, float *maxsim_dev, void *stream);
 
+/* Matching-track localisation -- the reference's generate_matching_result (VSC22-Matching-Track-1st/infer/src/utils.py:76-117:
+ * threshold, cv2.connectedComponentsWithStats, one sklearn RANSACRegressor fit per component group) -- over the refinement
+ * networks' probability maps, one workgroup per (map, threshold) item, all items of a call in one launch.
+ * maps_dev: fp32 probabilities (maps_len floats); items_host [n_items][3] = {element offset, h, w} (HOST memory): map i is the
+ * row-major [h, w] matrix at maps_dev + offset, x = row = query frame, y = column = reference frame.  thresholds / std_ratios
+ * [n_thr] (HOST): item (i, t) is map i at thresholds[t] with std_ratios[t].  Outputs (device), item index i * n_thr + t:
+ * out_segments_dev int32 [n_items * n_thr * max_segments][4] = {x first, y first, x last, y last}, out_scores_dev double
+ * [n_items * n_thr * max_segments], out_counts_dev int32 [n_items * n_thr] = segments FOUND (uncapped: a count above
+ * max_segments means only the first max_segments were stored -- call again wider).
+ * Contract (executable: tests/seg_contract.py).  sklearn's float64 lstsq puts points whose exact residual EQUALS the residual
+ * threshold at 2 +- 1e-14 and so decides them by rounding noise; here the trial phase is exact integer arithmetic and such
+ * points are inliers.  Everything else is sklearn 1.7's loop:
+ *   mask = P > threshold in fp32.  8-connected components; more than 10 pixels = large, all other masked pixels are loose.  One
+ *     group per large component (its pixels + ALL loose pixels) in raster order of the components' first pixels; without a
+ *     large component the single group is the loose pixels.  A group's points are taken in raster order (np.where).
+ *   A group with 3 or fewer distinct x is skipped.  Trial loop: n_inliers_best = 1, score_best = -inf, max_trials = 200; trial t
+ *     draws the 2-subset that sample_without_replacement(n, 2, random_state=rs) returns on its t-th call, rs = RandomState(2023)
+ *     (MT19937, masked rejection): n < 200: rs.permutation(n)[:2]; n >= 200: rs.randint(n), the second redrawn while equal.  The
+ *     trial is skipped if its inlier count k is below the best, or equal with R^2 below the best; otherwise it is kept and
+ *     max_trials = min(max_trials, ceil(log(1 - 0.99) / log(max(eps, 1 - (k / n)^2)))).
+ *   Trial model, dx = x2 - x1 != 0: inlier iff |(y - y1) dx - (y2 - y1)(x - x1)| <= 2 |dx| (integers).  Over the inliers
+ *     A = sum of that residual squared, B = k sum y^2 - (sum y)^2 (integers); R^2 = 1 - ((double)A (double)k) / ((double)dx^2
+ *     (double)B), every operation rounded on its own; B = 0: R^2 = 1 if A = 0, else 0.
+ *   dx = 0: the line is y = c, c = y1 if y1 = y2, else (w1 y1 + w2 y2) / (w1 + w2) in float64 with w = (double)(p * p), the
+ *     product in fp32; inlier iff |y - c| <= 2; res = ((double)sum y^2 - (2 c)(double)sum y) + ((double)k c) c; R^2 = 1 -
+ *     (res (double)k) / (double)B; B = 0: R^2 = 1 if res = 0, else 0.
+ *   Final model: float64 weighted least squares over the best inliers in closed form (weighted means, then sum w (x - xm)^2 and
+ *     sum w (x - xm)(y - ym); slope 0 when the former is 0).  Rejected if slope <= 0.  A point is near iff |y - (slope x + icpt)|
+ *     < 1; accepted iff more than 5 near points with more than 3 distinct x and more than 3 distinct y.  Segment = first and
+ *     last near point in raster order; score = (max(top) - std(top) std_ratio) - |max(1 / slope, slope) - 1| / 10 in float64,
+ *     top = the fp32 probabilities of the near points, std the population standard deviation.
+ *   The float64 sums of the final model are taken in the kernel's own fixed order: two runs give the same bytes; against another
+ *     summation order, decisions closer than ~1e-12 to their boundary may differ (tests/seg_contract.py reports that margin).
+ * Limits: h, w <= 224; 1 <= n_thr <= 8.  Non-finite probabilities are outside the contract.  Synchronises `stream` once (to
+ * upload the item table).  The item table lives in one per-device scratch slot that the kernel reads until it ends: calls on one
+ * device are ordered -- one stream, or streams synchronised around the call (as for the search path's scratch). */
+int vsc_match_segments_f32(const float *maps_dev, int64_t maps_len, const int64_t *items_host, int64_t n_items,
+                           const float *thresholds, const double *std_ratios, int32_t n_thr, int32_t max_segments,
+                           int32_t *out_segments_dev, double *out_scores_dev, int32_t *out_counts_dev, void *stream);
+
 /* Query view preprocessing -- the reference's image_process (VSC22-Descriptor-Track-1st/infer/src/image_preprocess.py:252-275,
  * applied to every query video by infer/src/dataset.py:82-88): the two per-video maps its border / split decisions read, and the
  * crop + resize of every view.  The decisions themselves run on the host (src/image_preprocess.py).  frames_dev: uint8

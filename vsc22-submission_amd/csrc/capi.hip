@@ -200,6 +200,13 @@ extern "C" int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const i
                            boxes_dev, counts_dev, maxsim_dev, (hipStream_t)stream);
 }
 
+extern "C" int vsc_match_segments_f32(const float *maps_dev, int64_t maps_len, const int64_t *items_host, int64_t n_items,
+                                      const float *thresholds, const double *std_ratios, int32_t n_thr, int32_t max_segments,
+                                      int32_t *out_segments_dev, double *out_scores_dev, int32_t *out_counts_dev, void *stream) {
+    return launch_match_segments(maps_dev, maps_len, items_host, n_items, thresholds, std_ratios, n_thr, max_segments, out_segments_dev,
+                                 out_scores_dev, out_counts_dev, (hipStream_t)stream);
+}
+
 extern "C" int vsc_frame_var_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, double *out_dev, void *stream) {
     return launch_frame_var_u8(frames_dev, n, h, w, out_dev, (hipStream_t)stream);
 }

@@ -294,10 +294,15 @@ int launch_f32_to_bf16(const float *src, uint16_t *dst, int64_t rows, int cols, 
 int search_scratch_get(int slot, size_t bytes, void **out);
 enum { SCRATCH_TN_TABLE = 19, SCRATCH_TN_NODES = 20 };   // slots of tn_align.hip (knn.hip uses 0-18)
 enum { SCRATCH_VIEW_CANNY = 21, SCRATCH_VIEW_RESIZE = 22 };   // slots of view_prep.hip
+enum { SCRATCH_MS_TABLE = 23 };   // slot of match_segments.hip
 // temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h
 int launch_tn_align(const float *sims, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias, int max_step,
                     int top_k, int max_path, double min_sim, int min_length, double max_iou, int32_t *boxes, int32_t *counts,
                     float *maxsim, hipStream_t stream);
+// connected components + RANSAC localisation of probability maps (match_segments.hip), contract at vsc_match_segments_f32 in include/vsc_hip.h
+int launch_match_segments(const float *maps, int64_t maps_len, const int64_t *items_host, int64_t n_items, const float *thresholds,
+                          const double *std_ratios, int n_thr, int max_segments, int32_t *segments, double *scores, int32_t *counts,
+                          hipStream_t stream);
 // query view preprocessing (view_prep.hip), contracts at vsc_frame_var_u8 / vsc_canny_count_u8 / vsc_resize_bicubic_u8 in include/vsc_hip.h
 int launch_frame_var_u8(const uint8_t *frames, int64_t n, int h, int w, double *out, hipStream_t stream);
 int launch_canny_count_u8(const uint8_t *frames, int64_t n, const int32_t *idx_host, int m, int h, int w, double low, double high,

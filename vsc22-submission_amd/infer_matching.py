@@ -11,7 +11,9 @@ descriptor track's query pipeline (extract_query_feats.py here) -- and then, per
   3. per-candidate similarity maps -> pair classifier (2 x MobileNetV3)     (generate_candidates_classfiy_feature,
                                                                              match_classify: vsc_pair_similarity_f32, vsc_conv2d_f32 ..)
   4. surviving candidates -> refinement nets (2 x HRNet, map + transpose)   (generate_matching_feature, match_refine)
-  5. connected components + RANSAC at three thresholds -> matches csv       (generate_matching_result; host code, as in the reference)
+  5. connected components + RANSAC at three thresholds -> matches csv       (generate_matching_result; host code as in the reference,
+                                                                             or --localize hip: vsc_match_segments_f32, one launch,
+                                                                             no scipy / sklearn, the maps stay on the device)
 
 This script runs 1-5 from descriptor files:
 
@@ -68,10 +70,16 @@ def query_len_map(query_list, query_frames=None) -> dict:
             for vf in query_list}
 
 
+LOCALIZE_PASSES = ((MATCH_REFINE_THRESHOLD_HIGH, 0.5), (MATCH_REFINE_THRESHOLD_MID, 1.25), (MATCH_REFINE_THRESHOLD_LOW, 2))   # :289-291
+
+
 def run(query_list, score_norm_refs, refs, sn_refs, cls_models, refine_models, query_frames=None, candidates_csv=None,
-        device="cuda"):
+        device="cuda", localize="host"):
     """Steps 1-5 on loaded VideoFeature lists and HIP models -> rows [query_id, ref_id, query_start, query_end, ref_start,
-    ref_end, score] (the reference's output columns, :306-310)."""
+    ref_end, score] (the reference's output columns, :306-310).  localize="hip": step 5 on the device, the three thresholds in
+    one launch over maps that never leave it (src.matching.generate_matching_results_hip)."""
+    if localize not in ("host", "hip"):
+        raise ValueError(f"localize must be 'host' or 'hip', not {localize!r}")
     from src import matching
     from vsc.baseline.score_normalization import normalize, query_score_normalize, transform_features
 
@@ -95,10 +103,14 @@ def run(query_list, score_norm_refs, refs, sn_refs, cls_models, refine_models, q
         best[q, r] = max(best.get((q, r), -1.0), p)
     candidate_score_list = [(q, r, p) for (q, r), p in sorted(best.items()) if p > MATCH_CLS_THRESHOLD]               # :283-284
     match_meta = matching.generate_matching_feature(query_map, ref_map, len_map, candidate_score_list)                # :285-286
-    refine_res = matching.match_refine(refine_models, match_meta, device=device)                                      # :288
+    refine_res = matching.match_refine(refine_models, match_meta, device=device, device_maps=localize == "hip")      # :288
     found = []
-    for thr, std_ratio in ((MATCH_REFINE_THRESHOLD_HIGH, 0.5), (MATCH_REFINE_THRESHOLD_MID, 1.25), (MATCH_REFINE_THRESHOLD_LOW, 2)):
-        found += matching.generate_matching_result(refine_res, threshold=thr, std_ratio=std_ratio)                  # :289-291
+    if localize == "hip":
+        for rows in matching.generate_matching_results_hip(refine_res, LOCALIZE_PASSES):
+            found += rows
+    else:
+        for thr, std_ratio in LOCALIZE_PASSES:
+            found += matching.generate_matching_result(refine_res, threshold=thr, std_ratio=std_ratio)              # :289-291
     top = {}
     for qid, rid, qs, rs, qe, re_, score in found:                                                # groupby(...).score.max() (:294)
         key = (qid, rid, float(qs), float(rs), float(qe), float(re_))
@@ -118,7 +130,7 @@ def main(args):
                                                            [load_state_dict(p) for p in args.refine_models])
     rows = run(load_features(args.query_features, Dataset.QUERIES), load_features(args.norm_refs, Dataset.REFS),
                load_features(args.refs, Dataset.REFS), load_features(args.sn_refs, Dataset.REFS), cls_models, refine_models,
-               query_frames, args.candidates_csv)
+               query_frames, args.candidates_csv, localize=args.localize)
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     with open(args.output, "w", newline="") as f:
         w = csv.writer(f)
@@ -137,5 +149,7 @@ if __name__ == "__main__":
     ap.add_argument("--refine_models", nargs="+", required=True)
     ap.add_argument("--query_frames", default=None)
     ap.add_argument("--candidates_csv", default="match_candidates_score.csv")
+    ap.add_argument("--localize", choices=("host", "hip"), default="host",
+                    help="step 5 on the host (scipy + sklearn, as the reference) or on the device (vsc_match_segments_f32)")
     ap.add_argument("--output", required=True)
     main(ap.parse_args())

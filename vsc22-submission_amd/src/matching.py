@@ -18,9 +18,12 @@ view, once for the map).  Here every candidate of a call goes through ONE ``vsc_
 over concatenated frame banks; each score is an independent ascending-k fp32 chain, so the map of the chosen
 view is a row slice of the full product -- bit for bit -- and nothing is multiplied twice.
 
-``generate_matching_result`` (utils.py:80-116) -- CPU post-processing of the refinement networks' probability
-maps, cv2 connected components + sklearn RANSAC in the reference -- is mirrored as host code with
-``scipy.ndimage.label`` in cv2's place (cv2 is not a dependency here); it is not part of the GPU path.
+``generate_matching_result`` (utils.py:80-116) -- post-processing of the refinement networks' probability maps, cv2
+connected components + sklearn RANSAC in the reference -- has two backends.  ``"host"`` (the default) mirrors it as host
+code with ``scipy.ndimage.label`` in cv2's place (cv2 is not a dependency here).  ``"hip"`` runs it on the device
+(``vsc_match_segments_f32``: one workgroup per (map, threshold), all of them in one launch) under the contract stated in
+include/vsc_hip.h -- sklearn's loop with the trial phase in exact integer arithmetic -- and needs neither scipy nor
+sklearn; with ``match_refine(..., device_maps=True)`` the probability maps never leave the device.
 """
 import dataclasses
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
@@ -257,21 +260,47 @@ def match_classify(cls_models, match_cls_feature, match_cls_info, batch_size: in
     return out
 
 
-def match_refine(refine_models, match_meta, batch_size: int = MATCH_REFINE_BATCH, device="cuda", pair_similarity=None):
+@dataclasses.dataclass
+class DeviceProbabilityMaps:
+    """The cropped probability maps of match_refine(..., device_maps=True): map i is the row-major [h, w] block of `flat`
+    (a float32 device tensor) at element offset items[i, 0], with items[i] = (offset, h, w) and ids[i] = (qid, rid)."""
+    ids: List[Tuple[str, str]]
+    items: np.ndarray
+    flat: object
+
+    def __len__(self):
+        return len(self.ids)
+
+
+def match_refine(refine_models, match_meta, batch_size: int = MATCH_REFINE_BATCH, device="cuda", pair_similarity=None,
+                 device_maps: bool = False):
     """Main.match_refine (infer_matching.py:177-204): per candidate the copy-probability map over (query frame, ref frame),
     averaged over the refinement models and over each model's transposed pass, cropped to the valid h x w.
-    -> [[qid, rid, probability map [h, w], similarity map [h, w]], ...], the input of generate_matching_result."""
+    -> [[qid, rid, probability map [h, w], similarity map [h, w]], ...], the input of generate_matching_result; with
+    ``device_maps=True`` a DeviceProbabilityMaps instead: the cropped maps stay on the device as one flat buffer plus a
+    table (the input of generate_matching_result(..., backend="hip"))."""
     import torch
 
     from vsc_hip import cnn
     data = MatchRefineDataset(match_meta, MATCH_REFINE_RESOLUTION, pair_similarity)
-    res_list = []
+    res_list, ids, table, parts, offset = [], [], [], [], 0
     for lo in range(0, len(data), batch_size):
         items = [data[i] for i in range(lo, min(lo + batch_size, len(data)))]
         feature = torch.from_numpy(np.stack([it[0] for it in items]))
-        pred = cnn.match_refine_probability(refine_models, feature.to(device)).cpu().numpy()
+        pred = cnn.match_refine_probability(refine_models, feature.to(device))
+        if device_maps:
+            for i, (_, qid, rid, h, w) in enumerate(items):
+                parts.append(pred[i, 1, :h, :w].reshape(-1))
+                ids.append((qid, rid))
+                table.append((offset, h, w))
+                offset += h * w
+            continue
+        pred = pred.cpu().numpy()
         for i, (fea, qid, rid, h, w) in enumerate(items):
             res_list.append([qid, rid, pred[i][1][:h, :w], fea[0][:h, :w]])
+    if device_maps:
+        flat = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=device)
+        return DeviceProbabilityMaps(ids, np.array(table, dtype=np.int64).reshape(-1, 3), flat)
     return res_list
 
 
@@ -308,13 +337,59 @@ def _fit_segment(prob_map: np.ndarray, x: np.ndarray, y: np.ndarray, std_ratio: 
     return [xs[0], ys[0], xs[-1], ys[-1], top.max() - top.std() * std_ratio - abs(slope - 1) / 10]
 
 
-def generate_matching_result(res_list, threshold=0.05, std_ratio=2):
+def _to_device_maps(res_list) -> DeviceProbabilityMaps:
+    """Host rows [[qid, rid, probability map, _], ...] (or a DeviceProbabilityMaps, returned as it is) -> device maps."""
+    import torch
+    if isinstance(res_list, DeviceProbabilityMaps):
+        return res_list
+    ids, table, parts, offset = [], [], [], 0
+    for qid, rid, prob_map, _ in res_list:
+        prob_map = np.ascontiguousarray(prob_map, dtype=np.float32)
+        h, w = prob_map.shape
+        ids.append((qid, rid))
+        table.append((offset, h, w))
+        parts.append(prob_map.reshape(-1))
+        offset += h * w
+    flat = np.concatenate(parts) if parts else np.zeros(0, np.float32)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return DeviceProbabilityMaps(ids, np.array(table, dtype=np.int64).reshape(-1, 3), torch.from_numpy(flat).to(dev))
+
+
+def generate_matching_results_hip(res_list, passes, max_segments: int = 8):
+    """The device backend of generate_matching_result for several (threshold, std_ratio) passes at once: one
+    vsc_match_segments_f32 launch over every (map, pass), one copy back of the segments.  -> one row list per pass, rows
+    [qid, rid, q_start, r_start, q_end, r_end, score] in map order.  Contract: vsc_match_segments_f32 in include/vsc_hip.h."""
+    from vsc_hip import _lib, ops
+    _lib.require_device()
+    passes = [(float(t), float(r)) for t, r in passes]
+    out = [[] for _ in passes]
+    maps = _to_device_maps(res_list)
+    if len(maps) == 0 or not passes:
+        return out
+    segments, scores, counts = ops.match_segments(maps.flat, maps.items, [t for t, _ in passes], [r for _, r in passes],
+                                                  max_segments)
+    segments, scores, counts = segments.cpu().numpy(), scores.cpu().numpy(), counts.cpu().numpy()
+    for i, (qid, rid) in enumerate(maps.ids):
+        for t in range(len(passes)):
+            for k in range(int(counts[i, t])):
+                out[t].append([qid, rid, *(int(v) for v in segments[i, t, k]), float(scores[i, t, k])])
+    return out
+
+
+def generate_matching_result(res_list, threshold=0.05, std_ratio=2, backend="host"):
     """[[qid, rid, probability map, similarity map], ...] -> [[qid, rid, q_start, r_start, q_end, r_end, score], ...].
+
+    ``backend="hip"`` runs on the device under the contract of vsc_match_segments_f32 (res_list may then also be the
+    DeviceProbabilityMaps of match_refine(..., device_maps=True)); it raises HipPathUnavailable without a device.
 
     Per map: pixels above ``threshold`` are split into 8-connected components; each component of more than ten
     pixels is fitted together with ALL pixels of the small components (or, when there is no large component, the
     small ones are fitted as one set); a fit yields a segment when its slope is positive and enough distinct
     frames lie within one frame of the line.  Same sklearn estimator, seed and thresholds as the reference."""
+    if backend == "hip":
+        return generate_matching_results_hip(res_list, [(threshold, std_ratio)])[0]
+    if backend != "host":
+        raise ValueError(f"backend must be 'host' or 'hip', not {backend!r}")
     match_res = []
     for qid, rid, prob_map, _ in res_list:
         loose = prob_map > threshold                 # ends up holding the pixels of the small components only

@@ -99,6 +99,8 @@ SIGNATURES = {
                                          c_void_p]),
     "vsc_tn_align_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, ctypes.c_float, c_int32, c_int32, c_int32,
                                    ctypes.c_double, c_int32, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vsc_match_segments_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                         c_void_p, c_void_p]),
     "vsc_frame_var_u8": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "vsc_canny_count_u8": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
                                      c_void_p, c_void_p]),

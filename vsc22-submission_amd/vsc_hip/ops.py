@@ -232,6 +232,41 @@ def tn_align(sims, pairs, bias: float, max_step: int, top_k: int, max_path: int,
     return boxes, counts, maxsim
 
 
+def match_segments(maps, items, thresholds, std_ratios, max_segments: int = 8):
+    """Connected components + RANSAC localisation of every probability map of a flat fp32 device tensor at every threshold,
+    one launch.  maps: flat float32 device tensor; items: int64 [n, 3] rows (element offset, h, w) on the host; thresholds /
+    std_ratios: sequences of equal length T.  -> (segments int32 [n, T, S, 4] = (x first, y first, x last, y last), scores
+    float64 [n, T, S], counts int32 [n, T]) on the device with S >= max_segments: the launch is repeated wider when an item
+    found more segments than S, so counts <= S on return (one device -> host copy of the counts per launch).  Contract and
+    limits: vsc_match_segments_f32 in include/vsc_hip.h."""
+    import numpy as np
+    lib = _rd()
+    maps = _dev(maps, torch.float32).reshape(-1)
+    items = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1, 3))
+    thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+    ratio = np.ascontiguousarray(np.asarray(std_ratios, dtype=np.float64).reshape(-1))
+    assert thr.size == ratio.size and thr.size >= 1, "one std_ratio per threshold"
+    cap = max(int(max_segments), 1)
+    segments, scores, counts = match_segments_once(maps, items, thr, ratio, cap, lib)
+    most = int(counts.max().item()) if counts.numel() else 0
+    if most > cap:                    # the counts do not depend on the slots: the second launch holds every segment
+        segments, scores, counts = match_segments_once(maps, items, thr, ratio, most, lib)
+    return segments, scores, counts
+
+
+def match_segments_once(maps, items, thr, ratio, max_segments: int, lib=None):
+    """One vsc_match_segments_f32 launch with exactly `max_segments` slots per item; the counts are NOT capped."""
+    lib = lib or _rd()
+    n, t = items.shape[0], thr.size
+    segments = torch.zeros((n, t, max_segments, 4), dtype=torch.int32, device=maps.device)
+    scores = torch.zeros((n, t, max_segments), dtype=torch.float64, device=maps.device)
+    counts = torch.zeros((n, t), dtype=torch.int32, device=maps.device)
+    check(lib.vsc_match_segments_f32(ptr(maps) if maps.numel() else None, maps.numel(), items.ctypes.data, n, thr.ctypes.data,
+                                     ratio.ctypes.data, t, int(max_segments), ptr(segments), ptr(scores), ptr(counts),
+                                     current_stream()))
+    return segments, scores, counts
+
+
 def _frames_u8(frames):
     assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3, \
         "frames must be uint8 [n, H, W, 3] on the GPU"
