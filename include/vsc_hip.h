@@ -400,6 +400,30 @@ int vsc_resize_bicubic_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32
  * infer/extract_query_feats.py:178, infer/vsc/baseline/score_normalization.py:84-88. */
 int vsc_l2_normalize_f32(float *x_dev, int64_t n, int32_t d, void *stream);
 
+/* PCA fit, the part that grows with the number of rows -- the reference fits its PCA inside the reference-side chain
+ * (infer/concat_pca_sn.py:42-54: PCA(n_components=512, random_state=2023).fit(train_features) on the concatenated, per-model
+ * normalised descriptors of every training reference).  The handle accumulates the RAW MOMENTS of fp32 rows in fp64 on the matrix
+ * pipe (v_mfma_f64_16x16x4_f64):  sum[d] = sum_rows x,  S2[d, d] = sum_rows x x^T.  Moments are additive: blocks of rows may arrive
+ * in any number of calls (and moments of several handles / ranks may be added).  The d x d eigenproblem is the caller's
+ * (vsc_hip/pca_fit.py: numpy.linalg.eigh in float64; contract in tests/pca_contract.py).
+ * Accuracy: every element is an fp64 sum of exact fp32 x fp32 products, |S2 - exact| <= n 2^-52 (|X|^T |X|) element-wise.  Rows are
+ * split over workgroups by (n, d) alone and partial sums are added in a fixed order, no atomics: the same sequence of calls gives
+ * the same bits.  16 <= d <= 4096.  One stream at a time per handle.  Scratch for the partials (< 512 MiB) grows with the largest
+ * update seen and is freed with the handle. */
+typedef struct vsc_pca_fit vsc_pca_fit;
+/* concat_pca_sn.py:42-54 (the PCA object before fit); needs a device */
+int vsc_pca_fit_create(int32_t d, vsc_pca_fit **out);
+/* concat_pca_sn.py:42-54 (fit's pass over the data): adds the n rows x_dev[i * ld .. i * ld + d), ld >= d, to the moments.  May be
+ * called any number of times; n = 0 is a no-op. */
+int vsc_pca_fit_update_f32(vsc_pca_fit *f, const float *x_dev, int64_t n, int64_t ld, void *stream);
+/* concat_pca_sn.py:42-54 (what fit has seen): sum_dev [d], s2_dev [d, d] -- the full symmetric S2, lower triangle mirrored from the
+ * upper, s2 == s2^T bit for bit -- and the row count in *n_out (HOST memory).  Any of the three may be null. */
+int vsc_pca_fit_moments_f64(vsc_pca_fit *f, double *sum_dev, double *s2_dev, int64_t *n_out, void *stream);
+/* concat_pca_sn.py:42-54 (fit's mean_ and the covariance its components diagonalise): mean_dev [d] = sum / n, cov_dev [d, d] =
+ * (S2 - n mu mu^T) / (n - 1) in fp64, every operation rounded on its own, symmetric bit for bit; fewer than 2 rows are refused. */
+int vsc_pca_fit_covariance_f64(vsc_pca_fit *f, double *mean_dev, double *cov_dev, void *stream);
+void vsc_pca_fit_destroy(vsc_pca_fit *f);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

@@ -22,7 +22,6 @@ import argparse
 import csv
 import io
 import os
-import pickle
 from zipfile import ZipFile
 
 import numpy as np
@@ -33,7 +32,7 @@ from src.matching import calclualte_low_var_dim
 from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
 from src.image_preprocess import HipViews
 from src.query_pipeline import RAW_KEY, VideoScorer, run_query_videos
-from src.query_postprocess import HipPCA, SCORE_THRESHOLD
+from src.query_postprocess import HipPCA, SCORE_THRESHOLD, load_pca_model
 from vsc.baseline.score_normalization import query_score_normalize
 from vsc.metrics import Dataset
 from vsc.storage import load_features, store_features
@@ -102,8 +101,7 @@ def main(args):
     device = torch.device("cuda", 0)
     specs = [parse_model_spec(s) for s in args.models]
     encoders = [load_encoder(arch, fmt, path, args.max_batch, precision=args.precision) for arch, fmt, path in specs]
-    with open(args.pca_model, "rb") as f:
-        pca = HipPCA(pickle.load(f))
+    pca = HipPCA(load_pca_model(args.pca_model))
     with open(args.input_file, encoding="utf-8") as f:
         vids = [x.strip() for x in f if x.strip()]
     scores = read_video_scores(args.video_scores)
@@ -134,7 +132,7 @@ def build_parser():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--split", default="test")
     ap.add_argument("--models", nargs="+", required=True, help="arch:weights_format:checkpoint_path, in concatenation order")
-    ap.add_argument("--pca_model", required=True, help="pickled sklearn PCA (mean_, components_, whiten, explained_variance_)")
+    ap.add_argument("--pca_model", required=True, help="the fitted PCA (mean_, components_, whiten, explained_variance_): .npz as concat_pca_sn.py --pca_fit hip writes it, else a pickled sklearn PCA")
     ap.add_argument("--zip_prefix", default="")
     ap.add_argument("--input_file", required=True, help="one query video id per line")
     ap.add_argument("--norm_refs", default="", help="score-normalisation reference descriptors (.npz)")

@@ -8,13 +8,14 @@ cd "$(dirname "$0")"
 export PYTHONPATH=$PYTHONPATH:$PWD
 CKPT=${CKPT:-../checkpoints}; ZIPS=${ZIPS:-../data/jpg_zips}; META=${META:-../data/meta}; OUT=${OUT:-./outputs}
 PRECISION=${PRECISION:-fp16}
+PCA_MODEL=${PCA_MODEL:-$CKPT/pca_model.pkl}    # after PCA_FIT=hip bash infer_ref.sh: PCA_MODEL=$CKPT/pca_model.npz
 for split in ${SPLITS:-train val test}; do
   # the other split's references are the score-normalisation bank (extract_query_feats.py:47-50 of the reference)
   if [ "$split" = test ]; then NORM="$OUT/train_refs.npz"; else NORM="$OUT/test_refs.npz"; fi
   python extract_query_feats.py --split "$split" --precision "$PRECISION" \
     --models "swinv2_base_256:swin_ref:$CKPT/swinv2_v115.torchscript.pt" "swinv2_base_256:swin_ref:$CKPT/swinv2_v107.torchscript.pt" \
              "swinv2_base_256:swin_ref:$CKPT/swinv2_v106.torchscript.pt" "vit_v68:timm_vit:$CKPT/vit_v68.torchscript.pt" \
-    --pca_model "$CKPT/pca_model.pkl" --zip_prefix "$ZIPS" --input_file "$META/$split/${split}_query_ids.txt" --norm_refs "$NORM" \
+    --pca_model "$PCA_MODEL" --zip_prefix "$ZIPS" --input_file "$META/$split/${split}_query_ids.txt" --norm_refs "$NORM" \
     --clip_checkpoint "$CKPT/clip.torchscript.pt" --vsm_checkpoint "$CKPT/vsm.torchscript.pt" --output_dir "$OUT" \
     --preprocess "${PREPROCESS:-none}"
 done

@@ -89,6 +89,38 @@ class HipPCA:
     __call__ = transform
 
 
+PCA_MODEL_KEYS = ("mean_", "components_", "explained_variance_", "whiten", "n_components_", "n_samples_")
+
+
+def save_pca_model(fitted, path: str) -> None:
+    """The fitted PCA as a file.  A path ending in ``.npz`` holds plain arrays under the attribute names (numpy, no pickle: what
+    ``concat_pca_sn.py --pca_fit hip`` writes); any other path is the reference's pickle of the object (concat_pca_sn.py:51-52)."""
+    if str(path).endswith(".npz"):
+        with open(path, "wb") as f:
+            np.savez(f, **{k: np.asarray(getattr(fitted, k)) for k in PCA_MODEL_KEYS})
+        return
+    import pickle
+    with open(path, "wb") as f:
+        pickle.dump(fitted, f)
+
+
+def load_pca_model(path: str):
+    """-> an object with ``mean_``, ``components_``, ``explained_variance_``, ``whiten`` (what ``HipPCA`` takes): a
+    ``vsc_hip.pca_fit.FittedPCA`` from an ``.npz`` (``allow_pickle=False``; neither pickle nor sklearn is imported), otherwise
+    whatever the reference's pickle holds (extract_query_feats.py:85-86)."""
+    if str(path).endswith(".npz"):
+        from vsc_hip.pca_fit import FittedPCA
+        with np.load(path, allow_pickle=False) as z:
+            missing = [k for k in PCA_MODEL_KEYS if k not in z.files]
+            if missing:
+                raise ValueError(f"{path} is not a PCA model file: no {missing}")
+            return FittedPCA(z["mean_"], z["components_"], z["explained_variance_"], whiten=bool(z["whiten"]),
+                             n_components_=int(z["n_components_"]), n_samples_=int(z["n_samples_"]))
+    import pickle
+    with open(path, "rb") as f:
+        return pickle.load(f)
+
+
 def greedy_select(sim: np.ndarray, frame_threshold: float = FRAME_THRESHOLD) -> List[int]:
     """sim: frame x frame similarity of one video with its diagonal removed -> indices kept (:200-207)."""
     removed = set()

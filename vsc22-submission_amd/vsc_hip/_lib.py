@@ -101,6 +101,11 @@ SIGNATURES = {
                                    ctypes.c_double, c_int32, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_match_segments_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
+    "vsc_pca_fit_create": (c_int32, [c_int32, POINTER(c_void_p)]),
+    "vsc_pca_fit_update_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
+    "vsc_pca_fit_moments_f64": (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
+    "vsc_pca_fit_covariance_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "vsc_pca_fit_destroy": (None, [c_void_p]),
     "vsc_frame_var_u8": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "vsc_canny_count_u8": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
                                      c_void_p, c_void_p]),
