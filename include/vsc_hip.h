@@ -465,7 +465,8 @@ int vsc_patchify_bf16(const float *frames_dev, uint16_t *patches_dev, int64_t n,
  * image token order; the cyclic shift and window partition are index math.  bias_dev f32
  * [heads, (2*window-1)^2]: the compact relative-position table 16*sigmoid(cpb_mlp(coords)),
  * bias(i, j) = table[(yi-yj+window-1)*(2*window-1) + xi-xj+window-1]; scale_dev f32 [heads] =
- * exp(min(logit_scale, ln 100)).
+ * exp(min(logit_scale, ln 100)).  window is 8, 12, 16 or 24 and divides res; shift is any 0 <= shift < window (the reference
+ * uses 0 and window / 2; 1 and window - 1 are tested as well); every other value of either is refused.
  * Bounded form (optional, per head): cosine logits cannot exceed U = scale + max(table).  A caller that has subtracted U from a
  * head's table and knows 2 scale + max(table) - min(table) <= 69 (so that no probability underflows) passes -scale for that
  * head: the kernel then skips the row maximum of the softmax -- the same quotient, a sixth fewer vector instructions

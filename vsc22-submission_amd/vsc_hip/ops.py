@@ -75,6 +75,31 @@ def attention_bf16(qkv, frames: int, tokens: int, heads: int):
     return out
 
 
+def attention_f32(qkv, tokens: int, heads: int, head_dim: int, seqs: int = 1, row_offsets=None, out=None):
+    """fp32 softmax(q k^T / sqrt(head_dim)) v of the video-score head; qkv [rows, 3 * heads * head_dim] float32 as q | k | v.
+    `seqs` sequences of `tokens` rows back to back (vsc_attention_f32 / vsc_attention_f32_batch), or, with row_offsets (int32
+    [seqs + 1] on the device), sequences of different lengths with `tokens` the longest one (vsc_attention_f32_varlen).
+    out: an [rows, heads * head_dim] float32 device tensor to write into (rows outside the sequences are left alone)."""
+    lib = _rd()
+    qkv = _dev(qkv, torch.float32)
+    width = heads * head_dim
+    assert qkv.dim() == 2 and qkv.shape[1] == 3 * width
+    if out is None:
+        out = torch.empty((qkv.shape[0], width), dtype=torch.float32, device=qkv.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (qkv.shape[0], width)
+    if row_offsets is not None:
+        row_offsets = _dev(row_offsets, torch.int32)
+        assert row_offsets.shape == (seqs + 1,)
+        check(lib.vsc_attention_f32_varlen(ptr(qkv), ptr(out), ptr(row_offsets), seqs, tokens, heads, head_dim, current_stream()))
+        return out
+    assert qkv.shape[0] == seqs * tokens
+    if seqs == 1:
+        check(lib.vsc_attention_f32(ptr(qkv), ptr(out), tokens, heads, head_dim, current_stream()))
+    else:
+        check(lib.vsc_attention_f32_batch(ptr(qkv), ptr(out), tokens, heads, head_dim, seqs, current_stream()))
+    return out
+
+
 def layernorm(x, gamma, beta, eps: float, out_f32: bool = False):
     lib = _rd()
     x, gamma, beta = (_dev(t, torch.float32) for t in (x, gamma, beta))
