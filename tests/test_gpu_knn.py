@@ -786,3 +786,66 @@ def test_search_scratch_release(dev):
     assert lib.vsc_search_release_scratch() == 0
     D1, I1 = ops.knn_ip(q, r, 20)
     assert torch.equal(I0, I1) and torch.equal(D0.view(torch.int32), D1.view(torch.int32))
+
+
+def test_search_entry_points_share_scratch_in_any_order(dev):
+    """The search entry points keep their device buffers in one set of grow-only scratch slots (SearchScratchSlot in
+    csrc/common.h): top-k, range search, video-pair maxima and pair similarity back to back on one device, on forced paths, so that
+    every slot is used, then asked for smaller (a 3 x 5 x 3 top-k) and larger again, and once more after a release.  Every result
+    against its oracle bit for bit, the exact range search and the repeated top-k against their first run, every last_path as forced."""
+    from oracle import knn_oracle, matching_oracle
+    from vsc_hip import _lib, ops
+    lib = _lib.require_device()
+    bits = lambda t: t.cpu().numpy().view(np.uint32)
+
+    def forced(option, path, call):
+        _lib.set_option(option, path)
+        try:
+            return call()
+        finally:
+            _lib.set_option(option, None)
+
+    qa, ra = synth.descriptor_bank(501, 130, 64), synth.descriptor_bank(502, 20000, 64)
+    qb, rb = synth.descriptor_bank(503, 130, 511), synth.descriptor_bank(504, 5000, 511)
+    qc, rc = synth.descriptor_bank(505, 200, 64), synth.descriptor_bank(506, 6000, 64)
+    rng = np.random.RandomState(9)
+    qvid, rvid = np.sort(rng.randint(0, 7, 200)).astype(np.int32), np.sort(rng.randint(0, 90, 6000)).astype(np.int32)
+    qe, re_ = synth.descriptor_bank(507, 3, 3), synth.descriptor_bank(508, 5, 3)
+    pairs = np.array([[0, 5, 10, 7], [100, 30, 19000, 129]], dtype=np.int64)
+    up = lambda x: torch.from_numpy(x).to(dev)
+    qat, rat, qbt, rbt = up(qa), up(ra), up(qb), up(rb)
+
+    # (a) top-k, pre-filter
+    Da, Ia = forced("VSC_KNN_PATH", "bf16", lambda: ops.knn_ip(qat, rat, 10))
+    assert lib.vsc_knn_last_path() == 2
+    Dr, Ir = knn_oracle.knn_ip(qa, ra, 10)
+    assert np.array_equal(Ia.cpu().numpy(), Ir) and np.array_equal(bits(Da), Dr.view(np.uint32))
+    # (b) range search, pre-filter
+    lb, Db, Ib = forced("VSC_RANGE_PATH", "bf16", lambda: ops.range_search_ip(qbt, rbt, 0.08, capacity=16))
+    assert lib.vsc_range_search_last_path() == 2
+    lr, Dr, Ir = knn_oracle.range_search_ip(qb, rb, 0.08)
+    assert lr[-1] > 0 and np.array_equal(lb.cpu().numpy(), lr) and np.array_equal(Ib.cpu().numpy(), Ir)
+    assert np.array_equal(bits(Db), Dr.view(np.uint32))
+    # (c) video-pair maxima, pre-filter
+    lc, vc, sc = forced("VSC_PAIRMAX_PATH", "bf16", lambda: ops.video_pair_max(up(qc), up(qvid), 7, up(rc), up(rvid), 90, 0.35))
+    assert lib.vsc_video_pair_max_last_path() == 2
+    want = matching_oracle.video_pair_max(qc, qvid, 7, rc, rvid, 90, 0.35)
+    assert want[0][-1] > 2 and np.array_equal(lc.cpu().numpy(), want[0]) and np.array_equal(vc.cpu().numpy(), want[1])
+    assert np.array_equal(bits(sc), want[2].view(np.uint32))
+    # (d) pair similarity (always the exact fp32 chain)
+    flat, off = ops.pair_similarity(qat, rat, pairs)
+    want = np.concatenate([knn_oracle.ip_matrix(qa[q0:q0 + qn], ra[r0:r0 + rn]).reshape(-1) for q0, qn, r0, rn in pairs])
+    assert off.tolist() == [0, 35, 35 + 30 * 129] and np.array_equal(bits(flat), want.view(np.uint32))
+    # (e) a tiny exact top-k: every slot of the exact sweep asked for far less than it holds
+    De, Ie = forced("VSC_KNN_PATH", "exact", lambda: ops.knn_ip(up(qe), up(re_), 2))
+    assert lib.vsc_knn_last_path() == 1
+    Dr, Ir = knn_oracle.knn_ip(qe, re_, 2)
+    assert np.array_equal(Ie.cpu().numpy(), Ir) and np.array_equal(bits(De), Dr.view(np.uint32))
+    # (f) release, (g) the range search of (b) on the exact path, (h) the top-k of (a) again
+    assert lib.vsc_search_release_scratch() > 0
+    lg, Dg, Ig = forced("VSC_RANGE_PATH", "exact", lambda: ops.range_search_ip(qbt, rbt, 0.08, capacity=16))
+    assert lib.vsc_range_search_last_path() == 1
+    assert torch.equal(lg, lb) and torch.equal(Ig, Ib) and torch.equal(Dg.view(torch.int32), Db.view(torch.int32))
+    Dh, Ih = forced("VSC_KNN_PATH", "bf16", lambda: ops.knn_ip(qat, rat, 10))
+    assert lib.vsc_knn_last_path() == 2
+    assert torch.equal(Ih, Ia) and torch.equal(Dh.view(torch.int32), Da.view(torch.int32))

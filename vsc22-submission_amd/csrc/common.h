@@ -292,9 +292,25 @@ int launch_f32_to_bf16(const float *src, uint16_t *dst, int64_t rows, int cols, 
 // grow-only device scratch of the search path (knn.hip), one set of slots per device; callers on one device are ordered
 // (one stream, or streams synchronised around the call)
 int search_scratch_get(int slot, size_t bytes, void **out);
-enum { SCRATCH_TN_TABLE = 19, SCRATCH_TN_NODES = 20 };   // slots of tn_align.hip (knn.hip uses 0-18)
-enum { SCRATCH_VIEW_CANNY = 21, SCRATCH_VIEW_RESIZE = 22 };   // slots of view_prep.hip
-enum { SCRATCH_MS_TABLE = 23 };   // slot of match_segments.hip
+// One owner per slot; two buffers that are live in one call never share one.  The numbers are part of nothing outside the library,
+// but tests/hip_emu/common.h mirrors SCRATCH_MS_TABLE.
+enum SearchScratchSlot {
+    // knn.hip, exact fp32 sweeps
+    SCRATCH_KNN_Q_F32 = 0, SCRATCH_KNN_R_F32 = 1,   // packed fp32 queries / references (every exact sweep, pair similarity)
+    SCRATCH_KNN_LISTS = 2,                          // exact top-k: candidate lists per workgroup
+    SCRATCH_KNN_PART = 3,                           // top-k, exact and pre-filter: sorted keys per (query, split)
+    SCRATCH_RANGE_COUNTS = 4,                       // range search, exact and pre-filter: hits per (query, split)
+    SCRATCH_PAIR_TILES = 5,                         // pair similarity: tile table
+    SCRATCH_PAIRMAX_TABLE = 6, SCRATCH_PAIRMAX_COUNTS = 7,   // video-pair maxima: [q videos][r videos] table, entries per row
+    // knn.hip, bf16 pre-filter (8-11: unused)
+    SCRATCH_PF_QB = 12, SCRATCH_PF_RB = 13,         // packed bf16 queries / references
+    SCRATCH_PF_QSTATS = 14, SCRATCH_PF_FLAGS = 15,  // per-query norms; max |r| bits + fallback flags + debug counters
+    SCRATCH_PF_LISTS = 16, SCRATCH_PF_CAND = 17, SCRATCH_PF_NCAND = 18,   // sweep lists per workgroup; survivors per (query, split), their number
+    SCRATCH_TN_TABLE = 19, SCRATCH_TN_NODES = 20,         // tn_align.hip
+    SCRATCH_VIEW_CANNY = 21, SCRATCH_VIEW_RESIZE = 22,    // view_prep.hip
+    SCRATCH_MS_TABLE = 23,                                // match_segments.hip
+    SCRATCH_SLOTS
+};
 // temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h
 int launch_tn_align(const float *sims, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias, int max_step,
                     int top_k, int max_path, double min_sim, int min_length, double max_iou, int32_t *boxes, int32_t *counts,

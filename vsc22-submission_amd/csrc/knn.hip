@@ -1307,12 +1307,12 @@ __global__ __launch_bounds__(256) void knn_rescore_kernel(const float *__restric
 }
 
 // ---- grow-only device scratch, one set per device.  Calls on one device must be ordered by the caller (one stream,
-// or streams synchronised around the call): the packed banks and candidate lists are shared between calls.
+// or streams synchronised around the call): the packed banks and candidate lists are shared between calls.  Which slot holds
+// which buffer: SearchScratchSlot in common.h.
 struct Scratch {
     void *ptr = nullptr;
     size_t bytes = 0;
 };
-constexpr int SCRATCH_SLOTS = 24;
 Scratch g_scratch[VSC_MAX_DEVICES][SCRATCH_SLOTS];
 std::mutex g_scratch_mutex;
 
@@ -1339,6 +1339,13 @@ int scratch_get(int slot, size_t bytes, void **out) {
         s.bytes = bytes;
     }
     *out = s.ptr;
+    return VSC_OK;
+}
+template <class T>
+int scratch_get(int slot, size_t bytes, T **out) {   // the same, into a typed pointer
+    void *p = nullptr;
+    VSC_TRY(scratch_get(slot, bytes, &p));
+    *out = (T *)p;
     return VSC_OK;
 }
 
@@ -1400,53 +1407,69 @@ extern "C" int vsc_knn_last_profile(float ms_out[4]) {
     return VSC_OK;
 }
 
+// How an exact fp32 sweep is cut into work items (query block of TQ, reference split) for its 512 workgroup slots, and its two
+// packed banks.  Two steps, so that a caller can ask for the buffers it sizes by the plan before anything is enqueued.
+struct ExactSweep {
+    int64_t nq, nr;
+    int d, dpad, nqb, splits, grid;
+    int64_t total_tiles, tiles_per_split;
+    float *qp, *rp;   // packed fp32 banks [nq, dpad], [nr, dpad]
+};
+static int exact_sweep_plan(int64_t nq, int64_t nr, int32_t d, ExactSweep *out) {
+    ExactSweep x{};
+    x.nq = nq; x.nr = nr; x.d = d;
+    x.dpad = (d + KS - 1) / KS * KS;
+    x.nqb = (int)((nq + TQ - 1) / TQ);
+    x.total_tiles = (nr + TR - 1) / TR;
+    int64_t want = (512 + x.nqb - 1) / x.nqb;
+    if (want > 256) want = 256;
+    if (want > x.total_tiles) want = x.total_tiles;
+    if (want < 1) want = 1;
+    x.tiles_per_split = (x.total_tiles + want - 1) / want;
+    x.splits = (int)((x.total_tiles + x.tiles_per_split - 1) / x.tiles_per_split);
+    const int64_t work = (int64_t)x.nqb * x.splits;
+    x.grid = (int)(work < 512 ? work : 512);
+    VSC_TRY(scratch_get(SCRATCH_KNN_Q_F32, (size_t)nq * x.dpad * 4, &x.qp));
+    VSC_TRY(scratch_get(SCRATCH_KNN_R_F32, (size_t)nr * x.dpad * 4, &x.rp));
+    *out = x;
+    return VSC_OK;
+}
+static int exact_sweep_pack(const ExactSweep &x, const float *q_dev, const float *r_dev, hipStream_t stream) {
+    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(x.nq * (x.dpad / 4))), dim3(256), 0, stream, q_dev, x.qp, x.nq, x.d, x.dpad);
+    VSC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(x.nr * (x.dpad / 4))), dim3(256), 0, stream, r_dev, x.rp, x.nr, x.d, x.dpad);
+    VSC_CHECK_LAUNCH();
+    return VSC_OK;
+}
+
 // exact fp32 MFMA sweep (the only path of round 1; now the path for small problems, k > 512 and the fallback)
 static int knn_exact(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k,
                      int64_t ref_id_offset, float *out_scores_dev, int64_t *out_ids_dev, hipStream_t stream) {
-    const int dpad = (d + KS - 1) / KS * KS;
     const int epl = k + TR <= 512 ? 8 : (k + TR <= 1024 ? 16 : 32);
     const int cap = 64 * epl;
-    const int nqb = (int)((nq + TQ - 1) / TQ);
-    const int64_t total_tiles = (nr + TR - 1) / TR;
-    int64_t want = (512 + nqb - 1) / nqb;
-    if (want > 256) want = 256;
-    if (want > total_tiles) want = total_tiles;
-    if (want < 1) want = 1;
-    const int64_t tiles_per_split = (total_tiles + want - 1) / want;
-    const int splits = (int)((total_tiles + tiles_per_split - 1) / tiles_per_split);
-    const int64_t work = (int64_t)nqb * splits;
-    const int grid = (int)(work < 512 ? work : 512);
-
-    void *qp, *rp, *lists, *part;
-    int rc;
-    if ((rc = scratch_get(0, (size_t)nq * dpad * 4, &qp))) return rc;
-    if ((rc = scratch_get(1, (size_t)nr * dpad * 4, &rp))) return rc;
-    if ((rc = scratch_get(2, (size_t)grid * 128 * cap * 8, &lists))) return rc;
-    if ((rc = scratch_get(3, (size_t)nq * splits * k * 8, &part))) return rc;
+    ExactSweep x;
+    unsigned long long *lists, *part;
+    VSC_TRY(exact_sweep_plan(nq, nr, d, &x));
+    VSC_TRY(scratch_get(SCRATCH_KNN_LISTS, (size_t)x.grid * 128 * cap * 8, &lists));
+    VSC_TRY(scratch_get(SCRATCH_KNN_PART, (size_t)nq * x.splits * k * 8, &part));
 
     knn_mark(0, stream);
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nq * (dpad / 4))), dim3(256), 0, stream, q_dev,
-                       (float *)qp, nq, d, dpad);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nr * (dpad / 4))), dim3(256), 0, stream, r_dev,
-                       (float *)rp, nr, d, dpad);
-    VSC_CHECK_LAUNCH();
+    VSC_TRY(exact_sweep_pack(x, q_dev, r_dev, stream));
     knn_mark(1, stream);
 
-    KnnArgs a{(const float *)qp, (const float *)rp, nq, nr, dpad, k, nqb, splits, total_tiles,
-              tiles_per_split, (unsigned long long *)lists, (unsigned long long *)part};
+    KnnArgs a{x.qp, x.rp, nq, nr, x.dpad, k, x.nqb, x.splits, x.total_tiles,
+              x.tiles_per_split, lists, part};
     if (epl == 8)
-        hipLaunchKernelGGL(knn_kernel<8>, dim3(grid), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(knn_kernel<8>, dim3(x.grid), dim3(256), 0, stream, a);
     else if (epl == 16)
-        hipLaunchKernelGGL(knn_kernel<16>, dim3(grid), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(knn_kernel<16>, dim3(x.grid), dim3(256), 0, stream, a);
     else
-        hipLaunchKernelGGL(knn_kernel<32>, dim3(grid), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(knn_kernel<32>, dim3(x.grid), dim3(256), 0, stream, a);
     VSC_CHECK_LAUNCH();
     knn_mark(2, stream);
     knn_mark(3, stream);   // no re-scoring phase on this path
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream,
-                       (const unsigned long long *)part, nq, splits, k, ref_id_offset, out_scores_dev,
-                       out_ids_dev);
+                       (const unsigned long long *)part, nq, x.splits, k, ref_id_offset, out_scores_dev, out_ids_dev);
     VSC_CHECK_LAUNCH();
     knn_mark(4, stream);
     return VSC_OK;
@@ -1552,90 +1575,179 @@ static int launch_sweep(const SweepArgs &a, int grid, hipStream_t stream) {
     return (nkt & (nkt - 1)) == 0 ? launch_sweep_t<EPL, 1>(a, grid, stream) : launch_sweep_t<EPL, 2>(a, grid, stream);
 }
 
+// ---- what every entry point that goes through the bf16 pre-filter shares: the plan, its seven buffers, the packed operands and
+// the sweep's arguments.  Two steps: prefilter_plan (host only) and prefilter_pack (enqueues), so that a caller can ask for the
+// buffer it sizes by the plan (top-k: parts, range search: counts) before anything is enqueued.
+struct Prefilter {
+    SweepPlan pl;
+    int d, cap, keep;    // cap = 64 EPL keys per list, keep = cap / 2 survivors
+    int64_t nlists;      // nq * splits
+    uint16_t *qb, *rb;   // bf16 [nq, dp], [nr, dp]
+    float *qstats;       // [nq][4]
+    // one buffer of flag_bytes, zeroed per call: [0..1] max |r|, max |dr| bits (16 bytes with their padding); fb_dev = [4 .. 4 + nqb]
+    // fallback flags ([0] any, [1 + b] query block b); a.dbg = the debug counters, 8-byte aligned behind them (8 of slack + 96)
+    unsigned *flags;
+    size_t flag_bytes;
+    int *fb_dev;
+    SweepArgs a;         // complete but for k (and, for a fixed threshold, thr_mode / thr0): set by the caller
+};
+static int prefilter_plan(int64_t nq, int64_t nr, int32_t d, int epl, Prefilter *out) {
+    Prefilter pf{};
+    const int dp = prefilter_dp(d);
+    VSC_TRY(sweep_plan(nq, nr, dp, &pf.pl));
+    const SweepPlan &pl = pf.pl;
+    pf.d = d;
+    pf.cap = 64 * epl;
+    pf.keep = pf.cap / 2;
+    pf.nlists = nq * pl.splits;
+    pf.flag_bytes = 16 + (size_t)(1 + pl.nqb) * 4 + 8 + 96;
+    SweepArgs &a = pf.a;
+    VSC_TRY(scratch_get(SCRATCH_PF_QB, (size_t)nq * dp * 2, &pf.qb));
+    VSC_TRY(scratch_get(SCRATCH_PF_RB, (size_t)nr * dp * 2, &pf.rb));
+    VSC_TRY(scratch_get(SCRATCH_PF_QSTATS, (size_t)nq * 16, &pf.qstats));
+    VSC_TRY(scratch_get(SCRATCH_PF_FLAGS, pf.flag_bytes, &pf.flags));
+    VSC_TRY(scratch_get(SCRATCH_PF_LISTS, (size_t)pl.grid * SQ * pf.cap * 8, &a.lists));
+    VSC_TRY(scratch_get(SCRATCH_PF_CAND, (size_t)pf.nlists * pf.keep * 8, &a.cand));
+    VSC_TRY(scratch_get(SCRATCH_PF_NCAND, (size_t)pf.nlists * 4, &a.ncand));
+    pf.fb_dev = (int *)pf.flags + 4;
+    a.qb = pf.qb; a.rb = pf.rb; a.qstats = pf.qstats; a.rmax_bits = pf.flags;
+    a.nq = nq; a.nr = nr; a.dp = dp;
+    a.nqb = pl.nqb; a.splits = pl.splits; a.total_tiles = pl.total_tiles; a.tiles_per_split = pl.tiles_per_split;
+    a.cd = (float)d * (2.384185791015625e-7f + 5.9604644775390625e-8f);   // d (2^-22 + 2^-24)
+    a.fallback = pf.fb_dev;
+    a.abl = 0;
+    a.dbg = (unsigned long long *)(((uintptr_t)(pf.fb_dev + 1 + pl.nqb) + 7) & ~(uintptr_t)7);
+    a.trig = pf.cap - 2 * SR;
+    a.xcd_map = pl.xcd_map;
+    *out = pf;
+    return VSC_OK;
+}
+// zeroes the flags and packs both operands; `mark` (top-k only): the pack is phase 0 of the call's profile
+static int prefilter_pack(const Prefilter &pf, const float *q_dev, const float *r_dev, hipStream_t stream, bool mark) {
+    VSC_CHECK_HIP(hipMemsetAsync(pf.flags, 0, pf.flag_bytes, stream));
+    if (mark) knn_mark(0, stream);
+    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(pf.a.nq * 64)), dim3(256), 0, stream, q_dev, pf.qb, pf.qstats,
+                       (unsigned *)nullptr, pf.a.nq, pf.d, pf.a.dp);
+    VSC_CHECK_LAUNCH();
+    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(pf.a.nr * 64)), dim3(256), 0, stream, r_dev, pf.rb, (float *)nullptr,
+                       pf.flags, pf.a.nr, pf.d, pf.a.dp);
+    VSC_CHECK_LAUNCH();
+    if (mark) knn_mark(1, stream);
+    return VSC_OK;
+}
+
+// dynamic LDS of knn_rescore_kernel: 4 waves x 2 gather buffers x 64 candidates x 36 floats (a 32-float chunk + 4 of padding) x 4 bytes
+constexpr int RESCORE_LDS_BYTES = 4 * 2 * 64 * 36 * 4;
+// exact re-scoring of a sweep's survivors, one wave per list (`nlists` lists of `splits` per query)
+template <int EPL, int MODE>
+static int launch_rescore(const Prefilter &pf, const float *q_dev, const float *r_dev, int64_t nlists, int splits, int k,
+                          unsigned long long *part, const PairMaxOut &pm, int lstride, hipStream_t stream) {
+    auto kern = knn_rescore_kernel<EPL, MODE>;
+    VSC_TRY(vsc_allow_dynamic_lds(kern, RESCORE_LDS_BYTES));
+    hipLaunchKernelGGL(kern, dim3((unsigned)((nlists + 3) / 4)), dim3(256), RESCORE_LDS_BYTES, stream, q_dev, r_dev, nlists, pf.d, splits, k,
+                       (const unsigned long long *)pf.a.cand, (const int *)pf.a.ncand, part, pm, lstride);
+    VSC_CHECK_LAUNCH();
+    return VSC_OK;
+}
+
+// Reads back a sweep's fallback flags (the call's host synchronisation) and has `redo(row0, rows)` redo every maximal run of
+// flagged query blocks (contiguous rows in, contiguous rows out) on the exact sweep; *redone = number of such blocks.
+template <class Redo>
+static int redo_flagged_runs(const Prefilter &pf, hipStream_t stream, int *redone, Redo redo) {
+    const int nqb = pf.pl.nqb;
+    const int64_t nq = pf.a.nq;
+    std::vector<int> fb(1 + nqb);
+    VSC_CHECK_HIP(hipMemcpyAsync(fb.data(), pf.fb_dev, fb.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+    VSC_CHECK_HIP(hipStreamSynchronize(stream));
+    *redone = 0;
+    if (!fb[0]) return VSC_OK;
+    for (int b = 0; b < nqb;) {
+        if (!fb[1 + b]) { ++b; continue; }
+        int e = b;
+        while (e < nqb && fb[1 + e]) ++e;
+        const int64_t row0 = (int64_t)b * SQ, rows = ((int64_t)e * SQ < nq ? (int64_t)e * SQ : nq) - row0;
+        VSC_TRY(redo(row0, rows));
+        *redone += e - b;
+        b = e;
+    }
+    return VSC_OK;
+}
+
+// VSC_KNN_ABL & 16 / & 8: the instrumented sweep's counters, to stderr (after the call's host synchronisation)
+static int print_sweep_diagnostics(const Prefilter &pf) {
+    if (pf.a.abl & 16) {
+        unsigned long long h[11];
+        VSC_CHECK_HIP(hipMemcpy(h, pf.a.dbg, sizeof(h), hipMemcpyDeviceToHost));
+        fprintf(stderr, "knn sweep phase cycles (wave 0 of workgroup 1): K loop + barrier %llu, compaction rounds %llu, thresholds + best-of-16 %llu, "
+                        "masks %llu, counters %llu, keys (queued) %llu, flush + tail %llu\n", h[4], h[5], h[6], h[7], h[8], h[10], h[9]);
+    }
+    if (pf.a.abl & 8) {
+        unsigned long long h[4];
+        VSC_CHECK_HIP(hipMemcpy(h, pf.a.dbg, sizeof(h), hipMemcpyDeviceToHost));
+        fprintf(stderr, "knn sweep counters: appends %llu (%.1f per query and split), compaction rounds %llu, lists compacted %llu, (wave, query) key walks with two or more hits in a lane %llu\n",
+                h[0], (double)h[0] / (double)pf.nlists, h[1], h[2], h[3]);
+    }
+    return VSC_OK;
+}
+
+// The pre-filter pays once the sweep dominates its fixed costs (two pack passes, the re-scoring launch and one host
+// synchronisation for the fallback flags): from ~16 M pairs and a few thousand references on.
+static inline bool prefilter_pays(int64_t nq, int64_t nr) { return nr >= 4096 && nq * nr >= (1ll << 24); }
+// VSC_{KNN,RANGE,PAIRMAX}_PATH=exact|bf16 forces one path (tests run both); anything else: the default
+static bool use_prefilter(VscOpt path, bool dflt) {
+    const char *e = vsc_opt(path);
+    return e && e[0] == 'b' ? true : (e && e[0] == 'e' ? false : dflt);
+}
+
 // bf16 pre-filter sweep + exact re-scoring.  Query blocks (256 queries) whose candidate bands did not fit, or whose
 // bound is not finite, are redone on the exact sweep; *fell_back = number of such blocks.
 static int knn_prefilter(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k,
                          int64_t ref_id_offset, float *out_scores_dev, int64_t *out_ids_dev, hipStream_t stream,
                          int *fell_back, const float *floor_dev = nullptr) {
-    const int dp = prefilter_dp(d);
     // CAP = 1024 / 2048 keys per list, KEEP = CAP / 2 survivors.  A list must hold k + its 2 eps band (about as many again) + a tile's
     // appends: the small form up to k = 128, the large one up to k = 384 (k = 256 on the small form overflowed its bands and redid every
     // block on the exact sweep: 1 490 ms for 65 536 x 1M against 105 now; tools/micro/knn_kd_scan.py)
     const int epl = k <= 128 ? 16 : 32;
-    const int cap = 64 * epl, keep = cap / 2;
-    SweepPlan pl;
-    int rc;
-    if ((rc = sweep_plan(nq, nr, dp, &pl))) return rc;
-    const int nqb = pl.nqb, splits = pl.splits, grid = pl.grid;
-    const int64_t total_tiles = pl.total_tiles, tiles_per_split = pl.tiles_per_split;
+    Prefilter pf;
+    unsigned long long *part;
+    VSC_TRY(prefilter_plan(nq, nr, d, epl, &pf));
+    VSC_TRY(scratch_get(SCRATCH_KNN_PART, (size_t)pf.nlists * k * 8, &part));
+    const int splits = pf.pl.splits, cap = pf.cap, keep = pf.keep;
     // few splits of a large call: their bands are merged per query before the exact re-scoring (knn_union_kernel)
-    const bool merge_bands = splits > 1 && (int64_t)splits * keep <= 64 * 32 && nqb >= 64;
-    const int64_t nlists = nq * splits;
+    const bool merge_bands = splits > 1 && (int64_t)splits * keep <= 64 * 32 && pf.pl.nqb >= 64;
 
-    void *qb, *rb, *qstats, *flags, *lists, *cand, *ncand, *part;
-    const size_t flag_bytes = 16 + (size_t)(1 + nqb) * 4 + 8 + 96;   // [0..1] max |r|, max |dr| bits; [4..] fallback flags; debug counters behind them
-    if ((rc = scratch_get(12, (size_t)nq * dp * 2, &qb))) return rc;
-    if ((rc = scratch_get(13, (size_t)nr * dp * 2, &rb))) return rc;
-    if ((rc = scratch_get(14, (size_t)nq * 16, &qstats))) return rc;
-    if ((rc = scratch_get(15, flag_bytes, &flags))) return rc;
-    if ((rc = scratch_get(16, (size_t)grid * SQ * cap * 8, &lists))) return rc;
-    if ((rc = scratch_get(17, (size_t)nlists * keep * 8, &cand))) return rc;
-    if ((rc = scratch_get(18, (size_t)nlists * 4, &ncand))) return rc;
-    if ((rc = scratch_get(3, (size_t)nlists * k * 8, &part))) return rc;
-    int *fb_dev = (int *)flags + 4;
-
-    VSC_CHECK_HIP(hipMemsetAsync(flags, 0, flag_bytes, stream));
-    knn_mark(0, stream);
-    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(nq * 64)), dim3(256), 0, stream, q_dev, (uint16_t *)qb,
-                       (float *)qstats, (unsigned *)nullptr, nq, d, dp);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(nr * 64)), dim3(256), 0, stream, r_dev, (uint16_t *)rb,
-                       (float *)nullptr, (unsigned *)flags, nr, d, dp);
-    VSC_CHECK_LAUNCH();
-    knn_mark(1, stream);
-    const float cd = (float)d * (2.384185791015625e-7f + 5.9604644775390625e-8f);   // d (2^-22 + 2^-24)
-    SweepArgs a{(const uint16_t *)qb, (const uint16_t *)rb, (const float *)qstats, (const unsigned *)flags, nq, nr, dp, k, nqb,
-                splits, total_tiles, tiles_per_split, cd, (unsigned long long *)lists, (unsigned long long *)cand,
-                (int *)ncand, fb_dev, 0, nullptr, cap - 2 * SR};
-    a.xcd_map = pl.xcd_map;
+    VSC_TRY(prefilter_pack(pf, q_dev, r_dev, stream, /*mark=*/true));
+    SweepArgs &a = pf.a;
+    a.k = k;
     if (floor_dev) {
-        hipLaunchKernelGGL(knn_set_floor_kernel, dim3(blocks_for(nq)), dim3(256), 0, stream, floor_dev, (float *)qstats, nq);
+        hipLaunchKernelGGL(knn_set_floor_kernel, dim3(blocks_for(nq)), dim3(256), 0, stream, floor_dev, pf.qstats, nq);
         VSC_CHECK_LAUNCH();
     }
     if (const int t = vsc_opt_int(OPT_KNN_TRIG, 0); t >= k && t <= cap - 2 * SR) a.trig = t;
     a.delta = cap;   // measured (tools/micro/knn_trig.py, 65536 x 1M, k = 100): 64 / 100 / 150 / 200 / 400 appends between compactions -> 79.6 / 73.4 / 71.0 / 68.7 / 66.8 ms: the
                      // appends are already within 25 % of their floor (the 2 eps band doubles the effective k), rounds stall the workgroup
     if (const int t = vsc_opt_int(OPT_KNN_DELTA, 0); t >= 16 && t <= cap) a.delta = t;
-    a.dbg = (unsigned long long *)(((uintptr_t)(fb_dev + 1 + nqb) + 7) & ~(uintptr_t)7);
     a.abl = vsc_opt_int(OPT_KNN_ABL, 0);
-    if ((rc = epl == 16 ? launch_sweep<16>(a, grid, stream) : launch_sweep<32>(a, grid, stream))) return rc;
+    VSC_TRY(epl == 16 ? launch_sweep<16>(a, pf.pl.grid, stream) : launch_sweep<32>(a, pf.pl.grid, stream));
     knn_mark(2, stream);
     // re-scoring and the merge across splits: per (query, split) list, or -- after the union -- per query
-    int64_t rlists = nlists;
+    int64_t rlists = pf.nlists;
     int rsplits = splits, lstride = 1;
     if (merge_bands) {
         const unsigned ugrid = (unsigned)((nq + 3) / 4);
         if ((int64_t)splits * keep <= 64 * 16)
-            hipLaunchKernelGGL(knn_union_kernel<16>, dim3(ugrid), dim3(256), 0, stream, (unsigned long long *)cand, (int *)ncand,
-                               (const float *)qstats, (const unsigned *)flags, cd, nq, splits, keep, k, fb_dev);
+            hipLaunchKernelGGL(knn_union_kernel<16>, dim3(ugrid), dim3(256), 0, stream, a.cand, a.ncand, (const float *)pf.qstats,
+                               (const unsigned *)pf.flags, a.cd, nq, splits, keep, k, pf.fb_dev);
         else
-            hipLaunchKernelGGL(knn_union_kernel<32>, dim3(ugrid), dim3(256), 0, stream, (unsigned long long *)cand, (int *)ncand,
-                               (const float *)qstats, (const unsigned *)flags, cd, nq, splits, keep, k, fb_dev);
+            hipLaunchKernelGGL(knn_union_kernel<32>, dim3(ugrid), dim3(256), 0, stream, a.cand, a.ncand, (const float *)pf.qstats,
+                               (const unsigned *)pf.flags, a.cd, nq, splits, keep, k, pf.fb_dev);
         VSC_CHECK_LAUNCH();
         rlists = nq;
         rsplits = 1;
         lstride = splits;
     }
-    const unsigned rgrid = (unsigned)((rlists + 3) / 4);
-    VSC_TRY(vsc_allow_dynamic_lds(knn_rescore_kernel<8>, 4 * 2 * 64 * 36 * 4));
-    VSC_TRY(vsc_allow_dynamic_lds(knn_rescore_kernel<16>, 4 * 2 * 64 * 36 * 4));
-    if (epl == 16)
-        hipLaunchKernelGGL(knn_rescore_kernel<8>, dim3(rgrid), dim3(256), 4 * 2 * 64 * 36 * 4, stream, q_dev, r_dev, rlists, d, rsplits,
-                           k, (const unsigned long long *)cand, (const int *)ncand, (unsigned long long *)part, PairMaxOut{}, lstride);
-    else
-        hipLaunchKernelGGL(knn_rescore_kernel<16>, dim3(rgrid), dim3(256), 4 * 2 * 64 * 36 * 4, stream, q_dev, r_dev, rlists, d,
-                           rsplits, k, (const unsigned long long *)cand, (const int *)ncand, (unsigned long long *)part, PairMaxOut{}, lstride);
-    VSC_CHECK_LAUNCH();
+    VSC_TRY((epl == 16 ? launch_rescore<8, 0>(pf, q_dev, r_dev, rlists, rsplits, k, part, PairMaxOut{}, lstride, stream)
+                       : launch_rescore<16, 0>(pf, q_dev, r_dev, rlists, rsplits, k, part, PairMaxOut{}, lstride, stream)));
     knn_mark(3, stream);
     hipLaunchKernelGGL(knn_merge_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, stream,
                        (const unsigned long long *)part, nq, rsplits, k, ref_id_offset, out_scores_dev, out_ids_dev);
@@ -1644,35 +1756,10 @@ static int knn_prefilter(const float *q_dev, int64_t nq, const float *r_dev, int
     const bool was_profiling = g_knn_profiling;
     g_knn_profiling = false;   // the events of this call stay those of the pre-filter phases if blocks are redone below
     struct Restore { bool v; ~Restore() { g_knn_profiling = v; } } restore{was_profiling};
-    std::vector<int> fb(1 + nqb);
-    VSC_CHECK_HIP(hipMemcpyAsync(fb.data(), fb_dev, fb.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
-    VSC_CHECK_HIP(hipStreamSynchronize(stream));
-    *fell_back = 0;
-    if (a.abl & 16) {
-        unsigned long long h[11];
-        VSC_CHECK_HIP(hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "knn sweep phase cycles (wave 0 of workgroup 1): K loop + barrier %llu, compaction rounds %llu, thresholds + best-of-16 %llu, "
-                        "masks %llu, counters %llu, keys (queued) %llu, flush + tail %llu\n", h[4], h[5], h[6], h[7], h[8], h[10], h[9]);
-    }
-    if (a.abl & 8) {
-        unsigned long long h[4];
-        VSC_CHECK_HIP(hipMemcpy(h, a.dbg, sizeof(h), hipMemcpyDeviceToHost));
-        fprintf(stderr, "knn sweep counters: appends %llu (%.1f per query and split), compaction rounds %llu, lists compacted %llu, (wave, query) key walks with two or more hits in a lane %llu\n",
-                h[0], (double)h[0] / (double)nlists, h[1], h[2], h[3]);
-    }
-    if (!fb[0]) return VSC_OK;
-    // redo the flagged query blocks (contiguous rows in, contiguous rows out) on the exact sweep, runs of blocks at a time
-    for (int b = 0; b < nqb;) {
-        if (!fb[1 + b]) { ++b; continue; }
-        int e = b;
-        while (e < nqb && fb[1 + e]) ++e;
-        const int64_t row0 = (int64_t)b * SQ, rows = ((int64_t)e * SQ < nq ? (int64_t)e * SQ : nq) - row0;
-        if ((rc = knn_exact(q_dev + row0 * d, rows, r_dev, nr, d, k, ref_id_offset, out_scores_dev + row0 * k,
-                            out_ids_dev + row0 * k, stream))) return rc;
-        *fell_back += e - b;
-        b = e;
-    }
-    return VSC_OK;
+    VSC_TRY(redo_flagged_runs(pf, stream, fell_back, [&](int64_t row0, int64_t rows) {
+        return knn_exact(q_dev + row0 * d, rows, r_dev, nr, d, k, ref_id_offset, out_scores_dev + row0 * k, out_ids_dev + row0 * k, stream);
+    }));
+    return print_sweep_diagnostics(pf);
 }
 
 // Merge of per-shard top-k lists (sharded / pipelined search: every shard of the bank was swept on its own, with its id offset):
@@ -1745,7 +1832,55 @@ __global__ __launch_bounds__(256) void knn_floor_kernel(const float *__restrict_
 }
 
 static int knn_ip_impl(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k, int64_t ref_id_offset,
-                       const float *floor_dev, float *out_scores_dev, int64_t *out_ids_dev, hipStream_t stream);
+                       const float *floor_dev, float *out_scores_dev, int64_t *out_ids_dev, hipStream_t stream) {
+    VSC_REQUIRE(q_dev && r_dev && out_scores_dev && out_ids_dev, "knn: null pointer");
+    VSC_REQUIRE(nq > 0 && nr > 0, "knn: empty query or reference set (nq=%lld nr=%lld)", (long long)nq,
+                (long long)nr);
+    VSC_REQUIRE(d > 0 && d <= 4096, "knn: dimension %d unsupported", d);
+    VSC_REQUIRE(k >= 1 && k <= 1024, "knn: k=%d out of range [1,1024]", k);
+    VSC_REQUIRE(nr < (1ll << 32) - 1, "knn: more than 2^32-2 references in one call");
+    // Path: prefilter_pays, and VSC_KNN_PATH=exact|bf16 forces one (bf16: up to k = 512).
+    // (beyond k = 384 the bands outgrow the lists, and so they do beyond d = 1024, where the error bound d 2^-22 |q||r| widens them:
+    // the exact sweep at once instead of a pre-filter sweep whose every block is redone -- 65 536 x 1M at d = 2048: 2 560 ms)
+    if (use_prefilter(OPT_KNN_PATH, k <= 384 && d <= 1024 && prefilter_pays(nq, nr)) && k <= 512) {
+        // Tail balancing.  Query blocks (256 queries) are dealt to 256 persistent workgroups in rounds; with one split per block a call
+        // of 3 907 blocks (1M queries) runs 15.26 rounds and its sixteenth keeps 67 of 256 CUs busy.  The blocks of that last partial
+        // round are swept as a call of their own, which cuts the bank into as many splits as fill the chip once (sweep_plan): a
+        // third-size round instead of a whole one.  Queries are independent: the results are the same bits.  VSC_KNN_TAIL=0: one sweep.
+        // (Round 5, second step: from 257 blocks on -- 70 000 x 1M ran two rounds, 107 ms, for 1.07 rounds of work -- and decided by the
+        // plan's cost model instead of a fixed window of remainders.)
+        const int64_t nqb = (nq + SQ - 1) / SQ, rem = nqb % 256;
+        g_knn_set = 0;
+        bool split_tail = false;
+        if (!vsc_opt_is(OPT_KNN_TAIL, '0') && nqb > 256 && rem != 0) {
+            // by the plan's own cost model: whole rounds at one split + the tail's best plan + a second pack of the bank and the
+            // launches (~0.05 of a round), against the best plan for the call as a whole
+            const int dp = prefilter_dp(d);
+            SweepPlan whole, head_pl, tail_pl;
+            VSC_TRY(sweep_plan(nq, nr, dp, &whole));
+            VSC_TRY(sweep_plan((nqb - rem) * SQ, nr, dp, &head_pl));
+            VSC_TRY(sweep_plan(nq - (nqb - rem) * SQ, nr, dp, &tail_pl));
+            split_tail = head_pl.cost + tail_pl.cost + 0.05 < whole.cost;
+        }
+        if (split_tail) {
+            const int64_t head = (nqb - rem) * SQ;
+            int fb0 = 0, fb1 = 0;
+            VSC_TRY(knn_prefilter(q_dev, head, r_dev, nr, d, k, ref_id_offset, out_scores_dev, out_ids_dev, stream, &fb0, floor_dev));
+            g_knn_set = 1;
+            const int rc = knn_prefilter(q_dev + head * d, nq - head, r_dev, nr, d, k, ref_id_offset, out_scores_dev + head * k,
+                                         out_ids_dev + head * k, stream, &fb1, floor_dev ? floor_dev + head : nullptr);
+            g_knn_set = 0;
+            g_knn_last_path = (fb0 || fb1) ? 3 : 2;
+            return rc;
+        }
+        int fb = 0;
+        const int rc = knn_prefilter(q_dev, nq, r_dev, nr, d, k, ref_id_offset, out_scores_dev, out_ids_dev, stream, &fb, floor_dev);
+        g_knn_last_path = fb ? 3 : 2;
+        return rc;
+    }
+    g_knn_last_path = 1;
+    return knn_exact(q_dev, nq, r_dev, nr, d, k, ref_id_offset, out_scores_dev, out_ids_dev, stream);
+}
 
 extern "C" int vsc_knn_ip_f32(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr,
                               int32_t d, int32_t k, int64_t ref_id_offset, float *out_scores_dev,
@@ -1762,64 +1897,6 @@ extern "C" int vsc_knn_ip_floor_f32(const float *q_dev, int64_t nq, const float 
     hipLaunchKernelGGL(knn_floor_kernel, dim3(blocks_for(nq * k)), dim3(256), 0, stream, floor_dev, nq, k, out_scores_dev, out_ids_dev);
     VSC_CHECK_LAUNCH();
     return VSC_OK;
-}
-
-static int knn_ip_impl(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k, int64_t ref_id_offset,
-                       const float *floor_dev, float *out_scores_dev, int64_t *out_ids_dev, hipStream_t stream) {
-    VSC_REQUIRE(q_dev && r_dev && out_scores_dev && out_ids_dev, "knn: null pointer");
-    VSC_REQUIRE(nq > 0 && nr > 0, "knn: empty query or reference set (nq=%lld nr=%lld)", (long long)nq,
-                (long long)nr);
-    VSC_REQUIRE(d > 0 && d <= 4096, "knn: dimension %d unsupported", d);
-    VSC_REQUIRE(k >= 1 && k <= 1024, "knn: k=%d out of range [1,1024]", k);
-    VSC_REQUIRE(nr < (1ll << 32) - 1, "knn: more than 2^32-2 references in one call");
-    // Path: the pre-filter pays once the sweep dominates (its fixed costs: two pack passes, the re-scoring launch and
-    // one host synchronisation for the fallback flag).  VSC_KNN_PATH=exact|bf16 forces one (tests run both).
-    // (beyond k = 384 the bands outgrow the lists, and so they do beyond d = 1024, where the error bound d 2^-22 |q||r| widens them:
-    // the exact sweep at once instead of a pre-filter sweep whose every block is redone -- 65 536 x 1M at d = 2048: 2 560 ms)
-    bool prefilter = k <= 384 && d <= 1024 && nr >= 4096 && nq * nr >= (1ll << 24);
-    if (const char *e = vsc_opt(OPT_KNN_PATH)) {
-        if (e[0] == 'e') prefilter = false;
-        if (e[0] == 'b') prefilter = k <= 512;
-    }
-    if (prefilter) {
-        // Tail balancing.  Query blocks (256 queries) are dealt to 256 persistent workgroups in rounds; with one split per block a call
-        // of 3 907 blocks (1M queries) runs 15.26 rounds and its sixteenth keeps 67 of 256 CUs busy.  The blocks of that last partial
-        // round are swept as a call of their own, which cuts the bank into as many splits as fill the chip once (sweep_plan): a
-        // third-size round instead of a whole one.  Queries are independent: the results are the same bits.  VSC_KNN_TAIL=0: one sweep.
-        // (Round 5, second step: from 257 blocks on -- 70 000 x 1M ran two rounds, 107 ms, for 1.07 rounds of work -- and decided by the
-        // plan's cost model instead of a fixed window of remainders.)
-        const int64_t nqb = (nq + SQ - 1) / SQ, rem = nqb % 256;
-        g_knn_set = 0;
-        bool split_tail = false;
-        if (!vsc_opt_is(OPT_KNN_TAIL, '0') && nqb > 256 && rem != 0) {
-            // by the plan's own cost model: whole rounds at one split + the tail's best plan + a second pack of the bank and the
-            // launches (~0.05 of a round), against the best plan for the call as a whole
-            const int dp = prefilter_dp(d);
-            SweepPlan whole, head_pl, tail_pl;
-            int rc;
-            if ((rc = sweep_plan(nq, nr, dp, &whole)) || (rc = sweep_plan((nqb - rem) * SQ, nr, dp, &head_pl)) ||
-                (rc = sweep_plan(nq - (nqb - rem) * SQ, nr, dp, &tail_pl))) return rc;
-            split_tail = head_pl.cost + tail_pl.cost + 0.05 < whole.cost;
-        }
-        if (split_tail) {
-            const int64_t head = (nqb - rem) * SQ;
-            int fb0 = 0, fb1 = 0;
-            int rc = knn_prefilter(q_dev, head, r_dev, nr, d, k, ref_id_offset, out_scores_dev, out_ids_dev, stream, &fb0, floor_dev);
-            if (rc) return rc;
-            g_knn_set = 1;
-            rc = knn_prefilter(q_dev + head * d, nq - head, r_dev, nr, d, k, ref_id_offset, out_scores_dev + head * k, out_ids_dev + head * k, stream, &fb1,
-                               floor_dev ? floor_dev + head : nullptr);
-            g_knn_set = 0;
-            g_knn_last_path = (fb0 || fb1) ? 3 : 2;
-            return rc;
-        }
-        int fb = 0;
-        const int rc = knn_prefilter(q_dev, nq, r_dev, nr, d, k, ref_id_offset, out_scores_dev, out_ids_dev, stream, &fb, floor_dev);
-        g_knn_last_path = fb ? 3 : 2;
-        return rc;
-    }
-    g_knn_last_path = 1;
-    return knn_exact(q_dev, nq, r_dev, nr, d, k, ref_id_offset, out_scores_dev, out_ids_dev, stream);
 }
 
 // one wave per (query, split) list: its hits (exact keys, ascending reference id, left by knn_rescore_kernel<.., 2>) -> CSR rows
@@ -1845,63 +1922,32 @@ static int range_prefilter(const float *q_dev, int64_t nq, const float *r_dev, i
                            int64_t ref_id_offset, int64_t *lims_dev, float *out_scores_dev, int64_t *out_ids_dev,
                            int64_t capacity, int64_t *total_out, hipStream_t stream, int *overflow) {
     constexpr int EPL = 32;
-    const int dp = prefilter_dp(d);
-    const int cap = 64 * EPL, keep = cap / 2;
-    SweepPlan pl;
-    int rc;
-    if ((rc = sweep_plan(nq, nr, dp, &pl))) return rc;
-    const int nqb = pl.nqb, splits = pl.splits, grid = pl.grid;
-    const int64_t total_tiles = pl.total_tiles, tiles_per_split = pl.tiles_per_split;
-    const int64_t nlists = nq * splits;
-    void *qb, *rb, *qstats, *flags, *lists, *cand, *ncand, *counts;
-    const size_t flag_bytes = 16 + (size_t)(1 + nqb) * 4 + 8 + 96;
-    if ((rc = scratch_get(12, (size_t)nq * dp * 2, &qb))) return rc;
-    if ((rc = scratch_get(13, (size_t)nr * dp * 2, &rb))) return rc;
-    if ((rc = scratch_get(14, (size_t)nq * 16, &qstats))) return rc;
-    if ((rc = scratch_get(15, flag_bytes, &flags))) return rc;
-    if ((rc = scratch_get(16, (size_t)grid * SQ * cap * 8, &lists))) return rc;
-    if ((rc = scratch_get(17, (size_t)nlists * keep * 8, &cand))) return rc;
-    if ((rc = scratch_get(18, (size_t)nlists * 4, &ncand))) return rc;
-    if ((rc = scratch_get(4, (size_t)nlists * 8, &counts))) return rc;
-    int *fb_dev = (int *)flags + 4;
-    VSC_CHECK_HIP(hipMemsetAsync(flags, 0, flag_bytes, stream));
-    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(nq * 64)), dim3(256), 0, stream, q_dev, (uint16_t *)qb,
-                       (float *)qstats, (unsigned *)nullptr, nq, d, dp);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(nr * 64)), dim3(256), 0, stream, r_dev, (uint16_t *)rb,
-                       (float *)nullptr, (unsigned *)flags, nr, d, dp);
-    VSC_CHECK_LAUNCH();
-    const float cd = (float)d * (2.384185791015625e-7f + 5.9604644775390625e-8f);
-    SweepArgs a{(const uint16_t *)qb, (const uint16_t *)rb, (const float *)qstats, (const unsigned *)flags, nq, nr, dp, /*k=*/cap, nqb,
-                splits, total_tiles, tiles_per_split, cd, (unsigned long long *)lists, (unsigned long long *)cand,
-                (int *)ncand, fb_dev, 0, nullptr, cap - 2 * SR};
-    a.thr_mode = 1;
-    a.xcd_map = pl.xcd_map;
-    a.thr0 = radius;
-    a.dbg = (unsigned long long *)(((uintptr_t)(fb_dev + 1 + nqb) + 7) & ~(uintptr_t)7);
-    if ((rc = launch_sweep<EPL>(a, grid, stream))) return rc;
-    const unsigned rgrid = (unsigned)((nlists + 3) / 4);
-    auto rk = knn_rescore_kernel<EPL / 2, 2>;
-    VSC_TRY(vsc_allow_dynamic_lds(rk, 4 * 2 * 64 * 36 * 4));
+    Prefilter pf;
+    long long *counts;
+    VSC_TRY(prefilter_plan(nq, nr, d, EPL, &pf));
+    VSC_TRY(scratch_get(SCRATCH_RANGE_COUNTS, (size_t)pf.nlists * 8, &counts));
+    VSC_TRY(prefilter_pack(pf, q_dev, r_dev, stream, /*mark=*/false));
+    pf.a.thr_mode = 1;
+    pf.a.thr0 = radius;
+    pf.a.k = pf.cap;
+    VSC_TRY(launch_sweep<EPL>(pf.a, pf.pl.grid, stream));
     PairMaxOut pm{};
     pm.thr = radius;
-    pm.counts = (long long *)counts;
-    hipLaunchKernelGGL(rk, dim3(rgrid), dim3(256), 4 * 2 * 64 * 36 * 4, stream, q_dev, r_dev, nlists, d, splits, cap,
-                       (const unsigned long long *)cand, (const int *)ncand, (unsigned long long *)nullptr, pm, 1);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(1024), 0, stream, (long long *)counts, nlists, splits, nq, lims_dev);
+    pm.counts = counts;
+    VSC_TRY((launch_rescore<EPL / 2, 2>(pf, q_dev, r_dev, pf.nlists, pf.pl.splits, pf.cap, nullptr, pm, 1, stream)));
+    hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, pf.nlists, pf.pl.splits, nq, lims_dev);
     VSC_CHECK_LAUNCH();
     int64_t total = 0;
     int fb0 = 0;
     VSC_CHECK_HIP(hipMemcpyAsync(&total, lims_dev + nq, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
-    VSC_CHECK_HIP(hipMemcpyAsync(&fb0, fb_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
+    VSC_CHECK_HIP(hipMemcpyAsync(&fb0, pf.fb_dev, sizeof(int), hipMemcpyDeviceToHost, stream));
     VSC_CHECK_HIP(hipStreamSynchronize(stream));
     *overflow = fb0 != 0;
     if (fb0) return VSC_OK;
     *total_out = total;
     if (total > capacity || total == 0) return VSC_OK;
-    hipLaunchKernelGGL(range_emit_kernel, dim3(rgrid), dim3(256), 0, stream, (const unsigned long long *)cand, (const int *)ncand,
-                       (const long long *)counts, nlists, keep, ref_id_offset, out_scores_dev, out_ids_dev);
+    hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)((pf.nlists + 3) / 4)), dim3(256), 0, stream, (const unsigned long long *)pf.a.cand,
+                       (const int *)pf.a.ncand, (const long long *)counts, pf.nlists, pf.keep, ref_id_offset, out_scores_dev, out_ids_dev);
     VSC_CHECK_LAUNCH();
     return VSC_OK;
 }
@@ -1919,47 +1965,24 @@ extern "C" int vsc_range_search_ip_f32(const float *q_dev, int64_t nq, const flo
     VSC_REQUIRE(d > 0 && d <= 4096, "range_search: dimension %d unsupported", d);
     VSC_REQUIRE(capacity >= 0 && (capacity == 0 || (out_scores_dev && out_ids_dev)),
                 "range_search: capacity %lld without output buffers", (long long)capacity);
-    int rc;
-    {   // path: as vsc_knn_ip_f32 (VSC_RANGE_PATH=exact|bf16 forces one)
-        bool prefilter = nr >= 4096 && nq * nr >= (1ll << 24);
-        if (const char *e = vsc_opt(OPT_RANGE_PATH)) prefilter = e[0] == 'b' ? true : (e[0] == 'e' ? false : prefilter);
-        g_range_last_path = 1;
-        if (prefilter) {
-            int overflow = 0;
-            if ((rc = range_prefilter(q_dev, nq, r_dev, nr, d, radius, ref_id_offset, lims_dev, out_scores_dev, out_ids_dev, capacity,
-                                      total_out, stream, &overflow))) return rc;
-            g_range_last_path = overflow ? 3 : 2;
-            if (!overflow) return VSC_OK;
-        }
+    g_range_last_path = 1;
+    if (use_prefilter(OPT_RANGE_PATH, prefilter_pays(nq, nr))) {   // path: as vsc_knn_ip_f32
+        int overflow = 0;
+        VSC_TRY(range_prefilter(q_dev, nq, r_dev, nr, d, radius, ref_id_offset, lims_dev, out_scores_dev, out_ids_dev, capacity,
+                                total_out, stream, &overflow));
+        g_range_last_path = overflow ? 3 : 2;
+        if (!overflow) return VSC_OK;
     }
-    const int dpad = (d + KS - 1) / KS * KS;
-    const int nqb = (int)((nq + TQ - 1) / TQ);
-    const int64_t total_tiles = (nr + TR - 1) / TR;
-    int64_t want = (512 + nqb - 1) / nqb;
-    if (want > 256) want = 256;
-    if (want > total_tiles) want = total_tiles;
-    if (want < 1) want = 1;
-    const int64_t tiles_per_split = (total_tiles + want - 1) / want;
-    const int splits = (int)((total_tiles + tiles_per_split - 1) / tiles_per_split);
-    const int64_t work = (int64_t)nqb * splits;
-    const int grid = (int)(work < 512 ? work : 512);
-
-    void *qp, *rp, *counts;
-    if ((rc = scratch_get(0, (size_t)nq * dpad * 4, &qp))) return rc;
-    if ((rc = scratch_get(1, (size_t)nr * dpad * 4, &rp))) return rc;
-    if ((rc = scratch_get(4, (size_t)nq * splits * 8, &counts))) return rc;
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nq * (dpad / 4))), dim3(256), 0, stream, q_dev,
-                       (float *)qp, nq, d, dpad);
+    ExactSweep x;
+    long long *counts;
+    VSC_TRY(exact_sweep_plan(nq, nr, d, &x));
+    VSC_TRY(scratch_get(SCRATCH_RANGE_COUNTS, (size_t)nq * x.splits * 8, &counts));
+    VSC_TRY(exact_sweep_pack(x, q_dev, r_dev, stream));
+    RangeArgs a{x.qp, x.rp, nq, nr, x.dpad, x.nqb, x.splits, x.total_tiles,
+                x.tiles_per_split, radius, counts, out_scores_dev, out_ids_dev, ref_id_offset};
+    hipLaunchKernelGGL(range_kernel<false>, dim3(x.grid), dim3(256), 0, stream, a);
     VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nr * (dpad / 4))), dim3(256), 0, stream, r_dev,
-                       (float *)rp, nr, d, dpad);
-    VSC_CHECK_LAUNCH();
-    RangeArgs a{(const float *)qp, (const float *)rp, nq, nr, dpad, nqb, splits, total_tiles,
-                tiles_per_split, radius, (long long *)counts, out_scores_dev, out_ids_dev, ref_id_offset};
-    hipLaunchKernelGGL(range_kernel<false>, dim3(grid), dim3(256), 0, stream, a);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(1024), 0, stream, (long long *)counts,
-                       (int64_t)nq * splits, splits, nq, lims_dev);
+    hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, (int64_t)nq * x.splits, x.splits, nq, lims_dev);
     VSC_CHECK_LAUNCH();
     int64_t total = 0;
     VSC_CHECK_HIP(hipMemcpyAsync(&total, lims_dev + nq, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
@@ -1967,7 +1990,7 @@ extern "C" int vsc_range_search_ip_f32(const float *q_dev, int64_t nq, const flo
     *total_out = total;
     if (total > capacity) return VSC_OK;  // caller re-calls with capacity >= total
     if (total > 0) {
-        hipLaunchKernelGGL(range_kernel<true>, dim3(grid), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(range_kernel<true>, dim3(x.grid), dim3(256), 0, stream, a);
         VSC_CHECK_LAUNCH();
     }
     return VSC_OK;
@@ -1981,7 +2004,6 @@ extern "C" int vsc_pair_similarity_f32(const float *q_dev, int64_t nq, const flo
     VSC_REQUIRE(nq > 0 && nr > 0 && n_pairs >= 0, "pair_similarity: empty bank (nq=%lld nr=%lld)", (long long)nq,
                 (long long)nr);
     VSC_REQUIRE(d > 0 && d <= 4096, "pair_similarity: dimension %d unsupported", d);
-    const int dpad = (d + KS - 1) / KS * KS;
     // tile table
     static thread_local std::vector<PairTile> tiles;
     tiles.clear();
@@ -2003,21 +2025,15 @@ extern "C" int vsc_pair_similarity_f32(const float *q_dev, int64_t nq, const flo
     VSC_REQUIRE(out_dev && capacity >= total, "pair_similarity: output holds %lld floats, %lld needed", (long long)capacity,
                 (long long)total);
     VSC_REQUIRE(tiles.size() < (1ull << 31), "pair_similarity: too many tiles");
-    void *qp, *rp, *tt;
-    int rc;
-    if ((rc = scratch_get(0, (size_t)nq * dpad * 4, &qp))) return rc;
-    if ((rc = scratch_get(1, (size_t)nr * dpad * 4, &rp))) return rc;
-    if ((rc = scratch_get(5, tiles.size() * sizeof(PairTile), &tt))) return rc;
+    ExactSweep x;   // for its packed banks: the tiles of the pair table are the work items here
+    PairTile *tt;
+    VSC_TRY(exact_sweep_plan(nq, nr, d, &x));
+    VSC_TRY(scratch_get(SCRATCH_PAIR_TILES, tiles.size() * sizeof(PairTile), &tt));
     VSC_CHECK_HIP(hipMemcpyAsync(tt, tiles.data(), tiles.size() * sizeof(PairTile), hipMemcpyHostToDevice, stream));
     VSC_CHECK_HIP(hipStreamSynchronize(stream));  // `tiles` is reused by the next call
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nq * (dpad / 4))), dim3(256), 0, stream, q_dev, (float *)qp, nq,
-                       d, dpad);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nr * (dpad / 4))), dim3(256), 0, stream, r_dev, (float *)rp, nr,
-                       d, dpad);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(pair_sim_kernel, dim3((unsigned)tiles.size()), dim3(256), 0, stream, (const float *)qp,
-                       (const float *)rp, dpad, (const PairTile *)tt, out_dev);
+    VSC_TRY(exact_sweep_pack(x, q_dev, r_dev, stream));
+    hipLaunchKernelGGL(pair_sim_kernel, dim3((unsigned)tiles.size()), dim3(256), 0, stream, (const float *)x.qp,
+                       (const float *)x.rp, x.dpad, (const PairTile *)tt, out_dev);
     VSC_CHECK_LAUNCH();
     return VSC_OK;
 }
@@ -2025,30 +2041,12 @@ extern "C" int vsc_pair_similarity_f32(const float *q_dev, int64_t nq, const flo
 // The exact fp32 sweep of the pair table: queries [q_dev, q_dev + nq) (video ids qvid), all references.
 static int pair_max_exact(const float *q_dev, int64_t nq, const int32_t *qvid, const float *r_dev, int64_t nr, const int32_t *rvid,
                           int32_t n_r_videos, int32_t d, float threshold, unsigned *table, hipStream_t stream) {
-    const int dpad = (d + KS - 1) / KS * KS;
-    const int nqb = (int)((nq + TQ - 1) / TQ);
-    const int64_t total_tiles = (nr + TR - 1) / TR;
-    int64_t want = (512 + nqb - 1) / nqb;
-    if (want > 256) want = 256;
-    if (want > total_tiles) want = total_tiles;
-    if (want < 1) want = 1;
-    const int64_t tiles_per_split = (total_tiles + want - 1) / want;
-    const int splits = (int)((total_tiles + tiles_per_split - 1) / tiles_per_split);
-    const int64_t work = (int64_t)nqb * splits;
-    const int grid = (int)(work < 512 ? work : 512);
-    void *qp, *rp;
-    int rc;
-    if ((rc = scratch_get(0, (size_t)nq * dpad * 4, &qp))) return rc;
-    if ((rc = scratch_get(1, (size_t)nr * dpad * 4, &rp))) return rc;
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nq * (dpad / 4))), dim3(256), 0, stream, q_dev, (float *)qp, nq,
-                       d, dpad);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_pack_kernel, dim3(blocks_for(nr * (dpad / 4))), dim3(256), 0, stream, r_dev, (float *)rp, nr,
-                       d, dpad);
-    VSC_CHECK_LAUNCH();
-    PairMaxArgs a{(const float *)qp, (const float *)rp, qvid, rvid, nq, nr, dpad, nqb, splits,
-                  total_tiles, tiles_per_split, threshold, table, n_r_videos};
-    hipLaunchKernelGGL(pair_max_kernel, dim3(grid), dim3(256), 0, stream, a);
+    ExactSweep x;
+    VSC_TRY(exact_sweep_plan(nq, nr, d, &x));
+    VSC_TRY(exact_sweep_pack(x, q_dev, r_dev, stream));
+    PairMaxArgs a{x.qp, x.rp, qvid, rvid, nq, nr, x.dpad, x.nqb, x.splits,
+                  x.total_tiles, x.tiles_per_split, threshold, table, n_r_videos};
+    hipLaunchKernelGGL(pair_max_kernel, dim3(x.grid), dim3(256), 0, stream, a);
     VSC_CHECK_LAUNCH();
     return VSC_OK;
 }
@@ -2062,62 +2060,19 @@ static int pair_max_prefilter(const float *q_dev, int64_t nq, const int32_t *qvi
                               const int32_t *rvid, int32_t n_r_videos, int32_t d, float threshold, unsigned *table,
                               hipStream_t stream, int *fell_back) {
     constexpr int EPL = 32;
-    const int dp = prefilter_dp(d);
-    const int cap = 64 * EPL, keep = cap / 2;
-    SweepPlan pl;
-    int rc;
-    if ((rc = sweep_plan(nq, nr, dp, &pl))) return rc;
-    const int nqb = pl.nqb, splits = pl.splits, grid = pl.grid;
-    const int64_t total_tiles = pl.total_tiles, tiles_per_split = pl.tiles_per_split;
-    const int64_t nlists = nq * splits;
-    void *qb, *rb, *qstats, *flags, *lists, *cand, *ncand;
-    const size_t flag_bytes = 16 + (size_t)(1 + nqb) * 4 + 8 + 96;
-    if ((rc = scratch_get(12, (size_t)nq * dp * 2, &qb))) return rc;
-    if ((rc = scratch_get(13, (size_t)nr * dp * 2, &rb))) return rc;
-    if ((rc = scratch_get(14, (size_t)nq * 16, &qstats))) return rc;
-    if ((rc = scratch_get(15, flag_bytes, &flags))) return rc;
-    if ((rc = scratch_get(16, (size_t)grid * SQ * cap * 8, &lists))) return rc;
-    if ((rc = scratch_get(17, (size_t)nlists * keep * 8, &cand))) return rc;
-    if ((rc = scratch_get(18, (size_t)nlists * 4, &ncand))) return rc;
-    int *fb_dev = (int *)flags + 4;
-    VSC_CHECK_HIP(hipMemsetAsync(flags, 0, flag_bytes, stream));
-    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(nq * 64)), dim3(256), 0, stream, q_dev, (uint16_t *)qb,
-                       (float *)qstats, (unsigned *)nullptr, nq, d, dp);
-    VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(knn_pack_bf16_kernel, dim3(blocks_for(nr * 64)), dim3(256), 0, stream, r_dev, (uint16_t *)rb,
-                       (float *)nullptr, (unsigned *)flags, nr, d, dp);
-    VSC_CHECK_LAUNCH();
-    const float cd = (float)d * (2.384185791015625e-7f + 5.9604644775390625e-8f);
-    SweepArgs a{(const uint16_t *)qb, (const uint16_t *)rb, (const float *)qstats, (const unsigned *)flags, nq, nr, dp, /*k=*/cap, nqb,
-                splits, total_tiles, tiles_per_split, cd, (unsigned long long *)lists, (unsigned long long *)cand,
-                (int *)ncand, fb_dev, 0, nullptr, cap - 2 * SR};
-    a.thr_mode = 1;
-    a.xcd_map = pl.xcd_map;
-    a.thr0 = threshold;
-    a.dbg = (unsigned long long *)(((uintptr_t)(fb_dev + 1 + nqb) + 7) & ~(uintptr_t)7);
-    if ((rc = launch_sweep<EPL>(a, grid, stream))) return rc;
-    const unsigned rgrid = (unsigned)((nlists + 3) / 4);
-    auto rk = knn_rescore_kernel<EPL / 2, 1>;
-    VSC_TRY(vsc_allow_dynamic_lds(rk, 4 * 2 * 64 * 36 * 4));
-    hipLaunchKernelGGL(rk, dim3(rgrid), dim3(256), 4 * 2 * 64 * 36 * 4, stream, q_dev, r_dev, nlists, d, splits, cap,
-                       (const unsigned long long *)cand, (const int *)ncand, (unsigned long long *)nullptr,
-                       PairMaxOut{qvid, rvid, table, (int64_t)n_r_videos, threshold}, 1);
-    VSC_CHECK_LAUNCH();
-    std::vector<int> fb(1 + nqb);
-    VSC_CHECK_HIP(hipMemcpyAsync(fb.data(), fb_dev, fb.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
-    VSC_CHECK_HIP(hipStreamSynchronize(stream));
-    *fell_back = 0;
-    if (!fb[0]) return VSC_OK;
-    for (int b = 0; b < nqb;) {   // flagged query blocks (overfull lists, non-finite bound): the exact sweep decides
-        if (!fb[1 + b]) { ++b; continue; }
-        int e = b;
-        while (e < nqb && fb[1 + e]) ++e;
-        const int64_t row0 = (int64_t)b * SQ, rows = ((int64_t)e * SQ < nq ? (int64_t)e * SQ : nq) - row0;
-        if ((rc = pair_max_exact(q_dev + row0 * d, rows, qvid + row0, r_dev, nr, rvid, n_r_videos, d, threshold, table, stream))) return rc;
-        *fell_back += e - b;
-        b = e;
-    }
-    return VSC_OK;
+    Prefilter pf;
+    VSC_TRY(prefilter_plan(nq, nr, d, EPL, &pf));
+    VSC_TRY(prefilter_pack(pf, q_dev, r_dev, stream, /*mark=*/false));
+    pf.a.thr_mode = 1;
+    pf.a.thr0 = threshold;
+    pf.a.k = pf.cap;
+    VSC_TRY(launch_sweep<EPL>(pf.a, pf.pl.grid, stream));
+    VSC_TRY((launch_rescore<EPL / 2, 1>(pf, q_dev, r_dev, pf.nlists, pf.pl.splits, pf.cap, nullptr,
+                                        PairMaxOut{qvid, rvid, table, (int64_t)n_r_videos, threshold}, 1, stream)));
+    // flagged query blocks (overfull lists, non-finite bound): the exact sweep decides
+    return redo_flagged_runs(pf, stream, fell_back, [&](int64_t row0, int64_t rows) {
+        return pair_max_exact(q_dev + row0 * d, rows, qvid + row0, r_dev, nr, rvid, n_r_videos, d, threshold, table, stream);
+    });
 }
 
 static int g_pair_max_last_path = 0;   // 1 exact, 2 pre-filter, 3 pre-filter with blocks redone
@@ -2135,29 +2090,25 @@ extern "C" int vsc_video_pair_max_f32(const float *q_dev, int64_t nq, const int3
     VSC_REQUIRE(capacity >= 0 && (capacity == 0 || (out_rvideo_dev && out_score_dev)),
                 "video_pair_max: capacity %lld without output buffers", (long long)capacity);
     const size_t table_bytes = (size_t)n_q_videos * n_r_videos * 4;
-    void *table, *counts;
-    int rc;
-    if ((rc = scratch_get(6, table_bytes, &table))) return rc;
-    if ((rc = scratch_get(7, (size_t)n_q_videos * 8, &counts))) return rc;
+    unsigned *table;
+    long long *counts;
+    VSC_TRY(scratch_get(SCRATCH_PAIRMAX_TABLE, table_bytes, &table));
+    VSC_TRY(scratch_get(SCRATCH_PAIRMAX_COUNTS, (size_t)n_q_videos * 8, &counts));
     VSC_CHECK_HIP(hipMemsetAsync(table, 0, table_bytes, stream));
-    // path: as vsc_knn_ip_f32 -- the pre-filter pays from ~16 M pairs and a few thousand references on
-    bool prefilter = nr >= 4096 && nq * nr >= (1ll << 24);
-    if (const char *e = vsc_opt(OPT_PAIRMAX_PATH)) prefilter = e[0] == 'b' ? true : (e[0] == 'e' ? false : prefilter);
-    if (prefilter) {
+    if (use_prefilter(OPT_PAIRMAX_PATH, prefilter_pays(nq, nr))) {   // path: as vsc_knn_ip_f32
         int fb = 0;
-        if ((rc = pair_max_prefilter(q_dev, nq, q_video_dev, r_dev, nr, r_video_dev, n_r_videos, d, threshold, (unsigned *)table,
-                                     stream, &fb))) return rc;
+        VSC_TRY(pair_max_prefilter(q_dev, nq, q_video_dev, r_dev, nr, r_video_dev, n_r_videos, d, threshold, table,
+                                   stream, &fb));
         g_pair_max_last_path = fb ? 3 : 2;
     } else {
-        if ((rc = pair_max_exact(q_dev, nq, q_video_dev, r_dev, nr, r_video_dev, n_r_videos, d, threshold, (unsigned *)table, stream)))
-            return rc;
+        VSC_TRY(pair_max_exact(q_dev, nq, q_video_dev, r_dev, nr, r_video_dev, n_r_videos, d, threshold, table, stream));
         g_pair_max_last_path = 1;
     }
     const int rows_grid = n_q_videos < 4096 ? n_q_videos : 4096;
     hipLaunchKernelGGL(pair_max_count_kernel, dim3(rows_grid), dim3(256), 0, stream, (const unsigned *)table,
-                       (int64_t)n_q_videos, (int64_t)n_r_videos, (long long *)counts);
+                       (int64_t)n_q_videos, (int64_t)n_r_videos, counts);
     VSC_CHECK_LAUNCH();
-    hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(1024), 0, stream, (long long *)counts, (int64_t)n_q_videos, 1,
+    hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, (int64_t)n_q_videos, 1,
                        (int64_t)n_q_videos, lims_dev);
     VSC_CHECK_LAUNCH();
     int64_t total = 0;
