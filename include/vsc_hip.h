@@ -444,6 +444,17 @@ int vsc_gemm_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *bia
                   const float *aux_dev, void *out_dev, int64_t m, int32_t n, int32_t k,
                   int32_t epilogue, int32_t tokens, void *stream);
 
+/* x_inout[M,N] += A[M,K] . W[N,K]^T + bias[N] (float32), y_out[M,N] = LayerNorm_row(x_inout) * gamma + beta in the operand type:
+ * the residual GEMM of a transformer block and the LayerNorm behind it.  Where the persistent 256 x 256 kernel has that form
+ * (N = 768, whole row blocks per XCD: ceil(M / 256) % 8 == 0, more tiles than CUs) AND the switch VSC_GEMM_LN_TAIL is 1, this
+ * is ONE launch whose workgroups normalise every finished 256-row block as a tail; otherwise vsc_gemm_bf16(RESADD) followed by
+ * vsc_layernorm_f32.  The same bits either way.  Launches on one stream share a workspace kept by the library. */
+int vsc_gemm_resadd_ln_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *bias_dev, float *x_inout_dev,
+                            const float *gamma_dev, const float *beta_dev, uint16_t *y_out_dev, int64_t m, int32_t n, int32_t k,
+                            float eps, void *stream);
+/* which form the last vsc_gemm_resadd_ln_bf16 / encoder residual GEMM took: 1 one launch with the LayerNorm tail, 2 two launches */
+int vsc_gemm_resadd_ln_last_path(void);
+
 /* qkv_dev bf16 [frames*tokens, 3*width] (q | k | v column blocks, head-major inside
  * each) -> out_dev bf16 [frames*tokens, width]; softmax(q k^T / 8) v per head;
  * head_dim 64. */

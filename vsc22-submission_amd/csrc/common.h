@@ -50,7 +50,7 @@ void vsc_set_error(const char *fmt, ...);
     X(ATTN_SKEW) X(ATTN_ABL) X(ATTN_NI) X(ATTN_DMA) X(CONV_IMPLICIT) X(CONV_DIRECT) X(CONV_REMAP) X(CONV_PERSIST) X(CONV_STAGES) X(CONV_WAVES) X(CONV_NARROW_MAX) X(CONV_NARROW_NT) X(CONV_EXPAND) X(DWCONV_SMALL) X(CONV_STEM) X(CONV_STREAM_MIN_COUT) X(CONV_X3)      \
     X(GEMM_GROUP_N) X(GEMM_V4_SKEW) X(GEMM_TIMING_PRINT) X(GEMM_V4) X(GEMM_V4_GRID) X(GEMM_SKEW_NS_PER_K) X(GEMM_CFG)    \
     X(GEMM_V3) X(GEMM_ABL) X(GEMM_V1) X(KNN_TRIG) X(KNN_ABL) X(KNN_PATH) X(KNN_XCD_MAP) X(KNN_DELTA) X(KNN_TAIL) X(RANGE_PATH) X(PAIRMAX_PATH) X(WATTN_ABL)      \
-    X(SWIN_SPLIT_LN) X(SWIN_SPLIT_K) X(GEMM_LN_V4) X(SWIN_FUSED_MLP) X(SWIN_MLP512) X(SWIN_PROJ512) X(SWIN_QKV512) X(SWIN_MLP512_GRID) X(SWIN_FUSED_PROJ) X(SWIN_MLP_ABL) X(SWIN_MLP_SEQ) X(SWIN_MLP_NW4) X(SWIN_FUSED_MERGE) X(SWIN_ROW_MAX) X(LN_LIGHT) X(WATTN_STREAM)
+    X(SWIN_SPLIT_LN) X(SWIN_SPLIT_K) X(GEMM_LN_V4) X(SWIN_FUSED_MLP) X(SWIN_MLP512) X(SWIN_PROJ512) X(SWIN_QKV512) X(SWIN_MLP512_GRID) X(SWIN_FUSED_PROJ) X(SWIN_MLP_ABL) X(SWIN_MLP_SEQ) X(SWIN_MLP_NW4) X(SWIN_FUSED_MERGE) X(SWIN_ROW_MAX) X(LN_LIGHT) X(WATTN_STREAM) X(GEMM_LN_TAIL)
 enum VscOpt {
 #define X(n) OPT_##n,
     VSC_OPT_LIST(X)
@@ -218,7 +218,10 @@ bool gemm_ln_supported(int n, int k);
 //   LN_RES_F32       Swin-V2's res-post-norm update on the persistent kernel: out = (aux ? aux : 0) + LayerNorm(acc + bias) * gamma + beta
 //                    over the whole row (N = 256: one tile; N = 512: the two workgroups holding a row's two tiles exchange their
 //                    (mean, M2) through L2), plus xb = bf16(out)
-enum { VSC_EPI_LNF_BF16 = 6, VSC_EPI_LNF_GELU_BF16 = 7, VSC_EPI_LNF_QGELU_BF16 = 8, VSC_EPI_RESADD_STATS_F32 = 9, VSC_EPI_LN_RES_F32 = 10 };
+//   RESADD_LN_F32    RESADD_F32 on the persistent kernel (N = 768) whose launch also writes ln_out = bf16(LayerNorm(out) * gamma + beta):
+//                    the workgroups run the LayerNorm of every finished 256-row block as a tail (launch_gemm_resadd_ln_bf16)
+enum { VSC_EPI_LNF_BF16 = 6, VSC_EPI_LNF_GELU_BF16 = 7, VSC_EPI_LNF_QGELU_BF16 = 8, VSC_EPI_RESADD_STATS_F32 = 9, VSC_EPI_LN_RES_F32 = 10,
+       VSC_EPI_RESADD_LN_F32 = 11 };
 struct GemmExtra {
     uint16_t *xb = nullptr;          // RESADD_STATS: bf16 copy of out [m, n]
     float *stats = nullptr;          // RESADD_STATS: [n / 64][m][2]
@@ -231,6 +234,8 @@ struct GemmExtra {
     float *xch = nullptr;            // LN_RES, N = 512: [2][256 workgroups][256 rows][2] partial row statistics
     int *xflags = nullptr;           // LN_RES, N = 512: [256 workgroups][2] tiles published, counting up across launches from `epoch`
     int epoch = 0;
+    uint16_t *ln_out = nullptr;      // RESADD_LN: [m, n] LayerNorm of out in the operand type (uses gamma, beta, eps)
+    unsigned *tail_ws = nullptr;     // RESADD_LN: gemm_ln_tail_ws_bytes(m) of zeroed device memory, private to the stream
 };
 // bytes of the pair-exchange workspace of launch_gemm_ln_bf16 (one per stream that may run it).
 // Contract: the workspace's flag words count up from launch to launch; the count ("epoch") is kept by the launcher in a host map keyed
@@ -241,6 +246,14 @@ constexpr size_t VSC_GEMM_LN_WS_BYTES = 2 * 256 * 256 * 2 * 4 + 256 * 2 * 4;
 void gemm_ln_workspace_forget(const void *ws);   // call before freeing a workspace that was passed to launch_gemm_ln_bf16
 int launch_gemm_bf16_ex(const uint16_t *a, const uint16_t *w, const float *bias, const float *aux, void *out, int64_t m,
                         int n, int k, int epilogue, int tokens, const GemmExtra &ex, hipStream_t stream);
+// x += a . w^T + bias, y = LayerNorm(x) * gamma + beta in the operand type.  One launch of the persistent kernel with the LayerNorm
+// as its tail where that form exists (gemm_resadd_ln_tail_eligible), otherwise launch_gemm_bf16(RESADD_F32) + launch_layernorm: the
+// same bits either way.  tail_ws: gemm_ln_tail_ws_bytes(m) bytes, zeroed ONCE by the owner (every launch leaves them zero again), used
+// by one stream at a time; nullptr forces the two launches.
+int launch_gemm_resadd_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias, float *x, const float *gamma, const float *beta,
+                               uint16_t *y, int64_t m, int n, int k, float eps, unsigned *tail_ws, hipStream_t stream);
+bool gemm_resadd_ln_tail_eligible(int64_t m, int n, int k);   // (on the current device, with the switches as they stand)
+size_t gemm_ln_tail_ws_bytes(int64_t m);
 int launch_ln_stats_merge(const float *stats, float *rowstats, int64_t rows, int slices, int width, float eps,
                           hipStream_t stream);
 int launch_attention_bf16(const uint16_t *qkv, uint16_t *out, int frames, int tokens, int heads,

@@ -39,6 +39,10 @@ struct vsc_encoder : ModelHost {
         float *x = nullptr, *pooled = nullptr;
         float *stats = nullptr, *rowstats = nullptr;  // LayerNorm folding: [D/64][M][2] slice partials, [M][2] (mean, rstd)
         uint16_t *xb = nullptr;                       //                    bf16(x) [M, D]
+        // LayerNorm as the tail of the residual GEMMs (gemm_bf16.hip, RESADD_LN): proj's A operand is y, so its tail writes LN2 to a
+        // buffer of its own; the counters / claim words of the lane's launches (zeroed here once, zero again behind every launch)
+        uint16_t *yln = nullptr;
+        unsigned *tail_ws = nullptr;
     } ws[2];
     int lanes = 1;
     int64_t ws_bytes = 0;
@@ -212,6 +216,8 @@ extern "C" int vsc_encoder_finalize(vsc_encoder *e) {
                  sz_pool = B * (size_t)(c.head_conv_dim ? c.head_conv_dim : D) * 4;
     VSC_REQUIRE(c.head_conv_dim <= c.mlp_dim, "encoder: head_conv_dim %d > mlp_dim %d", c.head_conv_dim, c.mlp_dim);
     e->lanes = c.lanes == 2 ? 2 : 1;
+    // the LayerNorm-tail form of the residual GEMMs (opt-in): its buffers exist when the switch is on HERE; after that it is read per launch
+    const bool ln_tail = c.fuse_ln <= 0 && vsc_opt_is(OPT_GEMM_LN_TAIL, '1');
     for (int l = 0; l < e->lanes; ++l) {
         vsc_encoder::Workspace &w = e->ws[l];
         VSC_TRY(e->alloc(sz_patches, (void **)&w.patches));
@@ -225,10 +231,15 @@ extern "C" int vsc_encoder_finalize(vsc_encoder *e) {
             VSC_TRY(e->alloc(M * 2 * 4, (void **)&w.rowstats));
             VSC_TRY(e->alloc(sz_y, (void **)&w.xb));
         }
+        if (ln_tail) {
+            VSC_TRY(e->alloc(sz_y, (void **)&w.yln));
+            VSC_TRY(e->alloc(gemm_ln_tail_ws_bytes((int64_t)M), (void **)&w.tail_ws));
+            VSC_CHECK_HIP(hipMemset(w.tail_ws, 0, gemm_ln_tail_ws_bytes((int64_t)M)));
+        }
         w.hconv_out = w.h;  // [M, head_conv_dim] bf16 fits in the (idle) MLP buffer: head_conv_dim <= mlp_dim
     }
     if (e->lanes == 2) VSC_TRY(e->make_lanes());
-    e->ws_bytes = (int64_t)(sz_patches + sz_x + sz_y + sz_qkv + sz_h + sz_pool + (c.fuse_ln > 0 ? sz_y + ((size_t)(D / 64) + 1) * M * 8 : 0)) * e->lanes;
+    e->ws_bytes = (int64_t)(sz_patches + sz_x + sz_y + sz_qkv + sz_h + sz_pool + (c.fuse_ln > 0 ? sz_y + ((size_t)(D / 64) + 1) * M * 8 : ln_tail ? sz_y + gemm_ln_tail_ws_bytes((int64_t)M) : 0)) * e->lanes;
     e->drop_host();
     return VSC_OK;
 }
@@ -268,8 +279,13 @@ static int encoder_run_chunks(vsc_encoder *e, const float *frames, const uint8_t
         // LayerNorm folding (opt-in): from the first residual GEMM on, bf16(x) and x's row statistics
         // come out of the proj / fc2 write-out (into w.xb / w.stats) and LN2 / the next layer's LN1 are applied inside
         // the fc1 / qkv epilogues -- no LN pass.  Layer 0's LN1 stays (x comes from the patch / cls kernels).
-        // Measured on the power-limited MI355X it is throughput-neutral (18.8 k frames/s either way: the 48 removed
-        // LayerNorm launches come back as ~25 us on each GEMM), so the separate passes remain the default.
+        // Measured on the power-limited MI355X it costs +14 ... +23 us on each of the four GEMMs for the LayerNorm launches it
+        // removes: neutral to +1.1 % on two lanes, and it changes bits -- so it stays opt-in.
+        //
+        // A second opt-in (VSC_GEMM_LN_TAIL=1 from finalize on) runs LN2 / the next layer's LN1 as a TAIL of the proj /
+        // fc2 launch wherever the persistent kernel has that form (gemm_resadd_ln_tail_eligible): same arithmetic, same bits, no
+        // launch -- and, as measured, no gain either.  y_ready: the previous fc2 launch has already written this layer's LN1
+        // output to w.y.
         const bool fold = c.fuse_ln > 0;
         const int act_lnf = c.act == 0 ? VSC_EPI_LNF_GELU_BF16 : VSC_EPI_LNF_QGELU_BF16;
         GemmExtra emit, take;
@@ -279,6 +295,9 @@ static int encoder_run_chunks(vsc_encoder *e, const float *frames, const uint8_t
         take.slices = w.stats;
         take.nslices = D / 64;
         take.eps = c.ln_eps;
+        const bool tail_proj = !fold && w.yln && gemm_resadd_ln_tail_eligible(M, D, D);
+        const bool tail_fc2 = !fold && w.yln && gemm_resadd_ln_tail_eligible(M, D, c.mlp_dim);
+        bool y_ready = false;
         for (int l = 0; l < c.layers; ++l) {
             const LayerW &L = e->layers[l];
             if (fold && l > 0) {
@@ -286,7 +305,7 @@ static int encoder_run_chunks(vsc_encoder *e, const float *frames, const uint8_t
                 ProfScope _ps(e, VSC_PROF_GEMM_QKV, st);
                 VSC_TRY(launch_gemm_bf16_ex(w.xb, L.qkv_wf, L.qkv_bf, nullptr, w.qkv, M, 3 * D, D, VSC_EPI_LNF_BF16, 0, take, st));
             } else {
-                { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); VSC_TRY(launch_layernorm(w.x, L.ln1_g, L.ln1_b, w.y, M, D, c.ln_eps, 0, st)); }
+                if (!y_ready) { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); VSC_TRY(launch_layernorm(w.x, L.ln1_g, L.ln1_b, w.y, M, D, c.ln_eps, 0, st)); }
                 { ProfScope _ps(e, VSC_PROF_GEMM_QKV, st); VSC_TRY(launch_gemm_bf16(w.y, L.qkv_w, L.qkv_b, nullptr, w.qkv, M, 3 * D, D, VSC_EPI_BF16, 0, st)); }
             }
             { ProfScope _ps(e, VSC_PROF_ATTENTION, st); VSC_TRY(launch_attention_bf16(w.qkv, w.y, (int)B, T, c.heads, st)); }
@@ -296,10 +315,25 @@ static int encoder_run_chunks(vsc_encoder *e, const float *frames, const uint8_t
                 { ProfScope _ps(e, VSC_PROF_GEMM_FC1, st); VSC_TRY(launch_gemm_bf16_ex(w.xb, L.fc1_wf, L.fc1_bf, nullptr, w.h, M, c.mlp_dim, D, act_lnf, 0, take, st)); }
                 { ProfScope _ps(e, VSC_PROF_GEMM_FC2, st); VSC_TRY(launch_gemm_bf16_ex(w.h, L.fc2_w, L.fc2_b, w.x, w.x, M, D, c.mlp_dim, l + 1 < c.layers ? VSC_EPI_RESADD_STATS_F32 : VSC_EPI_RESADD_F32, 0, emit, st)); }
             } else {
-                { ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st); VSC_TRY(launch_gemm_bf16(w.y, L.proj_w, L.proj_b, w.x, w.x, M, D, D, VSC_EPI_RESADD_F32, 0, st)); }
-                { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); VSC_TRY(launch_layernorm(w.x, L.ln2_g, L.ln2_b, w.y, M, D, c.ln_eps, 0, st)); }
-                { ProfScope _ps(e, VSC_PROF_GEMM_FC1, st); VSC_TRY(launch_gemm_bf16(w.y, L.fc1_w, L.fc1_b, nullptr, w.h, M, c.mlp_dim, D, act_epi, 0, st)); }
-                { ProfScope _ps(e, VSC_PROF_GEMM_FC2, st); VSC_TRY(launch_gemm_bf16(w.h, L.fc2_w, L.fc2_b, w.x, w.x, M, D, c.mlp_dim, VSC_EPI_RESADD_F32, 0, st)); }
+                const uint16_t *ln2 = w.y;
+                if (tail_proj) {
+                    ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st);
+                    VSC_TRY(launch_gemm_resadd_ln_bf16(w.y, L.proj_w, L.proj_b, w.x, L.ln2_g, L.ln2_b, w.yln, M, D, D, c.ln_eps, w.tail_ws, st));
+                    ln2 = w.yln;
+                } else {
+                    { ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st); VSC_TRY(launch_gemm_bf16(w.y, L.proj_w, L.proj_b, w.x, w.x, M, D, D, VSC_EPI_RESADD_F32, 0, st)); }
+                    { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); VSC_TRY(launch_layernorm(w.x, L.ln2_g, L.ln2_b, w.y, M, D, c.ln_eps, 0, st)); }
+                }
+                { ProfScope _ps(e, VSC_PROF_GEMM_FC1, st); VSC_TRY(launch_gemm_bf16(ln2, L.fc1_w, L.fc1_b, nullptr, w.h, M, c.mlp_dim, D, act_epi, 0, st)); }
+                y_ready = tail_fc2 && l + 1 < c.layers;
+                if (y_ready) {   // the next layer's LN1 rides on this launch (the last layer keeps the plain epilogue: ln_post is the pooling kernel's)
+                    const LayerW &N = e->layers[l + 1];
+                    ProfScope _ps(e, VSC_PROF_GEMM_FC2, st);
+                    VSC_TRY(launch_gemm_resadd_ln_bf16(w.h, L.fc2_w, L.fc2_b, w.x, N.ln1_g, N.ln1_b, w.y, M, D, c.mlp_dim, c.ln_eps, w.tail_ws, st));
+                } else {
+                    ProfScope _ps(e, VSC_PROF_GEMM_FC2, st);
+                    VSC_TRY(launch_gemm_bf16(w.h, L.fc2_w, L.fc2_b, w.x, w.x, M, D, c.mlp_dim, VSC_EPI_RESADD_F32, 0, st));
+                }
             }
         }
         if (c.head_conv_dim) {

@@ -24,11 +24,14 @@
 
 #include <type_traits>
 
+#include <atomic>
+#include <map>
 #include <mutex>
 #include <unordered_map>
 
 #include "common.h"
 #include "gelu_poly.h"
+#include "ln_row.h"
 #include "mainloop64.h"
 
 namespace {
@@ -764,7 +767,7 @@ int launch_v3(GemmArgs p, hipStream_t stream) {
 // Serves the plain, GELU and residual epilogues; K % 128 == 0 (an even number of K-tiles), K >= 256.
 constexpr bool epi_v4(int e) {
     return e == VSC_EPI_BF16 || e == VSC_EPI_GELU_BF16 || e == VSC_EPI_QGELU_BF16 || e == VSC_EPI_RESADD_F32 || e == VSC_EPI_F32 ||
-           e == VSC_EPI_LN_RES_F32 || epi_lnf(e) || e == VSC_EPI_RESADD_STATS_F32;
+           e == VSC_EPI_LN_RES_F32 || epi_lnf(e) || e == VSC_EPI_RESADD_STATS_F32 || e == VSC_EPI_RESADD_LN_F32;
 }
 
 #ifdef VSC_GEMM_TIMING
@@ -1078,6 +1081,99 @@ __device__ __forceinline__ void epilogue_ln(const GemmArgs &p, f32x4_t (&acc)[8]
     }
 }
 
+// ---- RESADD_LN: the LayerNorm of a finished 256-row block as a tail of the persistent kernel -----------------------------------
+// N = NV x 256 is one N-group (group_n == tiles_n), so a row block's NV tiles are consecutive tile indices, and the launcher admits
+// only tile counts whose XCD ranges (xcd_remap) hold whole row blocks: every writer of a block and whoever normalises it sit on ONE
+// XCD and meet in its L2 -- the argument of epilogue_ln's pair exchange.  Writers wait for their residual stores (vmcnt(0)) before
+// they count themselves in; the tail reads x with sc1 loads (agent scope: never served from the CU's own L1, which may still
+// hold the block's OLD values from this workgroup's residual reads).  No fence, no write-back.
+//
+// Workspace (unsigned words, zero between launches): cnt[tiles_m], then pend[8][words] -- one bit per row block of an XCD.
+//   arrive  after a tile's write-out (stores waited for, tile-end barrier passed) one lane adds 1 to cnt[tm].  Whoever brings it to
+//           tiles_n is the block's last writer: it puts the counter back to 0 (nobody touches it again in this launch) and sets the
+//           block's bit in its XCD's pend words.
+//   claim   one lane scans the pend words and clears ONE set bit with fetch_and; the bit was its to clear if the returned word still
+//           had it.  A set bit is cleared by exactly one fetch_and that sees it set, so a block is normalised exactly once.
+//   policy  a workgroup claims at most one block per tile, between the K loop and the write-out of every tile but its first, and
+//           after its last tile it claims until a scan finds nothing.  The fixed point gives NEGATIVE feedback: the blocks of a
+//           round are pushed at its end and taken a K loop later by the workgroups that get there FIRST, which are thereby the
+//           late ones of the next round.  ("The last writer normalises" is the opposite: it is late, so last again, and collects
+//           a tail per tile.)  Nothing depends on rounds: 32 slots per XCD are no multiple of 3, trios straddle them.
+//   every pushed block is taken: its pusher scans the words again after the push -- at a later claim point, or in the drain behind
+//           its last tile (which follows that tile's own push) -- and a scan leaves a bit it has seen only when another
+//           workgroup's fetch_and took it.
+// Nobody ever waits for anybody: no polling, no sleep, no residency assumption; every loop is bounded by the number of blocks.
+// The words return to zero by the end of every launch, so nothing is cleared between launches and there is no per-launch epoch
+// on the host (launches are capturable; the workspace serves one stream at a time).
+// (the atomics' address and constant operands are moved into vector registers HERE, per use: left to the compiler they are loop
+//  invariants, hoisted to the kernel's entry, and cost registers across the K loops -- 231 -> 235 VGPRs)
+__device__ __forceinline__ unsigned *ln_tail_ptr(unsigned *q) {
+    const unsigned long long a = (unsigned long long)q;
+    uint32_t lo, hi;
+    asm volatile("v_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=v"(lo), "=v"(hi) : "s"((uint32_t)a), "s"((uint32_t)(a >> 32)));
+    return (unsigned *)(((unsigned long long)hi << 32) | lo);
+}
+__device__ __forceinline__ void ln_tail_arrive(unsigned *cnt, unsigned *pend, int tm, int local, unsigned tiles_n) {
+    cnt = ln_tail_ptr(cnt + tm);
+    pend = ln_tail_ptr(pend + (local >> 5));
+    unsigned one;
+    asm volatile("v_mov_b32 %0, 1" : "=v"(one));
+    const unsigned old = __hip_atomic_fetch_add(cnt, one, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (old == tiles_n - 1) {
+        __hip_atomic_store(cnt, one - 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_or(pend, one << (local & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+// workgroup barrier behind this wave's LDS traffic only (a __syncthreads would also wait for the operand DMA in flight)
+__device__ __forceinline__ void lds_barrier() {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+// -> index of the claimed block inside its XCD's range, or -1
+__device__ __forceinline__ int ln_tail_claim(unsigned *pend, int words) {
+    for (int w = 0; w < words; ++w, ++pend) {
+        unsigned *word = ln_tail_ptr(pend);
+        unsigned v = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        while (v) {   // at most 32 rounds: v only loses bits
+            const unsigned bit = v & (0u - v);
+            const unsigned old = __hip_atomic_fetch_and(word, ~bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (old & bit) return w * 32 + __builtin_ctz(bit);
+            v &= old & ~bit;
+        }
+    }
+    return -1;
+}
+// rows blk * 256 .. + 255 (clipped at m) of x = p.out -> p.ex.ln_out, by all eight waves: wave w takes rows w, w + 8, ... with R
+// rows in flight.  The row arithmetic is ln_row.h's -- bit for bit what layernorm_light_kernel stores.
+// gb: gamma | beta of the launch in LDS (staged once at kernel start: as registers of the tail they were the kernel's high-water mark).
+template <int NV>
+__device__ __forceinline__ void ln_tail_block(const GemmArgs &p, int blk, int wave, int lane, const char *gb) {
+    constexpr int W = NV * 256, R = 3;
+    const int64_t r0 = (int64_t)blk * 256;
+    const int left = (int)p.m - blk * 256;   // (32-bit: the launcher keeps m n 4 below 2^32)
+    const int rows = left < 256 ? left : 256;
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void *)((float *)p.out + r0 * W), 0, rows * W * 4, 0x00020000);
+    const __amdgpu_buffer_rsrc_t ro = __builtin_amdgcn_make_buffer_rsrc((void *)(p.ex.ln_out + r0 * W), 0, rows * W * 2, 0x00020000);
+    const uint32_t off = (uint32_t)lane * 16u;
+    const f32x4_t *g = (const f32x4_t *)(gb + lane * 16), *b = (const f32x4_t *)(gb + W * 4 + lane * 16);   // round i: [i * 64]
+    f32x4_t v[R][NV];
+#pragma unroll
+    for (int u = 0; u < R; ++u)
+        if (u * 8 + wave < rows) ln_row_load<NV, 16>(v[u], rx, off, (uint32_t)(u * 8 + wave) * (W * 4));
+#pragma nounroll
+    for (int j = 0; j < 32; j += R) {
+#pragma unroll
+        for (int u = 0; u < R; ++u) {
+            const int row = (j + u) * 8 + wave;   // wave-uniform
+            if (j + u < 32 && row < rows) {
+                ln_row_finish<false, NV, true>(v[u], rx, rx, g, b, ro, off, (uint32_t)row * (W * 2), p.ex.eps);
+                if (row + R * 8 < rows) ln_row_load<NV, 16>(v[u], rx, off, (uint32_t)(row + R * 8) * (W * 4));
+            }
+        }
+    }
+}
+
 template <int EPI>
 __global__ __launch_bounds__(512, 2) void gemm_bf16_v4_kernel(GemmArgs p) {
     lp_kernel_entry();
@@ -1150,6 +1246,16 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_v4_kernel(GemmArgs p) {
         while (__builtin_amdgcn_s_memtime() - t_launch < (unsigned long long)skew_wait) __builtin_amdgcn_s_sleep(4);
     ml64::Frags f;
     char *reg = lds2 + 6 * ml64::UNIT_BYTES + wave * 4096;
+    // RESADD_LN (see ln_tail_arrive): this XCD's row blocks, its pend words, and the word behind the bias rows through which the
+    // claiming lane tells the workgroup which block it got
+    constexpr bool TAIL = EPI == VSC_EPI_RESADD_LN_F32;
+    const int tl_per = p.tiles_m >> 3, tl_words = (tl_per + 31) >> 5, tl_first = (int)(blockIdx.x & 7) * tl_per;
+    unsigned *tl_pend = TAIL ? p.ex.tail_ws + p.tiles_m + (blockIdx.x & 7) * tl_words : nullptr;
+    volatile int *tl_bc = (volatile int *)(ext + 2 * EXT);
+    const char *tl_gb = ext + 2 * EXT + 64;   // gamma | beta, 2 x 3 KiB
+    if constexpr (TAIL) {
+        if (tid < 384) *(f32x4_t *)(ext + 2 * EXT + 64 + tid * 16) = *(const f32x4_t *)((tid < 192 ? p.ex.gamma : p.ex.beta - 768) + tid * 4);   // (visible behind the prologue's barrier)
+    }
 #ifdef VSC_GEMM_TIMING
     const bool rec = blockIdx.x == 37 && lane == 0 && (wave == 0 || wave == 4) && p.dbg;
     unsigned long long *tb = p.dbg + (wave >> 2) * 32;
@@ -1183,6 +1289,14 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_v4_kernel(GemmArgs p) {
         // instead of hoisted out of the tile loop and carried (spilled) across the K loop
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
+        if constexpr (TAIL) {
+            if (i > 0) {   // the claim point (nothing can be complete before a workgroup's first write-out but by a faster neighbour: the drain's)
+                if (wave == 0 && lane == 0) *tl_bc = ln_tail_claim(tl_pend, tl_words);
+                lds_barrier();
+                const int got = __builtin_amdgcn_readfirstlane(*tl_bc);
+                if (got >= 0) ln_tail_block<3>(p, tl_first + got, wave, lane_e, tl_gb);
+            }
+        }
         if constexpr (EPI == VSC_EPI_LN_RES_F32)
             epilogue_ln(p, acc, lds2 + 6 * ml64::UNIT_BYTES, reg, ext + (i & 1) * EXT, lane_e, wm, wn, (int64_t)tm * 256, tn * 256, i);
         else
@@ -1211,9 +1325,17 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_v4_kernel(GemmArgs p) {
             tb[4 + i * 5] = __builtin_amdgcn_s_memtime();
         }
 #endif
+        if constexpr (TAIL) {
+            ml64::wait_vmcnt<0>();          // this wave's residual stores are in the XCD's L2 ...
+            __builtin_amdgcn_s_barrier();   // ... and so are the other seven's (the tile-end barrier, here behind the last tile as well)
+            __builtin_amdgcn_sched_barrier(0);
+            if (wave == 0 && lane == 0) ln_tail_arrive(p.ex.tail_ws, tl_pend, tm, tm - tl_first, (unsigned)p.tiles_n);
+            if (last) break;
+        } else {
         if (last) break;
         __builtin_amdgcn_s_barrier();   // every wave is done with slots 6, 7 and has waited for its DMA pieces
         __builtin_amdgcn_sched_barrier(0);
+        }
 #ifdef VSC_GEMM_TIMING
         if (rec && i < 6) tb[5 + i * 5] = __builtin_amdgcn_s_memtime();
 #endif
@@ -1221,12 +1343,24 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_v4_kernel(GemmArgs p) {
         tm = tm2;
         tn = tn2;
     }
+    if constexpr (TAIL) {
+        // the drain: behind this workgroup's last arrive, claim until a scan of the XCD's words finds nothing
+        for (;;) {
+            lds_barrier();   // (every wave has read the previous answer)
+            if (wave == 0 && lane == 0) *tl_bc = ln_tail_claim(tl_pend, tl_words);
+            lds_barrier();
+            const int got = __builtin_amdgcn_readfirstlane(*tl_bc);
+            if (got < 0) break;
+            ln_tail_block<3>(p, tl_first + got, wave, lane, tl_gb);
+        }
+    }
 }
 
 template <int EPI>
 int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
-    constexpr int smem_max = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + 12 * 2048 : 2048);
-    const int smem = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + p.ex.nslices * 2048 : 2048);
+    constexpr int smem_tail = EPI == VSC_EPI_RESADD_LN_F32 ? 64 + 2 * 768 * 4 : 0;   // the claim word and gamma | beta behind the bias rows
+    constexpr int smem_max = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + 12 * 2048 : 2048 + smem_tail);
+    const int smem = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + p.ex.nslices * 2048 : 2048 + smem_tail);
     auto kern = gemm_bf16_v4_kernel<EPI>;
     VSC_TRY(vsc_allow_dynamic_lds(kern, smem_max));
     // groups of 4 N-tiles; of 3 where that divides the row of tiles and 4 does not (qkv: 9 = 3 + 3 + 3 instead of 4 + 4 + 1:
@@ -1236,6 +1370,7 @@ int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
     p.group_n = g < 1 ? 1 : (g > p.tiles_n ? p.tiles_n : g);
     p.skew = 0;
     p.skew_groups = 1;
+    if (EPI == VSC_EPI_RESADD_LN_F32) p.group_n = p.tiles_n;   // a row block's tiles are consecutive tile indices (no diagnostic regrouping)
     constexpr bool pair_exchange = EPI == VSC_EPI_LN_RES_F32;
     if (pair_exchange) {
         // the row's two tiles (t, t ^ 1) must land on workgroups (b, b ^ 8) of the same round: N-groups spanning the whole row
@@ -1281,6 +1416,16 @@ int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
     return VSC_OK;
 }
 
+// the shapes the persistent kernel takes (p.tiles_m / p.tiles_n: 256 x 256 tiles)
+inline bool v4_shape_ok(const GemmArgs &p, int cus, bool bf16_out) {
+    const int64_t a_span = (int64_t)p.tiles_m * 256 * p.k * 2, w_span = (int64_t)p.tiles_n * 256 * p.k * 2;
+    // (K > 3072: the per-tile costs v4 removes are < 1 % of a tile and its lockstep costs ~3 % -- 8192^3 680 vs 701 us)
+    // fp32 write-outs address [m, n] by 32-bit byte offsets from the matrix origin, rows of the last (ragged) tile included
+    const bool out_span_ok = (int64_t)p.tiles_m * 256 * p.n * (bf16_out ? 2 : 4) < (1ll << 32);
+    return p.k % 128 == 0 && p.k >= 128 && p.k <= 3072 && cus % 8 == 0 && (int64_t)p.tiles_m * p.tiles_n > cus && a_span < (1ll << 32) &&
+           w_span < (1ll << 32) && out_span_ok;
+}
+
 // v3 or its persistent form: v4 wherever a workgroup gets more than one tile and the 32-bit source offsets hold
 template <int EPI>
 int launch_v34(GemmArgs p, hipStream_t stream) {
@@ -1290,12 +1435,7 @@ int launch_v34(GemmArgs p, hipStream_t stream) {
         const bool off = vsc_opt_is(OPT_GEMM_V4, '0');   // diagnostic A/B switch, read per launch
         int cus = 0;
         VSC_TRY(vsc_device_cus(&cus));
-        const int64_t a_span = (int64_t)p.tiles_m * 256 * p.k * 2, w_span = (int64_t)p.tiles_n * 256 * p.k * 2;
-        // (K > 3072: the per-tile costs v4 removes are < 1 % of a tile and its lockstep costs ~3 % -- 8192^3 680 vs 701 us)
-        // fp32 write-outs address [m, n] by 32-bit byte offsets from the matrix origin, rows of the last (ragged) tile included
-        const bool out_span_ok = (int64_t)p.tiles_m * 256 * p.n * (epi_bf16_out(EPI) ? 2 : 4) < (1ll << 32);
-        if (!off && p.k % 128 == 0 && p.k >= 128 && p.k <= 3072 && cus % 8 == 0 && (int64_t)p.tiles_m * p.tiles_n > cus &&
-            a_span < (1ll << 32) && w_span < (1ll << 32) && out_span_ok && (EPI != VSC_EPI_RESADD_F32 || p.aux) &&
+        if (!off && v4_shape_ok(p, cus, epi_bf16_out(EPI)) && (EPI != VSC_EPI_RESADD_F32 || p.aux) &&
             (!epi_lnf(EPI) || p.m * 8 < (1ll << 32)))
         {
             int grid = cus;
@@ -1753,6 +1893,81 @@ int launch_gemm_bf16_ex(const uint16_t *a, const uint16_t *w, const float *bias,
         default: VSC_REQUIRE(false, "gemm: unknown epilogue %d", epilogue);
     }
     return VSC_OK;
+}
+
+
+// ---- residual GEMM + LayerNorm: one persistent launch with the LayerNorm as its tail, or today's two launches ----------------------
+// The tail form needs what makes launch_gemm_bf16 pick the persistent kernel for this shape (no diagnostic switch that routes it
+// elsewhere), N = 768 as one N-group, and whole row blocks per XCD range: total % 8 == 0 and (total / 8) % tiles_n == 0, i.e.
+// tiles_m % 8 == 0 (see ln_tail_arrive).
+bool gemm_resadd_ln_tail_eligible(int64_t m, int n, int k) {
+    // OPT-IN (VSC_GEMM_LN_TAIL=1): measured on the MI355X the tail costs ~98 us a launch where the LayerNorm launch it replaces takes
+    // 55 -- one lane -6 %, two lanes inside the run-to-run spread
+    if (!vsc_opt_is(OPT_GEMM_LN_TAIL, '1') || vsc_opt_is(OPT_GEMM_V4, '0') || vsc_opt_is(OPT_GEMM_V3, '0') || vsc_opt(OPT_GEMM_V1) ||
+        vsc_opt(OPT_GEMM_CFG) || vsc_opt(OPT_GEMM_V4_GRID))
+        return false;
+    if (n != 768 || k <= 512 || k % 128 != 0 || m < 1024) return false;
+    int cus = 0;
+    if (vsc_device_cus(&cus) != VSC_OK) return false;
+    GemmArgs p{};
+    p.m = m;
+    p.n = n;
+    p.k = k;
+    p.tiles_m = (int)((m + 255) / 256);
+    p.tiles_n = n / 256;
+    return p.tiles_m % 8 == 0 && v4_shape_ok(p, cus, false);
+}
+size_t gemm_ln_tail_ws_bytes(int64_t m) {
+    const int64_t tiles_m = (m + 255) / 256;
+    return (size_t)(tiles_m + 8 * ((tiles_m / 8 + 31) / 32) + 8) * 4;
+}
+static std::atomic<int> g_resadd_ln_last_path{0};   // 1 the tail form, 2 two launches
+extern "C" int vsc_gemm_resadd_ln_last_path(void) { return g_resadd_ln_last_path.load(std::memory_order_relaxed); }
+
+int launch_gemm_resadd_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias, float *x, const float *gamma, const float *beta,
+                               uint16_t *y, int64_t m, int n, int k, float eps, unsigned *tail_ws, hipStream_t stream) {
+    VSC_REQUIRE(a && w && x && gamma && beta && y, "gemm_resadd_ln: null operand");
+    VSC_REQUIRE(m > 0 && n > 0 && k > 0, "gemm_resadd_ln: empty problem m=%lld n=%d k=%d", (long long)m, n, k);
+    if (tail_ws && gemm_resadd_ln_tail_eligible(m, n, k)) {
+        int cus = 0;
+        VSC_TRY(vsc_device_cus(&cus));
+        GemmArgs p{a, w, bias, x, x, m, n, k, 0, n / 256, (int)((m + 255) / 256), 1, 0};
+        p.abl = vsc_opt_int(OPT_GEMM_ABL, 0);
+        p.ex.gamma = gamma;
+        p.ex.beta = beta;
+        p.ex.eps = eps;
+        p.ex.ln_out = y;
+        p.ex.tail_ws = tail_ws;
+        g_resadd_ln_last_path.store(1, std::memory_order_relaxed);
+        return launch_v4<VSC_EPI_RESADD_LN_F32>(p, cus, stream);
+    }
+    g_resadd_ln_last_path.store(2, std::memory_order_relaxed);
+    VSC_TRY(launch_gemm_bf16(a, w, bias, x, x, m, n, k, VSC_EPI_RESADD_F32, 0, stream));
+    return launch_layernorm(x, gamma, beta, y, m, n, eps, 0, stream);
+}
+
+// debug entry (include/vsc_hip.h): the workspace is the library's, one per (device, stream), zeroed when it is made
+extern "C" int vsc_gemm_resadd_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias, float *x_inout, const float *gamma,
+                                       const float *beta, uint16_t *y_out, int64_t m, int32_t n, int32_t k, float eps, void *stream) {
+    static std::mutex mu;
+    static std::map<std::pair<int, void *>, std::pair<unsigned *, size_t>> spaces;
+    VSC_REQUIRE(m > 0, "gemm_resadd_ln: empty problem");
+    int dev = 0;
+    VSC_CHECK_HIP(hipGetDevice(&dev));
+    const size_t need = gemm_ln_tail_ws_bytes(m);
+    unsigned *ws = nullptr;
+    {
+        std::lock_guard<std::mutex> lock(mu);
+        auto &slot = spaces[{dev, stream}];
+        if (slot.second < need) {
+            // (a smaller one is left to the stream's earlier launches: a handful of bytes per distinct size)
+            VSC_CHECK_HIP(hipMalloc((void **)&slot.first, need));
+            slot.second = need;
+            VSC_CHECK_HIP(hipMemsetAsync(slot.first, 0, need, (hipStream_t)stream));
+        }
+        ws = slot.first;
+    }
+    return launch_gemm_resadd_ln_bf16(a, w, bias, x_inout, gamma, beta, y_out, m, n, k, eps, ws, (hipStream_t)stream);
 }
 
 // (mean, M2) of the width / 64 column slices of every row -> (mean, rstd) of the row (Chan's pairwise update with

@@ -145,6 +145,9 @@ SIGNATURES = {
     "vsc_l2_normalize_f32": (c_int32, [c_void_p, c_int64, c_int32, c_void_p]),
     "vsc_gemm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                 c_int32, c_int32, c_int32, c_void_p]),
+    "vsc_gemm_resadd_ln_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                          c_int32, c_float, c_void_p]),
+    "vsc_gemm_resadd_ln_last_path": (c_int32, []),
     "vsc_attention_bf16": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "vsc_layernorm_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float,
                                     c_int32, c_void_p]),

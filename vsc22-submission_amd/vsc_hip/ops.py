@@ -110,6 +110,30 @@ def layernorm(x, gamma, beta, eps: float, out_f32: bool = False):
     return out
 
 
+def gemm_resadd_ln_bf16(a, w, bias, x, gamma, beta, eps: float, y=None, rows=None):
+    """x[:rows] += a[:rows] @ w.T + bias IN PLACE (float32), y[:rows] = LayerNorm(x[:rows]) * gamma + beta in the operand type:
+    one persistent launch with the LayerNorm as its tail where that form exists, otherwise GEMM + LayerNorm launches -- the same
+    bits (gemm_resadd_ln_last_path() says which ran).  rows < len(x): the rows behind are left alone.  -> y"""
+    lib = _rd()
+    assert a.dtype == lp_dtype() and w.dtype == lp_dtype() and x.dtype == torch.float32 and x.is_contiguous() and a.is_contiguous()
+    m = a.shape[0] if rows is None else rows
+    k, n = a.shape[1], w.shape[0]
+    assert w.shape[1] == k and x.shape[1] == n and m <= a.shape[0] and m <= x.shape[0]
+    bias = None if bias is None else _dev(bias, torch.float32)
+    gamma, beta = _dev(gamma, torch.float32), _dev(beta, torch.float32)
+    if y is None:
+        y = torch.empty((x.shape[0], n), dtype=lp_dtype(), device=x.device)
+    assert y.dtype == lp_dtype() and y.is_contiguous() and y.shape[0] >= m
+    check(lib.vsc_gemm_resadd_ln_bf16(ptr(a), ptr(w.contiguous()), ptr(bias), ptr(x), ptr(gamma), ptr(beta), ptr(y), m, n, k, eps,
+                                      current_stream()))
+    return y
+
+
+def gemm_resadd_ln_last_path() -> int:
+    """1: the last residual GEMM + LayerNorm ran as one launch with the LayerNorm tail, 2: as two launches"""
+    return int(_rd().vsc_gemm_resadd_ln_last_path())
+
+
 def patchify_bf16(frames, patch: int, kpad: int):
     lib = _rd()
     frames = _dev(frames, torch.float32)
