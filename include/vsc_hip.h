@@ -283,6 +283,41 @@ int vsc_video_pair_max_f32(const float *q_dev, int64_t nq, const int32_t *q_vide
  * split) list held more than 1024 survivors).  Chosen like vsc_knn_ip_f32's path; VSC_PAIRMAX_PATH=exact|bf16 forces one. */
 int vsc_video_pair_max_last_path(void);
 
+/* Global top-k of frame pairs -- the selection behind the descriptor track's candidates (infer/vsc/index.py:145-165: every hit
+ * inside the radius sorted by score and cut to global_k; infer/vsc/candidates.py:24-40 consumes the list) -- over a probe that
+ * stays on the device: the search's [nq, k'] result, a range sweep's CSR hits, or the union of several ranks' selections.
+ * scores_dev / ids_dev [n]; rows_dev [n] int64, or NULL: the row of entry p is p / row_stride (a row-major [nq, row_stride]
+ * probe).  Entries with ids[p] < 0 are not candidates (the search's (-FLT_MAX, -1) padding).  Among the rest the
+ * m = min(want, valid) entries with the largest score are written best first to out_rows_dev / out_ids_dev / out_scores_dev
+ * (each [min(want, n)]; scores keep their bits) and m to out_count_dev [1] (device).  Equal scores keep their input order, and
+ * -0.0f equals +0.0f: the list is the head of a stable descending sort by score.  Scores are finite or infinite; NaN is
+ * outside the contract (it neither faults nor hangs, its place in the order is unspecified).  n < 2^31.  n == 0 or want == 0
+ * writes count 0 and launches nothing that reads the inputs.
+ * The result is a pure function of the inputs: integer atomics only accumulate histogram counts, every output position comes
+ * from a prefix scan.  Passes: radix select of the want-th key (4 histogram sweeps), stable compaction of the entries above it
+ * and of the first entries equal to it, stable 8-bit LSD radix sort of the survivors, gather.  The compaction works on tiles
+ * of VSC_GLOBAL_TOPK_TILE entries.  Scratch: the search's grow-only per-device buffers (8 bytes per 2048 entries + 16 bytes
+ * per selected entry), freed by vsc_search_release_scratch.  Only enqueues on `stream`; no host synchronisation. */
+#define VSC_GLOBAL_TOPK_TILE 2048
+int vsc_global_topk_f32(const float *scores_dev, const int64_t *rows_dev, const int64_t *ids_dev, int64_t n, int32_t row_stride,
+                        int64_t want, int64_t *out_rows_dev, int64_t *out_ids_dev, float *out_scores_dev, int64_t *out_count_dev,
+                        void *stream);
+
+/* First hit of every video pair in a best-first hit list -- the grouping of infer/vsc/candidates.py:24-40 under
+ * MaxScoreAggregation over the list of infer/vsc/index.py:145-165: in best-first order a video pair's first hit is its maximum.
+ * rows_dev / ids_dev [n]: query row and reference row of every hit; q_video_dev [number of query rows] / r_video_dev [number of
+ * reference rows]: int32 video index of a row, 0 <= r video < n_r_videos; every rows[p] / ids[p] >= 0 must index its table --
+ * the entry has no table lengths and checks nothing: the lists come from the library's own search and selection -- (a hit with a
+ * negative row or id belongs to no pair).  The pair key is q_video[rows[p]] * n_r_videos + r_video[ids[p]] in 64
+ * bits.  Writes to out_pos_dev [min(n, limit)] the positions p, ascending, of the first hit of every distinct key -- only the first
+ * `limit` of them (limit < 0: all) -- and their number to out_count_dev [1] (device): np.unique(key, return_index=True), sort,
+ * [:limit].  n < 2^31.  n == 0 or limit == 0 writes count 0 and launches nothing.  Deterministic: an open-addressing table keeps
+ * the atomicMin of the positions per key (order-independent), the positions are written through a prefix scan.  Scratch: the
+ * search's grow-only buffers (12 bytes per table slot, 2 n rounded up to a power of two slots, + n bytes).  Only enqueues. */
+int vsc_pair_first_hits(const int64_t *rows_dev, const int64_t *ids_dev, int64_t n, const int32_t *q_video_dev,
+                        const int32_t *r_video_dev, int32_t n_r_videos, int64_t limit, int64_t *out_pos_dev,
+                        int64_t *out_count_dev, void *stream);
+
 /* Temporal-network (TN) alignment -- VCSL's `tn` (VSC22-Descriptor-Track-1st/infer/vcsl/vta.py:244-363, with `iou` :80-95),
  * the alignment step of sscd_baseline's localize_and_verify -- over the matrices of vsc_pair_similarity_f32, one wave per pair.
  * sims_dev: fp32 similarities (sims_len floats); pairs_host [n_pairs][3] = {element offset, q_rows, r_rows} (HOST memory):

@@ -322,6 +322,11 @@ enum SearchScratchSlot {
     SCRATCH_TN_TABLE = 19, SCRATCH_TN_NODES = 20,         // tn_align.hip
     SCRATCH_VIEW_CANNY = 21, SCRATCH_VIEW_RESIZE = 22,    // view_prep.hip
     SCRATCH_MS_TABLE = 23,                                // match_segments.hip
+    // global_topk.hip
+    SCRATCH_GTK_STATE = 24, SCRATCH_GTK_BLOCKS = 25,      // global top-k: select state; (above, equal) counts per tile
+    SCRATCH_GTK_KEYS = 26, SCRATCH_GTK_PAY = 27, SCRATCH_GTK_HIST = 28,   // survivors' keys / positions (two buffers each); [digit][tile] counters
+    SCRATCH_PFH_KEYS = 29, SCRATCH_PFH_POS = 30,          // pair first hits: table keys, least position per key
+    SCRATCH_PFH_FLAGS = 31, SCRATCH_PFH_BLOCKS = 32,      // first-hit flag per entry; flags per tile
     SCRATCH_SLOTS
 };
 // temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h

@@ -27,14 +27,17 @@ logger = logging.getLogger("sscd_baseline.py")
 
 
 def search(queries: List[VideoFeature], refs: List[VideoFeature], retrieve_per_query: float = 1200.0,
-           candidates_per_query: float = 25.0) -> List[CandidatePair]:
-    cg = CandidateGeneration(refs, MaxScoreAggregation())
+           candidates_per_query: float = 25.0, selection: str = "host") -> List[CandidatePair]:
+    """selection: "host" (the probe is ordered and grouped on the host) or "hip" (vsc_global_topk_f32 / vsc_pair_first_hits: only
+    the candidate pairs leave the device); the same list either way."""
+    cg = CandidateGeneration(refs, MaxScoreAggregation(), selection=selection)
     candidates = cg.query(queries, global_k=int(retrieve_per_query * len(queries)), limit=int(candidates_per_query * len(queries)))
     logger.info("Got %d candidates", len(candidates))
     return candidates
 
 
 ALIGNMENTS = ("vcsl", "hip")
+CANDIDATES = ("host", "hip")
 
 
 def localize_and_verify(queries: List[VideoFeature], refs: List[VideoFeature], candidates: List[CandidatePair],
@@ -94,7 +97,7 @@ def main(args) -> None:
                                         beta=1.2)
         store_features(os.path.join(args.output_path, "sn_queries.npz"), queries)
         store_features(os.path.join(args.output_path, "sn_refs.npz"), refs)
-    candidates = search(queries, refs)
+    candidates = search(queries, refs, selection=getattr(args, "candidates", "host"))
     candidate_file = os.path.join(args.output_path, "candidates.csv")
     CandidatePair.write_csv(candidates, candidate_file)
     logger.info("Candidates: %s", candidate_file)
@@ -124,6 +127,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--alignment", choices=ALIGNMENTS, default="vcsl",
                     help="temporal alignment of matches.csv: the reference's VCSL package (vcsl) or the HIP kernel (hip)")
+    ap.add_argument("--candidates", choices=CANDIDATES, default="host",
+                    help="global top-k selection and video-pair grouping of candidates.csv: on the host (host) or in HIP (hip)")
     return ap
 
 

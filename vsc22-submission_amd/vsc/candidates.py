@@ -34,11 +34,12 @@ class MaxScoreAggregation(ScoreAggregation):
 
 
 class CandidateGeneration:
-    def __init__(self, references: Sequence[VideoFeature], aggregation: ScoreAggregation):
+    def __init__(self, references: Sequence[VideoFeature], aggregation: ScoreAggregation, selection: str = "host"):
+        """selection: "host" or "hip" -- where the global top-k is cut and grouped into video pairs (VideoIndex)."""
         if not references:
             raise ValueError("CandidateGeneration needs at least one reference video")
         self.aggregation = aggregation
-        self.index = VideoIndex(references[0].dimensions())
+        self.index = VideoIndex(references[0].dimensions(), selection=selection)
         self.index.add(list(references))
 
     def query(self, queries: List[VideoFeature], global_k: int, limit: int = None) -> List[CandidatePair]:

@@ -183,6 +183,27 @@ class FlatIPBank:
         keep = dist < np.float32(radius)
         return rows[keep], ids[keep], dist[keep]
 
+    def search_device(self, x: np.ndarray, k: int):
+        """search() whose result stays on the device: (D [nq,k] float32, I [nq,k] int64) tensors.  Inner product only: the L2
+        form orders by distances recomputed on the host."""
+        from vsc_hip import ops
+        if not self.is_similarity:
+            raise ValueError("search_device: inner-product indexes only (METRIC_L2 needs the host's exact distances)")
+        if k > MAX_K:
+            raise NotImplementedError(f"k={k} > {MAX_K} is not supported by vsc_knn_ip_f32")
+        return ops.knn_ip(self._device_queries(x), self.device_bank(), k)
+
+    def range_search_device(self, x: np.ndarray, radius: float):
+        """range_search() whose result stays on the device: (query rows, ref rows, scores) tensors, query-major, ascending ref
+        row inside a query.  Inner product only."""
+        import torch
+        from vsc_hip import ops
+        if not self.is_similarity:
+            raise ValueError("range_search_device: inner-product indexes only (METRIC_L2 needs the host's exact distances)")
+        lims, D, I = ops.range_search_ip(self._device_queries(x), self.device_bank(), float(radius))
+        rows = torch.repeat_interleave(torch.arange(lims.numel() - 1, dtype=torch.int64, device=lims.device), lims[1:] - lims[:-1])
+        return rows, I, D
+
     def search(self, x: np.ndarray, k: int):
         """-> (D [nq,k] float32, I [nq,k] int64), faiss.Index.search semantics: inner products descending, or squared
         L2 distances ascending."""
@@ -206,6 +227,16 @@ class FlatIPBank:
         return np.take_along_axis(dist, order, 1), np.take_along_axis(I, order, 1)
 
 
+def probe_size(global_k: int, nq: int, nr: int) -> int:
+    """k' of the global-threshold probe (VideoIndex._global_threshold_hits): twice the mean number of winners per query row as a
+    power of two, at least 16, at most min(global_k, nr, MAX_K); 0 when there is nothing to search."""
+    kk = int(min(global_k, nr, MAX_K))
+    if kk <= 0 or nq == 0:
+        return 0
+    mean = -(-int(min(global_k, nq * nr)) // nq)
+    return int(min(kk, max(16, 1 << (2 * mean - 1).bit_length())))
+
+
 def _best_first(scores: np.ndarray, want: int, descending: bool) -> np.ndarray:
     """Indices of the `want` best scores, best first, equal scores in their order of appearance: a stable sort -- of host bookkeeping,
     not of the search -- on the device where there is one (20M pairs: milliseconds), numpy's otherwise (the host-logic tests)."""
@@ -218,10 +249,22 @@ def _best_first(scores: np.ndarray, want: int, descending: bool) -> np.ndarray:
     return torch.sort(t, descending=descending, stable=True).indices[:want].cpu().numpy()
 
 
+SELECTIONS = ("host", "hip")
+
+
 class VideoIndex:
-    def __init__(self, dim: int, codec_str: str = "Flat", metric: int = METRIC_INNER_PRODUCT):
+    def __init__(self, dim: int, codec_str: str = "Flat", metric: int = METRIC_INNER_PRODUCT, selection: str = "host"):
+        """selection: where the global top-k is cut and grouped -- "host": the probe is copied back, ordered by _best_first and
+        grouped with numpy; "hip": the probe stays on the device (vsc_global_topk_f32, vsc_pair_first_hits) and only the
+        selected hits / the candidate pairs come back.  Same lists either way."""
         if codec_str != "Flat":
             raise NotImplementedError(f"codec {codec_str!r}: the descriptor track only uses 'Flat'")
+        if selection not in SELECTIONS:
+            raise ValueError(f"selection {selection!r}: one of {SELECTIONS}")
+        if selection == "hip" and metric != METRIC_INNER_PRODUCT:
+            raise ValueError("selection='hip' is the inner-product form: the METRIC_L2 path orders by the host's exact distances")
+        self.selection = selection
+        self._ref_video_table = None    # (names, int32 video of every bank row on the device), built once per bank
         self.dim = dim
         self.index = FlatIPBank(dim, metric)
         self.video_clip_idx: list = []
@@ -235,6 +278,7 @@ class VideoIndex:
             self.video_clip_to_video_ids.extend([vf.video_id] * n)
             self.video_metadata[vf.video_id] = vf.metadata()
             self.index.add(vf.feature)
+        self._ref_video_table = None
 
     def search(self, queries: List[VideoFeature], global_k: int) -> List[PairMatches]:
         query_ids, query_rows = [], []
@@ -281,6 +325,8 @@ class VideoIndex:
         if not queries:
             return [], [], []
         feats = np.concatenate([q.feature for q in queries])
+        if self.selection == "hip":
+            return self._pair_maxima_device(queries, feats, global_k, limit)
         rows, refs, scores = self._global_threshold_hits(feats, global_k)
         if len(rows) == 0:
             return [], [], []
@@ -293,6 +339,57 @@ class VideoIndex:
         qv, rv = q_of_row[rows[first]], r_of_row[refs[first]]
         return [queries[i].video_id for i in qv.tolist()], r_names[rv].tolist(), scores[first].tolist()
 
+    def _pair_maxima_device(self, queries: List[VideoFeature], feats: np.ndarray, global_k: int, limit):
+        """search_pair_maxima with the hit list on the device: grouped by vsc_pair_first_hits against int32 video tables (the
+        reference side built once per bank), and only the first `limit` (row, ref, score) triples are copied back."""
+        from vsc_hip import ops
+        rows, refs, scores = self._global_threshold_hits_device(feats, global_k)
+        if rows.numel() == 0:
+            return [], [], []
+        if self._ref_video_table is None:
+            names, r_of_row = np.unique(np.asarray(self.video_clip_to_video_ids), return_inverse=True)
+            self._ref_video_table = (names, self.index._to_device(np.ascontiguousarray(r_of_row, dtype=np.int32)))
+        r_names, r_video = self._ref_video_table
+        q_of_row = np.repeat(np.arange(len(queries), dtype=np.int32), [len(q) for q in queries])
+        first = ops.pair_first_hits(rows, refs, self.index._to_device(q_of_row), r_video, len(r_names), limit)
+        qv, rv = q_of_row[rows[first].cpu().numpy()], r_video[refs[first]].cpu().numpy()
+        return [queries[i].video_id for i in qv.tolist()], r_names[rv].tolist(), scores[first].cpu().tolist()
+
+    def _global_threshold_hits_device(self, feats: np.ndarray, global_k: int):
+        """_global_threshold_hits with the probe, the candidate set and the result on the device: (query rows, ref rows, scores)
+        tensors, the same list.  The probe size, the "does a row own more winners than the probe holds" test and the fall-back to
+        a threshold range sweep are the host path's; what differs is that the [nq, k'] probe is never copied back -- the cut is
+        vsc_global_topk_f32 (stable: the probe and the range sweep's CSR hits arrive query-major with equal scores of a row in
+        ascending ref order, so input order IS the host's tie order), the test is one reduction, and from the fall-back only the
+        probe's last column (nq floats, for _radius_for) reaches the host.  The test is strict, as on the host: a row whose k'-th
+        score equals the threshold is taken to own nothing more, so further pairs of exactly that score beyond its probe lose their
+        place at the end of the list to equal-score pairs of later rows -- the same list as the host path there too."""
+        import torch
+        from vsc_hip import ops
+        nr, nq = self.index.ntotal, feats.shape[0]
+        kk = probe_size(global_k, nq, nr)
+        if kk == 0:
+            dev = self.index._to_device(np.zeros(0, np.float32))
+            return dev.to(torch.int64), dev.to(torch.int64), dev
+        want = int(min(global_k, nq * nr))
+        D, I = self.index.search_device(feats, kk)
+        rows, refs, scores = ops.global_topk(D, I, want)
+        if kk < min(global_k, nr):   # the probe was capped: rows may hold winners beyond their k'-th hit
+            radius = None
+            kth = D[:, kk - 1]
+            if scores.numel() == want:
+                threshold = scores[-1]
+                if bool((kth > threshold).any()):
+                    radius = np.nextafter(np.float32(float(threshold)), np.float32(-np.inf))
+                    if self.index.range_count(feats, radius) > 2 * want + (1 << 20):
+                        radius = self._radius_for(feats, want, kth.cpu().numpy())
+            else:
+                radius = self._radius_for(feats, want, kth.cpu().numpy())
+            if radius is not None:
+                r_rows, r_refs, r_scores = self.index.range_search_device(feats, radius)
+                rows, refs, scores = ops.global_topk(r_scores, r_refs, want, rows=r_rows)
+        return rows, refs, scores
+
     def _global_threshold_hits(self, feats: np.ndarray, global_k: int):
         """-> (query rows, ref rows, scores): the min(global_k, nq * nr) best frame pairs, best first (ties: lower query row, then lower
         ref row).  The reference keeps every pair inside an adaptively tightened radius, sorts all of them by score and
@@ -302,6 +399,8 @@ class VideoIndex:
         probe holds fewer than global_k pairs in total -- an exact range sweep at a radius found by counting replaces
         the candidate set (since round 5 the probe is as small as the winners-per-row allow, not the fixed 1024).  Exact for inner-product indexes; for METRIC_L2 the distances handed back are recomputed exactly and the
         range sweep is widened by its rounding bound and re-filtered (FlatIPBank.range_search)."""
+        if self.selection == "hip":
+            return tuple(t.cpu().numpy() for t in self._global_threshold_hits_device(feats, global_k))
         sim = self.index.is_similarity
         nr, nq = self.index.ntotal, feats.shape[0]
         empty = (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.float32))

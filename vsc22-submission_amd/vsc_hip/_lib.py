@@ -97,6 +97,9 @@ SIGNATURES = {
     "vsc_video_pair_max_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int32,
                                          c_int32, ctypes.c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                          c_void_p]),
+    "vsc_global_topk_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                      c_void_p]),
+    "vsc_pair_first_hits": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int64, c_void_p, c_void_p, c_void_p]),
     "vsc_tn_align_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, ctypes.c_float, c_int32, c_int32, c_int32,
                                    ctypes.c_double, c_int32, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_match_segments_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,

@@ -187,3 +187,90 @@ def sharded_knn_score_normalized(queries_local: torch.Tensor, refs_local: torch.
     q2 = torch.cat([queries_local, bias.to(queries_local.dtype)], dim=1).contiguous()
     r2 = torch.cat([refs_local, torch.ones_like(refs_local[:, :1])], dim=1).contiguous()
     return sharded_knn(q2, r2, k, knn=knn, **kw)
+
+
+MAX_K = 1024     # vsc_knn_ip_f32's limit, the largest probe per query row (vsc/index.py: MAX_K)
+
+
+def _any_rank(flag: bool, device, always_collective: bool = False) -> bool:
+    """logical OR of a host flag over the ranks (one all_reduce of one int)"""
+    _, ws = world()
+    if ws == 1 and not (always_collective and dist.is_available() and dist.is_initialized()):
+        return bool(flag)
+    t = torch.tensor([1 if flag else 0], dtype=torch.int64, device=device)
+    dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    return bool(int(t.item()))
+
+
+def sharded_global_topk(queries_local: torch.Tensor, refs_local: torch.Tensor, global_k: int, knn: Optional[Callable] = None,
+                        select: Optional[Callable] = None, always_collective: bool = False, pipelined: bool = False):
+    """BASELINE.json configs[3]'s "global top-k" on the sharded path: the min(global_k, nq * nr) best (query row, reference row)
+    pairs over every rank's queries against every rank's references, best first, ties by (query row, reference row) -- the list
+    of VideoIndex._global_threshold_hits (infer/vsc/index.py:145-165) -> (rows, ids, scores) tensors, the same on every rank.
+
+    Query rows are numbered in rank order (one all_gather of the ranks' row counts gives the offsets), reference ids as
+    sharded_knn numbers them.  Every rank probes its own queries with sharded_knn(..., gather_to=None) at the probe size k' of
+    _global_threshold_hits and selects its min(want, local) best with `select`: a global winner owned by a rank is among that
+    rank's `want` best.  The lists are all_gathered in rank order -- which is row order, so a stable selection from the union
+    keeps the tie rule -- and every rank selects the global `want` from the union.  If some row's k'-th score still beats the
+    resulting threshold (that row may own winners the probe does not hold), or the probe holds fewer than `want` pairs, k' doubles,
+    up to MAX_K; beyond that NotImplementedError: the single-device path (VideoIndex(selection="hip")) answers such sets with a
+    range sweep.  The test is the host path's, strict: a row whose k'-th score EQUALS the threshold is taken to own nothing more, so
+    if it does own further pairs of exactly that score beyond its probe, equal-score pairs of later rows stand in their place at
+    the very end of the list (scores and count unaffected; _global_threshold_hits has the same edge).
+
+    `select(scores, ids, want, rows=) -> (rows, ids, scores)` defaults to the HIP selection (ops.global_topk), `knn` to the HIP
+    sweep; the CPU/gloo tests pass the oracle and the numpy contract -- test hooks, not fall-backs: the defaults raise without a GPU."""
+    if select is None:
+        from . import ops
+        select = ops.global_topk
+    rank, ws = world()
+    dev = queries_local.device
+    collective = ws > 1 or (always_collective and dist.is_available() and dist.is_initialized())
+    mine = torch.tensor([queries_local.shape[0], refs_local.shape[0]], dtype=torch.int64, device=dev)
+    if collective:
+        counts = torch.zeros(2 * ws, dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(counts, mine)
+        counts = counts.view(ws, 2).cpu()
+    else:
+        counts = mine.view(1, 2).cpu()
+    q_sizes = [int(v) for v in counts[:, 0].tolist()]
+    row0 = sum(q_sizes[:rank])
+    nq, nr = sum(q_sizes), int(counts[:, 1].sum())
+    empty = (torch.zeros(0, dtype=torch.int64, device=dev), torch.zeros(0, dtype=torch.int64, device=dev),
+             torch.zeros(0, dtype=torch.float32, device=dev))
+    full = int(min(global_k, nr))            # a probe this large holds every winner of every row
+    if full <= 0 or nq == 0:
+        return empty
+    want = int(min(global_k, nq * nr))
+    mean = -(-want // nq)
+    kk = int(min(full, MAX_K, max(16, 1 << (2 * mean - 1).bit_length())))
+    nq_local = queries_local.shape[0]
+    while True:
+        D, I = sharded_knn(queries_local, refs_local, kk, knn=knn, gather_to=None, always_collective=always_collective,
+                           pipelined=pipelined)
+        rows = (torch.arange(nq_local, dtype=torch.int64, device=dev) + row0)[:, None].expand(nq_local, kk).contiguous()
+        l_rows, l_ids, l_scores = select(D, I, want, rows=rows)
+        if collective:
+            # one collective for the three lists: (row, id, score bits) as int64 triples; all_gather_rows pads the shorter lists
+            # for the transfer and hands back the union without the padding, in rank order
+            packed = torch.stack([l_rows, l_ids, l_scores.contiguous().view(torch.int32).to(torch.int64)], dim=1)
+            union, _ = all_gather_rows(packed, always_collective)
+            u_rows, u_ids = union[:, 0].contiguous(), union[:, 1].contiguous()
+            u_scores = union[:, 2].to(torch.int32).view(torch.float32)
+            g_rows, g_ids, g_scores = select(u_scores, u_ids, want, rows=u_rows)
+        else:
+            g_rows, g_ids, g_scores = l_rows, l_ids, l_scores
+        if kk >= full:
+            return g_rows, g_ids, g_scores
+        if g_scores.numel() == want:
+            short = bool((D[:, kk - 1] > g_scores[-1]).any()) if nq_local else False
+        else:
+            short = True
+        if not _any_rank(short, dev, always_collective):
+            return g_rows, g_ids, g_scores
+        if kk >= MAX_K:
+            raise NotImplementedError(
+                f"sharded_global_topk: a query row owns more than {MAX_K} of the {want} best pairs (or the probe holds fewer than "
+                "that many); the single-device path, VideoIndex(selection='hip'), answers this with a range sweep")
+        kk = int(min(2 * kk, MAX_K, full))

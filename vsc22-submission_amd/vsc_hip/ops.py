@@ -238,6 +238,55 @@ def range_count_ip(q, r, radius: float) -> int:
     return int(total.value)
 
 
+GLOBAL_TOPK_TILE = 2048     # VSC_GLOBAL_TOPK_TILE (include/vsc_hip.h): entries per workgroup of the compaction passes
+
+
+def global_topk(scores, ids, want: int, rows=None):
+    """The min(want, valid) best entries of a probe, best first, equal scores in input order (vsc_global_topk_f32).
+    scores float32 / ids int64 of one shape, on the GPU; entries with ids < 0 are padding.  rows: int64 like ids, or None: the
+    row of an entry is its index along the first axis of a 2-d [nq, k] probe (its position, for a flat list).
+    -> (rows, ids, scores), device tensors cut to the count; synchronises once, to read that count."""
+    lib = _rd()
+    scores, ids = _dev(scores, torch.float32), _dev(ids, torch.int64)
+    assert scores.shape == ids.shape and scores.ndim in (1, 2), "scores / ids: one flat list or one [nq, k] probe"
+    n = scores.numel()
+    stride = scores.shape[1] if scores.ndim == 2 and rows is None else 1
+    if rows is not None:
+        rows = _dev(rows, torch.int64)
+        assert rows.shape == ids.shape
+    want = int(want)
+    assert want >= 0 and n < 1 << 31
+    cap = min(want, n)
+    out_rows = torch.empty(cap, dtype=torch.int64, device=scores.device)
+    out_ids = torch.empty(cap, dtype=torch.int64, device=scores.device)
+    out_scores = torch.empty(cap, dtype=torch.float32, device=scores.device)
+    count = torch.empty(1, dtype=torch.int64, device=scores.device)
+    check(lib.vsc_global_topk_f32(ptr(scores), ptr(rows), ptr(ids), n, max(stride, 1), want, ptr(out_rows), ptr(out_ids),
+                                  ptr(out_scores), ptr(count), current_stream()))
+    m = int(count.item())
+    return out_rows[:m], out_ids[:m], out_scores[:m]
+
+
+def pair_first_hits(rows, ids, q_video, r_video, n_r_videos: int, limit=None):
+    """Positions, ascending, of the first hit of every distinct (q_video[rows[p]], r_video[ids[p]]) pair of a best-first hit list,
+    the first `limit` of them (None: all) -- vsc_pair_first_hits.  rows / ids int64 [n], q_video / r_video int32 tables on the
+    GPU; every row / id >= 0 must index its table (the kernel has no table lengths: the lists are the search's and the selection's
+    own, nothing is checked here).  -> int64 device tensor; synchronises once, to read the count."""
+    lib = _rd()
+    rows, ids = _dev(rows, torch.int64), _dev(ids, torch.int64)
+    q_video, r_video = _dev(q_video, torch.int32), _dev(r_video, torch.int32)
+    n = rows.numel()
+    assert rows.shape == ids.shape == (n,) and n < 1 << 31 and n_r_videos >= 1
+    limit = n if limit is None or limit < 0 else min(int(limit), n)
+    out = torch.empty(limit, dtype=torch.int64, device=rows.device)
+    if n == 0 or limit == 0:
+        return out[:0]
+    count = torch.empty(1, dtype=torch.int64, device=rows.device)
+    check(lib.vsc_pair_first_hits(ptr(rows), ptr(ids), n, ptr(q_video), ptr(r_video), int(n_r_videos), limit, ptr(out), ptr(count),
+                                  current_stream()))
+    return out[: int(count.item())]
+
+
 def pair_similarity(q, r, pairs):
     """Frame x frame similarity matrices of candidate (query video, reference video) pairs.
     q [nq, d], r [nr, d]: frame banks; pairs: int64 [n, 4] rows (q_row0, q_rows, r_row0, r_rows) on the host.
