@@ -388,6 +388,33 @@ int vsc_match_segments_f32(const float *maps_dev, int64_t maps_len, const int64_
                            const float *thresholds, const double *std_ratios, int32_t n_thr, int32_t max_segments,
                            int32_t *out_segments_dev, double *out_scores_dev, int32_t *out_counts_dev, void *stream);
 
+/* Matching-track network inputs -- the reference's best-view choice (VSC22-Matching-Track-1st/infer/src/utils.py:18-73: per query
+ * view the mean of its ten largest row maxima, np.argmax over the views) and its padded 3-channel maps
+ * (VSC22-Matching-Track-1st/infer/src/dataset.py:103-144: MatchClassifyDataset / MatchRefineDataset) -- built on the device from the
+ * matrices of vsc_pair_similarity_f32, so that no similarity matrix and no network input crosses PCIe.
+ * sims_dev: fp32 similarities (sims_len floats); items_host [n_items][4] = {element offset, q_rows, r_rows, frames} (HOST memory):
+ * item p is the row-major [q_rows, r_rows] matrix s at sims_dev + offset, whose rows are views of `frames` rows each (frames = the
+ * query video's frame count).  resolution R: side of the canvas, 1 <= R <= 1024.  with_transpose: 0 or 1.
+ * Outputs (device): view_start_dev int32 [n_items] and out_dev float [n_items * (1 + with_transpose)][R][R][3] (channels last:
+ * viewed as [.., 3, R, R] it is a channels-last network input).
+ *   View: an item with q_rows <= frames has one view, view_start = 0, and is not read.  Otherwise, for view v = rows
+ *     [v frames, (v + 1) frames): m_i = fp32 maximum of row i over all r_rows columns (starting from -inf: rows of negative
+ *     similarities are legal); a[0 .. c-1] = the c = min(VSC_MATCH_TOP_ROWS, frames) largest m_i in ascending order; score =
+ *     fl(S / c) in fp32 (correctly rounded division) with S summed in numpy's pairwise order: c < 8: (((a0 + a1) + a2) + ..);
+ *     c = 8, 9, 10: ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)), then + a8, then + a9 -- np.sort(m)[-10:].mean() bit for
+ *     bit.  view_start = v frames of the first view whose score is strictly greater than every earlier one (np.argmax).
+ *   Canvas: slice p (1 + with_transpose): out[y][x][c] = s[view_start + y][x] for y < min(frames, q_rows, R) and x < min(r_rows, R),
+ *     0 elsewhere, the same on the three channels c.  With with_transpose, slice 2 p + 1: out[y][x][c] = s[view_start + x][y] for
+ *     y < min(r_rows, R) and x < min(frames, q_rows, R), 0 elsewhere.  EVERY element of out_dev is written.
+ * Refused (VSC_ERR_INVALID): frames < 1; an item outside sims_len; a multi-view item (q_rows > frames) with r_rows < 1 or with
+ * ragged views (q_rows % frames != 0) -- with whole views the valid height min(frames, R) is known on the host without a
+ * synchronisation.  Similarities are finite; NaN is outside the contract (it neither faults nor hangs; the chosen view is
+ * unspecified).  The item table travels in kernel arguments (128 items per pair of launches): no scratch, and the entry only
+ * enqueues on `stream` -- no host synchronisation. */
+#define VSC_MATCH_TOP_ROWS 10
+int vsc_match_maps_f32(const float *sims_dev, int64_t sims_len, const int64_t *items_host, int64_t n_items, int32_t resolution,
+                       int32_t with_transpose, int32_t *view_start_dev, float *out_dev, void *stream);
+
 /* Query view preprocessing -- the reference's image_process (VSC22-Descriptor-Track-1st/infer/src/image_preprocess.py:252-275,
  * applied to every query video by infer/src/dataset.py:82-88): the two per-video maps its border / split decisions read, and the
  * crop + resize of every view.  The decisions themselves run on the host (src/image_preprocess.py).  frames_dev: uint8

@@ -337,6 +337,9 @@ int launch_tn_align(const float *sims, int64_t sims_len, const int64_t *pairs_ho
 int launch_match_segments(const float *maps, int64_t maps_len, const int64_t *items_host, int64_t n_items, const float *thresholds,
                           const double *std_ratios, int n_thr, int max_segments, int32_t *segments, double *scores, int32_t *counts,
                           hipStream_t stream);
+// best query view + network input canvases of the matching track (match_maps.hip), contract at vsc_match_maps_f32 in include/vsc_hip.h
+int launch_match_maps(const float *sims, int64_t sims_len, const int64_t *items_host, int64_t n_items, int resolution, int with_transpose,
+                      int32_t *view_start, float *out, hipStream_t stream);
 // query view preprocessing (view_prep.hip), contracts at vsc_frame_var_u8 / vsc_canny_count_u8 / vsc_resize_bicubic_u8 in include/vsc_hip.h
 int launch_frame_var_u8(const uint8_t *frames, int64_t n, int h, int w, double *out, hipStream_t stream);
 int launch_canny_count_u8(const uint8_t *frames, int64_t n, const int32_t *idx_host, int m, int h, int w, double low, double high,

@@ -11,6 +11,9 @@ descriptor track's query pipeline (extract_query_feats.py here) -- and then, per
   3. per-candidate similarity maps -> pair classifier (2 x MobileNetV3)     (generate_candidates_classfiy_feature,
                                                                              match_classify: vsc_pair_similarity_f32, vsc_conv2d_f32 ..)
   4. surviving candidates -> refinement nets (2 x HRNet, map + transpose)   (generate_matching_feature, match_refine)
+                                                                            (--maps hip: steps 3 and 4 with the maps kept on the device --
+                                                                             vsc_match_maps_f32 picks the view and pads the network inputs;
+                                                                             the same matches csv, row for row)
   5. connected components + RANSAC at three thresholds -> matches csv       (generate_matching_result; host code as in the reference,
                                                                              or --localize hip: vsc_match_segments_f32, one launch,
                                                                              no scipy / sklearn, the maps stay on the device)
@@ -74,12 +77,16 @@ LOCALIZE_PASSES = ((MATCH_REFINE_THRESHOLD_HIGH, 0.5), (MATCH_REFINE_THRESHOLD_M
 
 
 def run(query_list, score_norm_refs, refs, sn_refs, cls_models, refine_models, query_frames=None, candidates_csv=None,
-        device="cuda", localize="host"):
+        device="cuda", localize="host", maps="host"):
     """Steps 1-5 on loaded VideoFeature lists and HIP models -> rows [query_id, ref_id, query_start, query_end, ref_start,
     ref_end, score] (the reference's output columns, :306-310).  localize="hip": step 5 on the device, the three thresholds in
-    one launch over maps that never leave it (src.matching.generate_matching_results_hip)."""
+    one launch over maps that never leave it (src.matching.generate_matching_results_hip).  maps="hip": steps 3 and 4 without a similarity
+    matrix or a network input crossing PCIe (src.matching.classify_candidates_hip / refine_candidates_hip) -- the same rows; it needs
+    query videos whose rows form whole views and raises ValueError otherwise."""
     if localize not in ("host", "hip"):
         raise ValueError(f"localize must be 'host' or 'hip', not {localize!r}")
+    if maps not in ("host", "hip"):
+        raise ValueError(f"maps must be 'host' or 'hip', not {maps!r}")
     from src import matching
     from vsc.baseline.score_normalization import normalize, query_score_normalize, transform_features
 
@@ -96,14 +103,21 @@ def run(query_list, score_norm_refs, refs, sn_refs, cls_models, refine_models, q
     query_map = {vf.video_id: vf.feature for vf in query_list}
     ref_map = {vf.video_id: vf.feature for vf in refs}
     len_map = query_len_map(query_list, query_frames)   # views share timestamps: best-view selection needs the frame count
-    cls_feature, cls_info = matching.generate_candidates_classfiy_feature(query_map, ref_map, search_res_list, len_map)   # :277-279
-    cls_rows = matching.match_classify(cls_models, cls_feature, [(q, r) for q, r, _ in cls_info], device=device)       # :280
+    if maps == "hip":
+        cls_rows = matching.classify_candidates_hip(cls_models, query_map, ref_map, search_res_list, len_map)
+    else:
+        cls_feature, cls_info = matching.generate_candidates_classfiy_feature(query_map, ref_map, search_res_list, len_map)   # :277-279
+        cls_rows = matching.match_classify(cls_models, cls_feature, [(q, r) for q, r, _ in cls_info], device=device)       # :280
     best = {}
     for q, r, p in cls_rows:                                                                      # groupby(query_id, ref_id).prob.max() (:281)
         best[q, r] = max(best.get((q, r), -1.0), p)
     candidate_score_list = [(q, r, p) for (q, r), p in sorted(best.items()) if p > MATCH_CLS_THRESHOLD]               # :283-284
-    match_meta = matching.generate_matching_feature(query_map, ref_map, len_map, candidate_score_list)                # :285-286
-    refine_res = matching.match_refine(refine_models, match_meta, device=device, device_maps=localize == "hip")      # :288
+    if maps == "hip":
+        refine_res = matching.refine_candidates_hip(refine_models, query_map, ref_map, len_map, candidate_score_list,
+                                                    device_maps=localize == "hip")
+    else:
+        match_meta = matching.generate_matching_feature(query_map, ref_map, len_map, candidate_score_list)                # :285-286
+        refine_res = matching.match_refine(refine_models, match_meta, device=device, device_maps=localize == "hip")      # :288
     found = []
     if localize == "hip":
         for rows in matching.generate_matching_results_hip(refine_res, LOCALIZE_PASSES):
@@ -130,7 +144,8 @@ def main(args):
                                                            [load_state_dict(p) for p in args.refine_models])
     rows = run(load_features(args.query_features, Dataset.QUERIES), load_features(args.norm_refs, Dataset.REFS),
                load_features(args.refs, Dataset.REFS), load_features(args.sn_refs, Dataset.REFS), cls_models, refine_models,
-               query_frames, args.candidates_csv, localize=args.localize)
+               query_frames, args.candidates_csv, localize=args.localize,
+               maps=getattr(args, "maps", "host"))   # main() is also called with namespaces built by hand, from before --maps
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     with open(args.output, "w", newline="") as f:
         w = csv.writer(f)
@@ -151,5 +166,8 @@ if __name__ == "__main__":
     ap.add_argument("--candidates_csv", default="match_candidates_score.csv")
     ap.add_argument("--localize", choices=("host", "hip"), default="host",
                     help="step 5 on the host (scipy + sklearn, as the reference) or on the device (vsc_match_segments_f32)")
+    ap.add_argument("--maps", choices=("host", "hip"), default="host",
+                    help="steps 3 and 4 feed the networks from host arrays (as the reference) or from maps that stay on the device "
+                         "(vsc_match_maps_f32; same csv)")
     ap.add_argument("--output", required=True)
     main(ap.parse_args())

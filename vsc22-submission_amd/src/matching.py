@@ -18,6 +18,11 @@ view, once for the map).  Here every candidate of a call goes through ONE ``vsc_
 over concatenated frame banks; each score is an independent ascending-k fp32 chain, so the map of the chosen
 view is a row slice of the full product -- bit for bit -- and nothing is multiplied twice.
 
+``classify_candidates_hip`` / ``refine_candidates_hip`` (``infer_matching.py --maps hip``) are the same two steps with the
+matrices left where the launch wrote them: ``vsc_match_maps_f32`` picks each candidate's query view and writes the cropped,
+zero-padded, 3-channel network inputs on the device -- the same bits as ``_best_view`` + the two datasets below -- so neither
+a similarity matrix nor a network input crosses PCIe.
+
 ``generate_matching_result`` (utils.py:80-116) -- post-processing of the refinement networks' probability maps, cv2
 connected components + sklearn RANSAC in the reference -- has two backends.  ``"host"`` (the default) mirrors it as host
 code with ``scipy.ndimage.label`` in cv2's place (cv2 is not a dependency here).  ``"hip"`` runs it on the device
@@ -300,6 +305,116 @@ def match_refine(refine_models, match_meta, batch_size: int = MATCH_REFINE_BATCH
             res_list.append([qid, rid, pred[i][1][:h, :w], fea[0][:h, :w]])
     if device_maps:
         flat = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device=device)
+        return DeviceProbabilityMaps(ids, np.array(table, dtype=np.int64).reshape(-1, 3), flat)
+    return res_list
+
+
+# ---- steps 3 and 4 with the maps kept on the device (infer_matching.py --maps hip) ------------------------------
+MATCH_MAPS_FLOAT_BUDGET = 1 << 28   # similarities (fp32 values) of one vsc_pair_similarity_f32 + vsc_match_maps_f32 call: 1 GiB
+MATCH_REFINE_GROUP = 64             # refinement batches whose canvases are built by one call (224 x 224 x 3 floats per candidate)
+
+
+def _map_shape(query, ref, candidate, len_map, resolution: int):
+    """(similarity rows, columns, frames per view) the canvas of one candidate needs.  A multi-view candidate needs every row
+    and every column (the view is chosen over all of them); a single-view one only the corner the canvas shows -- any slice of a
+    larger product is the same bits (vsc_pair_similarity_f32)."""
+    qid, rid = candidate[0], candidate[1]
+    q_rows, r_rows, frames = len(query[qid]), len(ref[rid]), int(len_map[qid])
+    if frames < 1:
+        raise ValueError(f"{qid}: {frames} frames per view")
+    if q_rows > frames:
+        if q_rows % frames:
+            raise ValueError(f"{qid}: {q_rows} descriptors are not whole views of {frames} frames -- the device path needs whole "
+                             "views (vsc_match_maps_f32); run with --maps host")
+        return q_rows, r_rows, frames
+    return min(q_rows, resolution), min(r_rows, resolution), frames
+
+
+def _device_canvases(query, ref, candidates, len_map, resolution: int, with_transpose: bool):
+    """Network inputs of a candidate list, built on the device: -> (float32 device tensor [n * (1 + with_transpose), 3, R, R],
+    channels last in memory -- the chosen view's map of every candidate and, with the transpose, its transposed map right behind
+    it --, [(valid height, valid width)] per candidate).  _Banks -> vsc_pair_similarity_f32 -> vsc_match_maps_f32, in as many
+    calls as MATCH_MAPS_FLOAT_BUDGET asks for; nothing is copied back and nothing waits for the device."""
+    shapes = [_map_shape(query, ref, c, len_map, resolution) for c in candidates]   # raises for ragged views: before any device work
+    import torch
+
+    from vsc_hip import _lib, ops
+    _lib.require_device()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    n, slices = len(candidates), 2 if with_transpose else 1
+    out = torch.empty((n * slices, resolution, resolution, 3), dtype=torch.float32, device=dev)   # every element is written
+    lo = 0
+    while lo < n:
+        hi, floats = lo, 0
+        while hi < n and (hi == lo or floats + shapes[hi][0] * shapes[hi][1] <= MATCH_MAPS_FLOAT_BUDGET):
+            floats += shapes[hi][0] * shapes[hi][1]
+            hi += 1
+        banks = _Banks(query, ref, candidates[lo:hi])
+        pairs = banks.pairs.copy()
+        pairs[:, 1] = [s[0] for s in shapes[lo:hi]]
+        pairs[:, 3] = [s[1] for s in shapes[lo:hi]]
+        items = np.zeros((hi - lo, 4), dtype=np.int64)
+        if floats:
+            flat, off = ops.pair_similarity(torch.from_numpy(banks.q_bank).to(dev), torch.from_numpy(banks.r_bank).to(dev), pairs)
+            items[:, 0] = off[:-1]
+        else:                                  # only empty matrices: all-zero canvases
+            flat = torch.empty(0, dtype=torch.float32, device=dev)
+        items[:, 1], items[:, 2], items[:, 3] = pairs[:, 1], pairs[:, 3], [s[2] for s in shapes[lo:hi]]
+        ops.match_maps(flat, items, resolution, with_transpose, out=out[lo * slices:hi * slices])
+        lo = hi
+    hw = [(min(f, q, resolution), min(r, resolution)) for q, r, f in shapes]
+    return out.permute(0, 3, 1, 2), hw
+
+
+def classify_candidates_hip(cls_models, query, ref, candidate_list, len_map, batch_size: int = MATCH_CLS_BATCH):
+    """generate_candidates_classfiy_feature + match_classify without a similarity matrix or a network input crossing PCIe:
+    -> the same [(query_id, ref_id, prob), ...], two rows per candidate (its map, then the transposed map).  Works in groups of
+    batch_size // 2 candidates, so every network batch holds exactly the items of the host path's batch; only the
+    probabilities are copied back.  Raises ValueError for a query whose rows are not whole views (ragged --query_frames)."""
+    from vsc_hip import cnn
+    assert batch_size >= 2 and batch_size % 2 == 0, "a candidate's map and its transpose share a batch"
+    candidate_list = list(candidate_list)
+    out = []
+    for lo in range(0, len(candidate_list), batch_size // 2):
+        group = candidate_list[lo:lo + batch_size // 2]
+        feature, _ = _device_canvases(query, ref, group, len_map, MATCH_CLS_RESOLUTION[0], True)
+        prob = cnn.match_classify_probability(cls_models, feature).cpu().numpy()
+        for i, (qid, rid, _) in enumerate(group):
+            out.append((qid, rid, float(prob[2 * i])))
+            out.append((qid, rid, float(prob[2 * i + 1])))
+    return out
+
+
+def refine_candidates_hip(refine_models, query, ref, len_map, candidate_score_list, device_maps: bool = False,
+                          batch_size: int = MATCH_REFINE_BATCH):
+    """generate_matching_feature + match_refine with the (query view, reference) maps chosen, cropped and padded on the device:
+    -> match_refine's rows [[qid, rid, probability map [h, w], similarity map [h, w]], ...] (the similarity map is the canvas's
+    crop, copied back), or with ``device_maps=True`` its DeviceProbabilityMaps -- then only the table is host data.  The network
+    batches are those of match_refine."""
+    import torch
+
+    from vsc_hip import cnn
+    candidate_score_list = list(candidate_score_list)
+    res_list, ids, table, parts, offset = [], [], [], [], 0
+    group = batch_size * MATCH_REFINE_GROUP
+    for glo in range(0, len(candidate_score_list), group):
+        cands = candidate_score_list[glo:glo + group]
+        canvas, hw = _device_canvases(query, ref, cands, len_map, MATCH_REFINE_RESOLUTION[0], False)
+        for lo in range(0, len(cands), batch_size):
+            feature = canvas[lo:lo + batch_size]
+            pred = cnn.match_refine_probability(refine_models, feature)
+            if device_maps:
+                for i, ((qid, rid, _), (h, w)) in enumerate(zip(cands[lo:lo + batch_size], hw[lo:])):
+                    parts.append(pred[i, 1, :h, :w].reshape(-1))
+                    ids.append((qid, rid))
+                    table.append((offset, h, w))
+                    offset += h * w
+                continue
+            pred, sims = pred.cpu().numpy(), feature[:, 0].contiguous().cpu().numpy()
+            for i, ((qid, rid, _), (h, w)) in enumerate(zip(cands[lo:lo + batch_size], hw[lo:])):
+                res_list.append([qid, rid, pred[i][1][:h, :w], sims[i][:h, :w]])
+    if device_maps:
+        flat = torch.cat(parts) if parts else torch.empty(0, dtype=torch.float32, device="cuda")
         return DeviceProbabilityMaps(ids, np.array(table, dtype=np.int64).reshape(-1, 3), flat)
     return res_list
 

@@ -104,6 +104,7 @@ SIGNATURES = {
                                    ctypes.c_double, c_int32, ctypes.c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_match_segments_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
                                          c_void_p, c_void_p]),
+    "vsc_match_maps_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "vsc_pca_fit_create": (c_int32, [c_int32, POINTER(c_void_p)]),
     "vsc_pca_fit_update_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
     "vsc_pca_fit_moments_f64": (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),

@@ -365,6 +365,29 @@ def match_segments_once(maps, items, thr, ratio, max_segments: int, lib=None):
     return segments, scores, counts
 
 
+def match_maps(sims, items, resolution: int, with_transpose: bool, out=None):
+    """Best query view + padded 3-channel network inputs of every matrix of a flat fp32 device tensor, without a host
+    synchronisation.  sims: flat float32 device tensor (ops.pair_similarity's); items: int64 [n, 4] rows (element offset, q_rows,
+    r_rows, frames per view) on the host.  -> (maps [n * (1 + with_transpose), 3, R, R] float32 on the device -- a permuted view
+    of the channels-last buffer the kernel writes, i.e. what the networks' NHWC conversion takes without a copy; with the
+    transpose the order is map, transposed map, map, ... --, view_start int32 [n] on the device).  `out`: a contiguous
+    [n * (1 + with_transpose), R, R, 3] float32 device tensor to write into (default: a new one; every element is written).
+    Contract and refusals: vsc_match_maps_f32 in include/vsc_hip.h."""
+    import numpy as np
+    lib = _rd()
+    sims = _dev(sims, torch.float32).reshape(-1)
+    items = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1, 4))
+    n, r, slices = items.shape[0], int(resolution), 2 if with_transpose else 1
+    if out is None:
+        out = torch.empty((n * slices, max(r, 0), max(r, 0), 3), dtype=torch.float32, device=sims.device)
+    assert out.is_cuda and out.dtype == torch.float32 and out.is_contiguous() and tuple(out.shape) == (n * slices, r, r, 3), \
+        "out must be a contiguous float32 [n * (1 + with_transpose), R, R, 3] device tensor"
+    view_start = torch.empty(n, dtype=torch.int32, device=sims.device)
+    check(lib.vsc_match_maps_f32(ptr(sims) if sims.numel() else None, sims.numel(), items.ctypes.data, n, r, int(bool(with_transpose)),
+                                 ptr(view_start) if n else None, ptr(out) if out.numel() else None, current_stream()))
+    return out.permute(0, 3, 1, 2), view_start
+
+
 def _frames_u8(frames):
     assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3, \
         "frames must be uint8 [n, H, W, 3] on the GPU"
