@@ -11,6 +11,14 @@
  * consecutive calls that share a handle or that scratch must be stream-ordered (same stream, or
  * ordered by events).  Different encoder handles are independent.
  *
+ * Alignment: a device pointer is aligned to its element type unless its entry says "Alignment:" -- there the kernels read or write
+ * the tensor 8 or 16 bytes at a time (dwordx4 accesses, LDS-DMA pieces), and a pointer less aligned than that is refused with
+ * VSC_ERR_INVALID before anything is launched (the message names the argument).  Row-major operands have no leading dimension of
+ * their own: with an aligned base their rows are aligned by the shape rules the entry already states (K % 64, N % 4, width % 4).
+ * Offsets that an entry takes as ARGUMENTS are legal at any element: the element offsets of vsc_tn_align_f32,
+ * vsc_match_segments_f32 and vsc_match_maps_f32, the row0 of vsc_pair_similarity_f32, the ld of vsc_pca_fit_update_f32.
+ * Everything an allocator hands out (hipMalloc: 256 bytes, torch: 512) satisfies every requirement below.
+ *
  * Each entry point names the reference interface it replaces
  * (paths relative to /root/reference/VSC22-Descriptor-Track-1st).
  */
@@ -101,7 +109,8 @@ int vsc_encoder_finalize(vsc_encoder *enc);
 
 /* frames_dev: float32 [n, channels, image, image], already normalised as
  * infer/src/transform.py does.  desc_dev: float32 [n, desc_dim] where desc_dim =
- * out_dim ? out_dim : width.  Asynchronous on `stream`. */
+ * out_dim ? out_dim : width.  Asynchronous on `stream`.
+ * Alignment: frames_dev 16 bytes (the patch gather reads float4). */
 int vsc_encoder_forward(vsc_encoder *enc, const float *frames_dev, int64_t n, float *desc_dev,
                         void *stream);
 /* The same from DECODED frames: frames_u8_dev uint8 [n, image, image, channels] (PIL / numpy layout); torchvision's
@@ -111,7 +120,7 @@ int vsc_encoder_forward(vsc_encoder *enc, const float *frames_dev, int64_t n, fl
 int vsc_encoder_forward_u8(vsc_encoder *enc, const uint8_t *frames_u8_dev, int64_t n, const float *mean,
                            const float *std, float *desc_dev, void *stream);
 /* Same, but also copies the last hidden state (after the final LayerNorm),
- * float32 [n, tokens, width], for parity tests.  tokens_dev may be NULL. */
+ * float32 [n, tokens, width], for parity tests.  tokens_dev may be NULL.  Alignment: frames_dev and tokens_dev 16 bytes. */
 int vsc_encoder_forward_debug(vsc_encoder *enc, const float *frames_dev, int64_t n,
                               float *desc_dev, float *tokens_dev, void *stream);
 int64_t vsc_encoder_workspace_bytes(const vsc_encoder *enc);
@@ -153,7 +162,8 @@ int vsc_swin_create(const vsc_swin_config *cfg, vsc_swin **out);
 void vsc_swin_destroy(vsc_swin *enc);
 int vsc_swin_set_weight(vsc_swin *enc, const char *name, const float *host, size_t count);
 int vsc_swin_finalize(vsc_swin *enc);
-/* frames_dev f32 [n, channels, image, image] -> desc_dev f32 [n, out_dim]; asynchronous on `stream`. */
+/* frames_dev f32 [n, channels, image, image] -> desc_dev f32 [n, out_dim]; asynchronous on `stream`.  Alignment: frames_dev 16 bytes
+ * (and tokens_dev of vsc_swin_forward_debug). */
 int vsc_swin_forward(vsc_swin *enc, const float *frames_dev, int64_t n, float *desc_dev, void *stream);
 /* uint8 [n, image, image, channels] input, normalisation fused as in vsc_encoder_forward_u8 */
 int vsc_swin_forward_u8(vsc_swin *enc, const uint8_t *frames_u8_dev, int64_t n, const float *mean, const float *std,
@@ -193,7 +203,10 @@ int vsc_swin_get_profile(vsc_swin *enc, double ms_out[VSC_SWIN_PROF_CLASSES], in
  * results: ~7 GB after a 1M x 1M call); vsc_search_release_scratch() returns it.  One search call per device at a time.
  * Host synchronisation: on the bf16 pre-filter path (nq * nr >= 2^24, nr >= 4096, k <= 512) the call waits for `stream`
  * once, after the merge, to read the per-block fallback flags -- on return the results are complete; on the exact path
- * (everything smaller) the call only enqueues. */
+ * (everything smaller) the call only enqueues.
+ * Alignment: q_dev, r_dev and the outputs at their element type -- except rows narrower than 32 floats whose width is a multiple of 4
+ * (d = 4, 8, .. 28): r_dev 16 bytes (the pre-filter path's re-scoring reads such rows as float4).  The same holds for
+ * vsc_knn_ip_floor_f32, vsc_range_search_ip_f32 and vsc_video_pair_max_f32. */
 int vsc_knn_ip_f32(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d,
                    int32_t k, int64_t ref_id_offset, float *out_scores_dev,
                    int64_t *out_ids_dev, void *stream);
@@ -501,7 +514,8 @@ typedef enum vsc_epilogue {
 
 /* out[M,N] = epi(A[M,K] . W[N,K]^T + bias[N]);  A, W bf16 row-major, K % 64 == 0,
  * N % 4 == 0.  bias may be NULL.  `aux_dev` = residual (RESADD) or pos (PATCH),
- * `tokens` = T for PATCH. */
+ * `tokens` = T for PATCH.  Alignment: a_dev, w_dev, bias_dev, aux_dev and out_dev 16 bytes (operands by LDS-DMA in 16-byte pieces,
+ * every other access a dwordx4). */
 int vsc_gemm_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *bias_dev,
                   const float *aux_dev, void *out_dev, int64_t m, int32_t n, int32_t k,
                   int32_t epilogue, int32_t tokens, void *stream);
@@ -510,7 +524,8 @@ int vsc_gemm_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *bia
  * the residual GEMM of a transformer block and the LayerNorm behind it.  Where the persistent 256 x 256 kernel has that form
  * (N = 768, whole row blocks per XCD: ceil(M / 256) % 8 == 0, more tiles than CUs) AND the switch VSC_GEMM_LN_TAIL is 1, this
  * is ONE launch whose workgroups normalise every finished 256-row block as a tail; otherwise vsc_gemm_bf16(RESADD) followed by
- * vsc_layernorm_f32.  The same bits either way.  Launches on one stream share a workspace kept by the library. */
+ * vsc_layernorm_f32.  The same bits either way.  Launches on one stream share a workspace kept by the library.
+ * Alignment: y_out_dev 8 bytes, every other pointer 16. */
 int vsc_gemm_resadd_ln_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *bias_dev, float *x_inout_dev,
                             const float *gamma_dev, const float *beta_dev, uint16_t *y_out_dev, int64_t m, int32_t n, int32_t k,
                             float eps, void *stream);
@@ -519,18 +534,19 @@ int vsc_gemm_resadd_ln_last_path(void);
 
 /* qkv_dev bf16 [frames*tokens, 3*width] (q | k | v column blocks, head-major inside
  * each) -> out_dev bf16 [frames*tokens, width]; softmax(q k^T / 8) v per head;
- * head_dim 64. */
+ * head_dim 64.  Alignment: qkv_dev and out_dev 16 bytes. */
 int vsc_attention_bf16(const uint16_t *qkv_dev, uint16_t *out_dev, int32_t frames, int32_t tokens,
                        int32_t heads, void *stream);
 
 /* Row LayerNorm over `width` of float32 x [rows,width]; out is bf16 (out_f32 = 0)
- * or float32 (out_f32 = 1; may alias x). */
+ * or float32 (out_f32 = 1; may alias x).  Alignment: x_dev, gamma_dev, beta_dev 16 bytes; out_dev 16 (float32) or 8 (bf16). */
 int vsc_layernorm_f32(const float *x_dev, const float *gamma_dev, const float *beta_dev,
                       void *out_dev, int64_t rows, int32_t width, float eps, int32_t out_f32,
                       void *stream);
 
 /* frames float32 [n,C,H,W] -> patches bf16 [n*grid*grid, kpad], k = c*p*p + py*p + px,
- * zero-filled up to kpad (kpad % 64 == 0). */
+ * zero-filled up to kpad (kpad % 64 == 0).  Alignment: patches_dev 16 bytes; frames_dev 16 when patch % 8 == 0 (other patch sizes are
+ * gathered pixel by pixel). */
 int vsc_patchify_bf16(const float *frames_dev, uint16_t *patches_dev, int64_t n, int32_t channels,
                       int32_t image, int32_t patch, int32_t kpad, void *stream);
 
@@ -543,17 +559,20 @@ int vsc_patchify_bf16(const float *frames_dev, uint16_t *patches_dev, int64_t n,
  * Bounded form (optional, per head): cosine logits cannot exceed U = scale + max(table).  A caller that has subtracted U from a
  * head's table and knows 2 scale + max(table) - min(table) <= 69 (so that no probability underflows) passes -scale for that
  * head: the kernel then skips the row maximum of the softmax -- the same quotient, a sixth fewer vector instructions
- * (vsc_swin_finalize does this for its own tables). */
+ * (vsc_swin_finalize does this for its own tables).
+ * Alignment: qkv_dev and out_dev 16 bytes (bias_dev and scale_dev are read element by element). */
 int vsc_window_attention_bf16(const uint16_t *qkv_dev, uint16_t *out_dev, const float *bias_dev,
                               const float *scale_dev, int32_t frames, int32_t res, int32_t window,
                               int32_t shift, int32_t heads, void *stream);
-/* x_out = (x_in ? x_in : 0) + LayerNorm(t) ; xb = bf16(x_out).  x_in may be NULL or alias x_out. */
+/* x_out = (x_in ? x_in : 0) + LayerNorm(t) ; xb = bf16(x_out).  x_in may be NULL or alias x_out.
+ * Alignment: xb_dev 8 bytes, every other pointer 16. */
 int vsc_ln_residual_f32(const float *t_dev, const float *gamma_dev, const float *beta_dev,
                         const float *x_in_dev, float *x_out_dev, uint16_t *xb_dev, int64_t rows,
                         int32_t width, float eps, void *stream);
 /* The same update with the LayerNorm input produced in place by a GEMM whose tile owns whole rows:
  * x_out = (x_in ? x_in : 0) + LayerNorm(A[m,k] W[n,k]^T + bias) ; xb = bf16(x_out).  n in {128, 256, 512},
- * k % 32 == 0 (torch2scripts.py:297-300, 361-362: Swin-V2 res-post-norm and the PatchMerging norm). */
+ * k % 32 == 0 (torch2scripts.py:297-300, 361-362: Swin-V2 res-post-norm and the PatchMerging norm).
+ * Alignment: xb_dev 8 bytes, every other pointer 16. */
 int vsc_gemm_ln_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *bias_dev,
                      const float *gamma_dev, const float *beta_dev, const float *x_in_dev,
                      float *x_out_dev, uint16_t *xb_dev, int64_t m, int32_t n, int32_t k, float eps,
@@ -564,7 +583,9 @@ int vsc_gemm_ln_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *
  * [m, 4c] never reach memory.  w2p_dev is fc2.weight in the kernel's contraction order, as made by
  * vsc_swin_mlp_permute_hidden_f32 (host arrays of c * 4c floats, once per model load) and then converted to bf16: for
  * c = 128 / 256 the hidden axis of every row reordered inside its 32-blocks, for c = 512 additionally chunk-major
- * [64 chunks][512][32] (one wave per SIMD with the whole register file: csrc/swin_mlp512.hip; m < 2^21 rows per call). */
+ * [64 chunks][512][32] (one wave per SIMD with the whole register file: csrc/swin_mlp512.hip; m < 2^21 rows per call).
+ * Alignment (all three fused entries): the bf16 weight matrices, att_dev, x_dev, xb_dev and qkv_next_dev 16 bytes; the bias and
+ * LayerNorm vectors are read element by element. */
 int vsc_swin_mlp_bf16(const uint16_t *w1_dev, const float *b1_dev, const uint16_t *w2p_dev, const float *b2_dev,
                       const float *gamma_dev, const float *beta_dev, float *x_dev, uint16_t *xb_dev, int64_t m, int32_t c,
                       float eps, void *stream);
@@ -585,7 +606,7 @@ int vsc_swin_proj_mlp_qkv_bf16(const uint16_t *att_dev, const uint16_t *wp_dev, 
                                const uint16_t *w1_dev, const float *b1_dev, const uint16_t *w2p_dev, const float *b2_dev, const float *gamma2_dev,
                                const float *beta2_dev, const uint16_t *wq_dev, const float *bq_dev, float *x_dev, uint16_t *qkv_next_dev,
                                int64_t m, int32_t c, float eps, void *stream);
-/* PatchMerging gather on bf16 tokens [frames, res, res, c] -> [frames*(res/2)^2, 4c] */
+/* PatchMerging gather on bf16 tokens [frames, res, res, c] -> [frames*(res/2)^2, 4c].  Alignment: both pointers 16 bytes. */
 int vsc_merge_gather_bf16(const uint16_t *xb_dev, uint16_t *out_dev, int64_t frames, int32_t res,
                           int32_t c, void *stream);
 

@@ -123,22 +123,36 @@ int vsc_allow_dynamic_lds_ptr(const void *kernel, int bytes) {
 extern "C" int vsc_gemm_bf16(const uint16_t *a, const uint16_t *w, const float *bias, const float *aux,
                              void *out, int64_t m, int32_t n, int32_t k, int32_t epilogue,
                              int32_t tokens, void *stream) {
+    // operands by LDS-DMA in 16-byte pieces; bias, residual / pos and both output types in 16-byte accesses
+    VSC_REQUIRE_ALIGNED("gemm", a, 16);
+    VSC_REQUIRE_ALIGNED("gemm", w, 16);
+    VSC_REQUIRE_ALIGNED("gemm", bias, 16);
+    VSC_REQUIRE_ALIGNED("gemm", aux, 16);
+    VSC_REQUIRE_ALIGNED("gemm", out, 16);
     return launch_gemm_bf16(a, w, bias, aux, out, m, n, k, epilogue, tokens, (hipStream_t)stream);
 }
 
 extern "C" int vsc_attention_bf16(const uint16_t *qkv, uint16_t *out, int32_t frames, int32_t tokens,
                                   int32_t heads, void *stream) {
+    VSC_REQUIRE_ALIGNED("attention", qkv, 16);
+    VSC_REQUIRE_ALIGNED("attention", out, 16);
     return launch_attention_bf16(qkv, out, frames, tokens, heads, (hipStream_t)stream);
 }
 
 extern "C" int vsc_layernorm_f32(const float *x, const float *g, const float *b, void *out,
                                  int64_t rows, int32_t width, float eps, int32_t out_f32,
                                  void *stream) {
+    VSC_REQUIRE_ALIGNED("layernorm", x, 16);
+    VSC_REQUIRE_ALIGNED("layernorm", g, 16);
+    VSC_REQUIRE_ALIGNED("layernorm", b, 16);
+    VSC_REQUIRE_ALIGNED("layernorm", out, out_f32 ? 16 : 8);   // float4 stores; four 16-bit values at a time
     return launch_layernorm(x, g, b, out, rows, width, eps, out_f32, (hipStream_t)stream);
 }
 
 extern "C" int vsc_patchify_bf16(const float *frames, uint16_t *patches, int64_t n, int32_t channels,
                                  int32_t image, int32_t patch, int32_t kpad, void *stream) {
+    if (patch % 8 == 0) VSC_REQUIRE_ALIGNED("patchify", frames, 16);   // eight pixels of a patch row as two float4 (other patch sizes gather)
+    VSC_REQUIRE_ALIGNED("patchify", patches, 16);
     return launch_patchify(frames, patches, n, channels, image, patch, kpad, (hipStream_t)stream);
 }
 
@@ -149,34 +163,68 @@ extern "C" int vsc_l2_normalize_f32(float *x, int64_t n, int32_t d, void *stream
 extern "C" int vsc_window_attention_bf16(const uint16_t *qkv, uint16_t *out, const float *bias, const float *scale,
                                          int32_t frames, int32_t res, int32_t window, int32_t shift,
                                          int32_t heads, void *stream) {
+    VSC_REQUIRE_ALIGNED("window_attention", qkv, 16);
+    VSC_REQUIRE_ALIGNED("window_attention", out, 16);
     return launch_window_attention(qkv, out, bias, scale, frames, res, window, shift, heads, (hipStream_t)stream);
 }
 
 extern "C" int vsc_ln_residual_f32(const float *t, const float *g, const float *b, const float *x_in, float *x_out,
                                    uint16_t *xb, int64_t rows, int32_t width, float eps, void *stream) {
+    VSC_REQUIRE_ALIGNED("ln_residual", t, 16);
+    VSC_REQUIRE_ALIGNED("ln_residual", g, 16);
+    VSC_REQUIRE_ALIGNED("ln_residual", b, 16);
+    VSC_REQUIRE_ALIGNED("ln_residual", x_in, 16);
+    VSC_REQUIRE_ALIGNED("ln_residual", x_out, 16);
+    VSC_REQUIRE_ALIGNED("ln_residual", xb, 8);
     return launch_ln_residual(t, g, b, x_in, x_out, xb, rows, width, eps, (hipStream_t)stream);
 }
 
 extern "C" int vsc_gemm_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias, const float *g, const float *b,
                                 const float *x_in, float *x_out, uint16_t *xb, int64_t m, int32_t n, int32_t k,
                                 float eps, void *stream) {
+    VSC_REQUIRE_ALIGNED("gemm_ln", a, 16);
+    VSC_REQUIRE_ALIGNED("gemm_ln", w, 16);
+    VSC_REQUIRE_ALIGNED("gemm_ln", bias, 16);
+    VSC_REQUIRE_ALIGNED("gemm_ln", g, 16);
+    VSC_REQUIRE_ALIGNED("gemm_ln", b, 16);
+    VSC_REQUIRE_ALIGNED("gemm_ln", x_in, 16);
+    VSC_REQUIRE_ALIGNED("gemm_ln", x_out, 16);
+    VSC_REQUIRE_ALIGNED("gemm_ln", xb, 8);
     return launch_gemm_ln_bf16(a, w, bias, g, b, x_in, x_out, xb, m, n, k, eps, (hipStream_t)stream);
 }
 
 extern "C" int vsc_swin_mlp_bf16(const uint16_t *w1, const float *b1, const uint16_t *w2p, const float *b2, const float *g, const float *b,
                                  float *x, uint16_t *xb, int64_t m, int32_t c, float eps, void *stream) {
+    // weights by LDS-DMA, x as float4, the shadow eight values at a time; the bias / gain vectors are read element by element
+    VSC_REQUIRE_ALIGNED("swin_mlp", w1, 16);
+    VSC_REQUIRE_ALIGNED("swin_mlp", w2p, 16);
+    VSC_REQUIRE_ALIGNED("swin_mlp", x, 16);
+    VSC_REQUIRE_ALIGNED("swin_mlp", xb, 16);
     return launch_swin_mlp(w1, b1, w2p, b2, g, b, x, xb, m, c, eps, (hipStream_t)stream);
 }
 
 extern "C" int vsc_swin_proj_mlp_bf16(const uint16_t *att, const uint16_t *wp, const float *bp, const float *g1, const float *be1, const uint16_t *w1,
                                       const float *b1, const uint16_t *w2p, const float *b2, const float *g2, const float *be2, float *x, uint16_t *xb,
                                       int64_t m, int32_t c, float eps, void *stream) {
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp", att, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp", wp, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp", w1, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp", w2p, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp", x, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp", xb, 16);
     return launch_swin_proj_mlp(att, wp, bp, g1, be1, w1, b1, w2p, b2, g2, be2, x, xb, m, c, eps, (hipStream_t)stream);
 }
 
 extern "C" int vsc_swin_proj_mlp_qkv_bf16(const uint16_t *att, const uint16_t *wp, const float *bp, const float *g1, const float *be1, const uint16_t *w1,
                                           const float *b1, const uint16_t *w2p, const float *b2, const float *g2, const float *be2, const uint16_t *wq,
                                           const float *bq, float *x, uint16_t *qkv_next, int64_t m, int32_t c, float eps, void *stream) {
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp_qkv", att, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp_qkv", wp, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp_qkv", w1, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp_qkv", w2p, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp_qkv", wq, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp_qkv", x, 16);
+    VSC_REQUIRE_ALIGNED("swin_proj_mlp_qkv", qkv_next, 16);
     VSC_REQUIRE(c == 512, "swin_proj_mlp_qkv: width %d unsupported (512)", c);
     return launch_swin_proj_mlp_qkv512(att, wp, bp, g1, be1, w1, b1, w2p, b2, g2, be2, wq, bq, x, qkv_next, m, eps, (hipStream_t)stream);
 }
@@ -223,6 +271,8 @@ extern "C" int vsc_resize_bicubic_u8(const uint8_t *frames_dev, int64_t n, int32
 
 extern "C" int vsc_merge_gather_bf16(const uint16_t *xb, uint16_t *out, int64_t frames, int32_t res, int32_t c,
                                      void *stream) {
+    VSC_REQUIRE_ALIGNED("merge_gather", xb, 16);
+    VSC_REQUIRE_ALIGNED("merge_gather", out, 16);
     return launch_merge_gather(xb, out, frames, res, c, (hipStream_t)stream);
 }
 

@@ -37,6 +37,13 @@ void vsc_set_error(const char *fmt, ...);
 
 #define VSC_CHECK_LAUNCH() VSC_CHECK_HIP(hipGetLastError())
 
+// Alignment of a caller's pointer at the C ABI (include/vsc_hip.h states it per entry): the kernels read and write it `bytes` at a
+// time -- dwordx4 loads and stores, LDS-DMA pieces -- and nothing is launched on a pointer less aligned than that.  A null
+// pointer (an optional operand) passes.  Used by the extern "C" wrappers only: the encoders' own launches go straight to launch_*.
+#define VSC_REQUIRE_ALIGNED(what, ptr, bytes)                                                                     \
+    VSC_REQUIRE((((uintptr_t)(ptr)) & ((uintptr_t)(bytes) - 1)) == 0, what ": %s must be %d-byte aligned (it is %p)", \
+                #ptr, (int)(bytes), (const void *)(ptr))
+
 // a call that has already reported its own error: pass its return code on
 #define VSC_TRY(expr)                     \
     do {                                  \

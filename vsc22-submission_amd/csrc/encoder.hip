@@ -376,6 +376,8 @@ static int encoder_forward_impl(vsc_encoder *e, const float *frames, const uint8
 extern "C" int vsc_encoder_forward_debug(vsc_encoder *e, const float *frames, int64_t n, float *desc,
                                          float *tokens_out, void *stream) {
     VSC_REQUIRE(frames, "forward: null frames");
+    VSC_REQUIRE_ALIGNED("forward", frames, 16);       // the patch gather reads eight pixels of a row as two float4
+    VSC_REQUIRE_ALIGNED("forward", tokens_out, 16);   // the final LayerNorm stores the hidden state as float4
     return encoder_forward_impl(e, frames, nullptr, nullptr, nullptr, n, desc, tokens_out, stream);
 }
 

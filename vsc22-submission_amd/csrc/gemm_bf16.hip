@@ -1952,6 +1952,13 @@ extern "C" int vsc_gemm_resadd_ln_bf16(const uint16_t *a, const uint16_t *w, con
     static std::mutex mu;
     static std::map<std::pair<int, void *>, std::pair<unsigned *, size_t>> spaces;
     VSC_REQUIRE(m > 0, "gemm_resadd_ln: empty problem");
+    VSC_REQUIRE_ALIGNED("gemm_resadd_ln", a, 16);
+    VSC_REQUIRE_ALIGNED("gemm_resadd_ln", w, 16);
+    VSC_REQUIRE_ALIGNED("gemm_resadd_ln", bias, 16);
+    VSC_REQUIRE_ALIGNED("gemm_resadd_ln", x_inout, 16);
+    VSC_REQUIRE_ALIGNED("gemm_resadd_ln", gamma, 16);
+    VSC_REQUIRE_ALIGNED("gemm_resadd_ln", beta, 16);
+    VSC_REQUIRE_ALIGNED("gemm_resadd_ln", y_out, 8);
     int dev = 0;
     VSC_CHECK_HIP(hipGetDevice(&dev));
     const size_t need = gemm_ln_tail_ws_bytes(m);

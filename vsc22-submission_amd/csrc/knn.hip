@@ -1834,6 +1834,7 @@ __global__ __launch_bounds__(256) void knn_floor_kernel(const float *__restrict_
 static int knn_ip_impl(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k, int64_t ref_id_offset,
                        const float *floor_dev, float *out_scores_dev, int64_t *out_ids_dev, hipStream_t stream) {
     VSC_REQUIRE(q_dev && r_dev && out_scores_dev && out_ids_dev, "knn: null pointer");
+    if (d < 32 && (d & 3) == 0) VSC_REQUIRE_ALIGNED("knn", r_dev, 16);   // knn_rescore_kernel (pre-filter path) reads such rows as float4
     VSC_REQUIRE(nq > 0 && nr > 0, "knn: empty query or reference set (nq=%lld nr=%lld)", (long long)nq,
                 (long long)nr);
     VSC_REQUIRE(d > 0 && d <= 4096, "knn: dimension %d unsupported", d);
@@ -1963,6 +1964,7 @@ extern "C" int vsc_range_search_ip_f32(const float *q_dev, int64_t nq, const flo
     VSC_REQUIRE(q_dev && r_dev && lims_dev && total_out, "range_search: null pointer");
     VSC_REQUIRE(nq > 0 && nr > 0, "range_search: empty query or reference set");
     VSC_REQUIRE(d > 0 && d <= 4096, "range_search: dimension %d unsupported", d);
+    if (d < 32 && (d & 3) == 0) VSC_REQUIRE_ALIGNED("range_search", r_dev, 16);   // knn_rescore_kernel (pre-filter path) reads such rows as float4
     VSC_REQUIRE(capacity >= 0 && (capacity == 0 || (out_scores_dev && out_ids_dev)),
                 "range_search: capacity %lld without output buffers", (long long)capacity);
     g_range_last_path = 1;
@@ -2087,6 +2089,7 @@ extern "C" int vsc_video_pair_max_f32(const float *q_dev, int64_t nq, const int3
     VSC_REQUIRE(nq > 0 && nr > 0, "video_pair_max: empty query or reference set");
     VSC_REQUIRE(n_q_videos > 0 && n_r_videos > 0, "video_pair_max: no videos (%d x %d)", n_q_videos, n_r_videos);
     VSC_REQUIRE(d > 0 && d <= 4096, "video_pair_max: dimension %d unsupported", d);
+    if (d < 32 && (d & 3) == 0) VSC_REQUIRE_ALIGNED("video_pair_max", r_dev, 16);   // knn_rescore_kernel (pre-filter path) reads such rows as float4
     VSC_REQUIRE(capacity >= 0 && (capacity == 0 || (out_rvideo_dev && out_score_dev)),
                 "video_pair_max: capacity %lld without output buffers", (long long)capacity);
     const size_t table_bytes = (size_t)n_q_videos * n_r_videos * 4;

@@ -441,6 +441,8 @@ extern "C" int vsc_swin_get_profile(vsc_swin *e, double *ms_out, int64_t *launch
 extern "C" int vsc_swin_forward_debug(vsc_swin *e, const float *frames, int64_t n, float *desc, float *tokens_out,
                                       void *stream) {
     VSC_REQUIRE(frames, "swin forward: null frames");
+    VSC_REQUIRE_ALIGNED("swin forward", frames, 16);       // the patch gather reads a patch row as float4
+    VSC_REQUIRE_ALIGNED("swin forward", tokens_out, 16);
     return swin_forward_impl(e, frames, nullptr, nullptr, nullptr, n, desc, tokens_out, stream);
 }
 
