@@ -499,6 +499,56 @@ int vsc_pca_fit_moments_f64(vsc_pca_fit *f, double *sum_dev, double *s2_dev, int
 int vsc_pca_fit_covariance_f64(vsc_pca_fit *f, double *mean_dev, double *cov_dev, void *stream);
 void vsc_pca_fit_destroy(vsc_pca_fit *f);
 
+/* Matching-track segment AP -- the reference's match_metric (VSC22-Matching-Track-1st/infer/vsc/metrics.py:120-383: Intervals,
+ * Match.overlaps, VideoPair.add_prediction and the accumulation loop), the number sscd_baseline.py:224-225 logs as "Matching track
+ * metric".  Two kernels; the divisions, square roots and the AP sum stay on the host (vsc_hip/segment_metric.py), so the device
+ * arithmetic is fp64 add, subtract, compare, min / max and one multiply, every operation rounded on its own -- bit-equality with the
+ * reference rests on IEEE arithmetic alone.  Executable contract: tests/segment_metric_contract.py.
+ *
+ * The handle owns the scratch and is bound to a stream at creation: every call of the handle enqueues on that stream and nothing
+ * else (no host synchronisation, no table in host memory; growing the scratch frees the smaller buffer, which waits for the
+ * device, as vsc_pca_fit_update_f32 does).  One host thread at a time per handle.  The results are pure functions of the operands.
+ *
+ * vsc_segment_metric_deltas_f64, one wave per video pair.  pred_boxes_dev [n_preds][4] = {q_start, q_end, r_start, r_end} in RANK
+ * order (rank = position in the stable descending sort by score); pred_ptr_dev [n_pairs + 1] / pred_rank_dev [n_preds]: CSR listing
+ * each pair's ranks in ascending order; gt_boxes_dev [n_gts][4] grouped by pair in file order, gt_ptr_dev [n_pairs + 1].  Outputs:
+ * deltas_dev [n_preds][4] = {dI_q, dI_r, dT_q, dT_r} written at the prediction's rank, gt_len_dev [n_pairs][2].  Per pair, with its
+ * predictions taken in rank order:
+ *   Considered ground truths: a ground truth becomes considered once
+ *     fabs(max(min(qe, qe') - max(qs, qs'), 0) * max(min(re, re') - max(rs, rs'), 0)) > 0.0
+ *     holds against any prediction so far -- that fp64 product as written (an underflowing product is "no overlap" in the reference
+ *     too).  The flag never clears.
+ *   Merged set of a list of intervals: its connected components under start <= current_end (touching intervals merge), each from
+ *     its least start to its greatest end.
+ *   len(S) = (((0.0 + (e0 - s0)) + (e1 - s1)) + ...) over the components in ascending start order; order and association are fixed.
+ *   Per axis: U = merged set of the predictions so far, G = merged set of the considered ground truths, W = merged set of U's and
+ *     G's components together; T = len(U); I = (T + len(G)) - len(W); dI = I - I_prev, dT = T - T_prev, both starting at 0.0.
+ *   gt_len[p][axis] = len(merged set of ALL the pair's ground truths).
+ * Lists longer than a wave go in chunks of 64: no limit on a pair's size below the global one, n_preds, n_gts, n_pairs < 2^31.
+ * Scratch: 128 (n_preds + n_gts) + 4 n_gts bytes, owned by the handle, initialised by every call.  Boxes are finite with
+ * end >= start (the host refuses others; on the device they neither fault nor hang, the result is unspecified); tables that point
+ * outside the operands leave their pair unwritten.  n_preds == 0 (or n_pairs == 0) launches nothing and writes nothing.
+ *
+ * vsc_segment_metric_scan_f64, one workgroup: out_dev[e][c] = ((0.0 + rows[0][c]) + rows[1][c]) + ... + rows[ends[e]][c] for
+ * rows_dev [n][cols] fp64, 1 <= cols <= 8, ends_dev [n_ends] int64 ascending (repeats allowed) in [0, n): strictly left to right,
+ * no tree, no atomics, no reassociation (np.cumsum(rows, axis=0)[ends]).  Serves the running {I_q, I_r, T_q, T_r} at the end of
+ * every tie group of scores, and the two ground-truth totals (rows = gt_len of the pairs that have ground truth, in order of first
+ * appearance in the ground-truth file: the insertion order of the reference's dict).  n == 0 or n_ends == 0 launches nothing.
+ *
+ * Refused (VSC_ERR_INVALID): a null handle, negative counts, counts of 2^31 or more, cols outside 1 .. 8, a null operand of a call
+ * that launches. */
+typedef struct vsc_segment_metric vsc_segment_metric;
+/* metrics.py:309-336 (the state match_metric sets up); every call of the handle enqueues on this stream */
+int vsc_segment_metric_create(void *stream, vsc_segment_metric **out);
+void vsc_segment_metric_destroy(vsc_segment_metric *m);
+/* metrics.py:243-306 (VideoPair.add_prediction for every prediction of every pair) and :262-263 (total_gt_length) */
+int vsc_segment_metric_deltas_f64(vsc_segment_metric *m, const double *pred_boxes_dev, const int64_t *pred_ptr_dev,
+                                  const int64_t *pred_rank_dev, int64_t n_preds, const double *gt_boxes_dev,
+                                  const int64_t *gt_ptr_dev, int64_t n_gts, int64_t n_pairs, double *deltas_dev, double *gt_len_dev);
+/* metrics.py:331-335 and :357-360 (the running sums, in dict order and in score order) */
+int vsc_segment_metric_scan_f64(vsc_segment_metric *m, const double *rows_dev, int64_t n, int32_t cols,
+                                const int64_t *ends_dev, int64_t n_ends, double *out_dev);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

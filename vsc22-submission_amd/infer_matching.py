@@ -152,6 +152,11 @@ def main(args):
         w.writerow(["query_id", "ref_id", "query_start", "query_end", "ref_start", "ref_end", "score"])
         w.writerows(rows)
     print(f"{len(rows)} matches -> {args.output}")
+    if getattr(args, "segment_metric", "none") == "hip" and getattr(args, "ground_truth", None):
+        from vsc.metrics import evaluate_matching_track
+        metrics = evaluate_matching_track(args.ground_truth, args.output)
+        print(f"Matching track metric: {metrics.segment_ap.ap:.4f}")
+        print(f"Matching track pairwise uAP: {metrics.pairwise_micro_ap.ap:.4f}")
 
 
 if __name__ == "__main__":
@@ -169,5 +174,9 @@ if __name__ == "__main__":
     ap.add_argument("--maps", choices=("host", "hip"), default="host",
                     help="steps 3 and 4 feed the networks from host arrays (as the reference) or from maps that stay on the device "
                          "(vsc_match_maps_f32; same csv)")
+    ap.add_argument("--ground_truth", default=None, help="matching ground-truth csv, scored with --segment_metric hip")
+    ap.add_argument("--segment_metric", choices=("none", "hip"), default="none",
+                    help="with --ground_truth: score the written csv by the matching-track segment AP on the device "
+                         "(vsc_segment_metric_*; the reference's evaluate_matching_track)")
     ap.add_argument("--output", required=True)
     main(ap.parse_args())

@@ -38,6 +38,7 @@ def search(queries: List[VideoFeature], refs: List[VideoFeature], retrieve_per_q
 
 ALIGNMENTS = ("vcsl", "hip")
 CANDIDATES = ("host", "hip")
+SEGMENT_METRICS = ("none", "hip")
 
 
 def localize_and_verify(queries: List[VideoFeature], refs: List[VideoFeature], candidates: List[CandidatePair],
@@ -105,6 +106,7 @@ def main(args) -> None:
         matches = localize_and_verify(queries, refs, candidates, score_normalization=bool(args.score_norm_features),
                                       alignment=args.alignment)
     except ImportError as exc:
+        matches_file = None
         logger.warning("matches.csv not written: %s", exc)
     else:
         matches_file = os.path.join(args.output_path, "matches.csv")
@@ -115,6 +117,17 @@ def main(args) -> None:
         uap = average_precision(read_ground_truth_pairs(args.ground_truth), candidates)
         logger.info("Candidate uAP: %.4f", uap.ap)
         print(f"Candidate uAP: {uap.ap:.4f}")
+        segment_metric = getattr(args, "segment_metric", "none")       # main() is also called with namespaces from before the option
+        if segment_metric not in SEGMENT_METRICS:
+            raise ValueError(f"segment_metric {segment_metric!r}: one of {SEGMENT_METRICS}")
+        if segment_metric == "hip" and matches_file:
+            # sscd_baseline.py:224-225 of the matching track: evaluate_matching_track on the file just written
+            from vsc.metrics import evaluate_matching_track
+            metrics = evaluate_matching_track(args.ground_truth, matches_file)
+            logger.info("Matching track metric: %.4f", metrics.segment_ap.ap)
+            logger.info("Matching track pairwise uAP: %.4f", metrics.pairwise_micro_ap.ap)
+            print(f"Matching track metric: {metrics.segment_ap.ap:.4f}")
+            print(f"Matching track pairwise uAP: {metrics.pairwise_micro_ap.ap:.4f}")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -129,6 +142,8 @@ def build_parser() -> argparse.ArgumentParser:
                     help="temporal alignment of matches.csv: the reference's VCSL package (vcsl) or the HIP kernel (hip)")
     ap.add_argument("--candidates", choices=CANDIDATES, default="host",
                     help="global top-k selection and video-pair grouping of candidates.csv: on the host (host) or in HIP (hip)")
+    ap.add_argument("--segment_metric", choices=SEGMENT_METRICS, default="none",
+                    help="with --ground_truth and a written matches.csv: the matching-track segment AP on the device (hip)")
     return ap
 
 

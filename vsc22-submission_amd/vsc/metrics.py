@@ -1,7 +1,8 @@
 """The slice of the reference's vsc/metrics.py that the descriptor path touches:
 video-id formatting, candidate pairs, predicted matches (the rows of matches.csv) and the
-descriptor-track micro-AP (infer/vsc/metrics.py:21-119, 183-243, 423-494).  The matching-track
-segment metric is out of scope of this path."""
+descriptor-track micro-AP (infer/vsc/metrics.py:21-119, 183-243, 423-494), and the matching-track
+segment AP (VSC22-Matching-Track-1st/infer/vsc/metrics.py:120-420: match_metric, evaluate_matching_track), whose
+interval arithmetic runs on the device (vsc_hip/segment_metric.py) -- there is no CPU implementation of it here."""
 from __future__ import annotations
 
 import dataclasses
@@ -78,9 +79,11 @@ class Match(NamedTuple):
         df.to_csv(file, index=False)
 
     @classmethod
-    def read_csv(cls, file, is_gt: bool = False, check: bool = True) -> List["Match"]:
+    def read_csv(cls, file, is_gt: bool = False, check: bool = True, float_precision: Optional[str] = None) -> List["Match"]:
+        """float_precision: pandas' parser for the numbers; the default (as the reference reads) may be an ulp off the written
+        value, "round_trip" is correctly rounded"""
         import pandas as pd
-        df = pd.read_csv(file)
+        df = pd.read_csv(file, float_precision=float_precision)
         df["query_id"] = df.query_id.map(lambda x: format_video_id(x, Dataset.QUERIES))
         df["ref_id"] = df.ref_id.map(lambda x: format_video_id(x, Dataset.REFS))
         if is_gt:
@@ -191,3 +194,32 @@ def micro_average_precision(ground_truth: Collection[CandidatePair],
     if not len(predictions) or not len(ground_truth):
         return 0.0
     return float(average_precision(ground_truth, predictions).simple_ap)
+
+
+def match_metric(gts: Collection[Match], predictions: Collection[Match]) -> AveragePrecision:
+    """The matching-track metric (metrics.py:309-383): AP = sum_i P(i) dR(i) over the groups of equal scores, with
+    P = sqrt(P_q P_r) and R = sqrt(R_q R_r) from the covered lengths on the query and reference axes, as in VCSL.  `.ap` and the
+    curve are the reference's bit for bit (tests/golden/segment_metric.json).  Runs on the HIP path: without a device it raises
+    HipPathUnavailable.  ZeroDivisionError where the reference raises it; ValueError for non-finite values and for boxes with
+    end < start, whose result in the reference depends on sort accidents (vsc_hip/segment_metric.py)."""
+    from vsc_hip import segment_metric
+    ap, precisions, recalls, scores = segment_metric.segment_ap(list(gts), list(predictions))
+    return AveragePrecision(ap, PrecisionRecallCurve(np.array(precisions), np.array(recalls), np.array(scores)))
+
+
+@dataclasses.dataclass
+class MatchingTrackMetrics:
+    """metrics.py:386-391: the main metric, and the pairwise uAP that ignores localisation."""
+    segment_ap: AveragePrecision
+    pairwise_micro_ap: AveragePrecision
+
+
+def evaluate_matching_track(ground_truth_filename: str, predictions_filename: str) -> MatchingTrackMetrics:
+    """metrics.py:394-420: both files are csvs with the columns query_id, ref_id, query_start, query_end, ref_start, ref_end
+    (+ score for the predictions), in any order.  The numbers are parsed correctly rounded, so a file written by Match.write_csv
+    scores exactly as the list it was written from (pandas' default parser, which the reference uses, can be an ulp off)."""
+    gt = Match.read_csv(ground_truth_filename, is_gt=True, float_precision="round_trip")
+    predictions = Match.read_csv(predictions_filename, float_precision="round_trip")
+    metric = match_metric(gt, predictions)
+    pair_ap = average_precision(candidate_pairs_from_matches(gt), candidate_pairs_from_matches(predictions))
+    return MatchingTrackMetrics(segment_ap=metric, pairwise_micro_ap=pair_ap)

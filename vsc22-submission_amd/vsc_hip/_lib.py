@@ -110,6 +110,11 @@ SIGNATURES = {
     "vsc_pca_fit_moments_f64": (c_int32, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p]),
     "vsc_pca_fit_covariance_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_pca_fit_destroy": (None, [c_void_p]),
+    "vsc_segment_metric_create": (c_int32, [c_void_p, POINTER(c_void_p)]),
+    "vsc_segment_metric_destroy": (None, [c_void_p]),
+    "vsc_segment_metric_deltas_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64,
+                                                c_void_p, c_void_p]),
+    "vsc_segment_metric_scan_f64": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int64, c_void_p]),
     "vsc_frame_var_u8": (c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "vsc_canny_count_u8": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
                                      c_void_p, c_void_p]),
