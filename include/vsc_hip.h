@@ -475,6 +475,44 @@ int vsc_resize_bicubic_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32
  * infer/extract_query_feats.py:178, infer/vsc/baseline/score_normalization.py:84-88. */
 int vsc_l2_normalize_f32(float *x_dev, int64_t n, int32_t d, void *stream);
 
+/* Score normalisation on the device: what infer/vsc/baseline/score_normalization.py does per set of descriptors -- the
+ * low-variance dimension (:74-76; infer/src/utils.py:2-5), np.delete of that column and the row normalisation (:84-88), the bias
+ * -beta * mean of the nk best noise scores (:95-105) with the video-score gate (:141-150), and the appended column -- with the
+ * BITS of that numpy chain (executable form of the contract: tests/score_norm_contract.py).  The three entries take a handle
+ * that holds the caller's stream (vsc_score_norm_create; as vsc_segment_metric and vsc_pca_fit bind theirs): they only enqueue on it
+ * and never synchronise with the host; the handle owns no device memory, a null handle is refused; operands are float32 rows with a row stride in elements, stride >= width.
+ *
+ * vsc_column_var_f32: var_dev[c] = x.var(axis=0)[c] as numpy computes it for a C-contiguous [n, d] float32 array.  Per column one
+ * chain over the rows in ascending order:  s = ((x[0] + x[1]) + x[2]) + ... in fp32;  mean = (float)((double)s / (double)n);
+ * acc = sum over the rows, in that order, of fl(fl(x - mean) * fl(x - mean)), the subtraction, the product and the sum each rounded
+ * on their own (no fused multiply-add);  var = (float)((double)acc / (double)n).  The low-variance dimension is the host's
+ * np.argmin of var_dev.  One workgroup per 64 columns, rows staged through LDS in tiles of VSC_COLUMN_VAR_TILE; rows past n and
+ * columns past d are never read.  Refused: n < 1, d < 1, ld < d, a null pointer.
+ *
+ * vsc_score_norm_rows_f32: out = concatenate([normalize(delete(x, drop, axis=1)), last], axis=1).  drop in [0, d) or -1 (no column
+ * dropped); normalize 0 or 1; append 0 (no column), 1 (the constant 1.0f) or 2 (last_dev[row]); the output has
+ * d - (drop >= 0) + (append != 0) columns.  normalize = 1 is vsc_l2_normalize_f32 on the narrowed row: lane l of the row's wave sums
+ * the squares of the narrowed row's columns l, l + 64, ... as fmaf(x, x, ss), the lanes are added by the xor butterfly 32 ... 1,
+ * nrm = sqrtf(ss), and the row becomes x / nrm -- or stays exactly as it was when nrm == 0 (a zero row, and a row whose squares
+ * underflow).  out_dev must not overlap x_dev (refused: the kernel is no in-place shift).  n == 0 launches nothing.  Refused: n < 0
+ * or n >= 2^31, drop outside [-1, d), other values of normalize / append, a stride below its width, a null operand that is needed.
+ *
+ * vsc_score_norm_bias_f32: bias_dev[q] = fl32(neg_beta * mean(topk[q, 0:nk])) with numpy's row sum -- nk < 8: left to right from
+ * the first element; 8 <= nk <= 128: eight accumulators r[j] = a[j], r[j] += a[i + j] for i = 8, 16, ... < nk - nk % 8, then
+ * ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)), then the remaining nk % 8 elements left to right -- and
+ * mean = (float)((double)sum / (double)nk); neg_beta is the caller's (float)(-beta).  gate_dev: uint8 [nq] or NULL; a non-zero
+ * entry makes the row's bias exactly -100.0f (a video below the score threshold).  nq == 0 launches nothing.  Refused: nk outside
+ * [1, 128] (beyond it numpy's sum recurses), ldk < nk, nq < 0 or nq >= 2^31, a null operand. */
+#define VSC_COLUMN_VAR_TILE 64
+typedef struct vsc_score_norm vsc_score_norm;
+int vsc_score_norm_create(void *stream, vsc_score_norm **out);   /* every call of the handle enqueues on this stream */
+void vsc_score_norm_destroy(vsc_score_norm *h);
+int vsc_column_var_f32(vsc_score_norm *h, const float *x_dev, int64_t n, int32_t d, int64_t ld, float *var_dev);
+int vsc_score_norm_rows_f32(vsc_score_norm *h, const float *x_dev, int64_t n, int32_t d, int64_t ldx, int32_t drop, int32_t normalize,
+                            int32_t append, const float *last_dev, float *out_dev, int64_t ldo);
+int vsc_score_norm_bias_f32(vsc_score_norm *h, const float *topk_dev, int64_t nq, int64_t ldk, int32_t nk, float neg_beta,
+                            const uint8_t *gate_dev, float *bias_dev);
+
 /* PCA fit, the part that grows with the number of rows -- the reference fits its PCA inside the reference-side chain
  * (infer/concat_pca_sn.py:42-54: PCA(n_components=512, random_state=2023).fit(train_features) on the concatenated, per-model
  * normalised descriptors of every training reference).  The handle accumulates the RAW MOMENTS of fp32 rows in fp64 on the matrix

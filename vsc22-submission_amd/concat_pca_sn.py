@@ -6,6 +6,7 @@
 Per feature set (train_refs, test_refs): the per-model descriptors of every video are L2-normalised, concatenated and
 mapped to 512-d by the PCA (concat_pca_sn.py:56-68) -> <root>/<set>.npz; then each set is score-normalised against the
 other (:71-88) -> <root>/<set>_sn.npz.  Row normalisation and the PCA product run on the GPU (HipOps / HipPCA).
+``--score_norm hip`` runs that normalisation on the device (vsc.baseline.score_normalization, device="hip"; the same files).
 ``--fit_pca`` fits the PCA on the train set first (:42-54).  ``--pca_fit sklearn`` (the default) does it with sklearn on the host
 exactly as the reference does and pickles the object; ``--pca_fit hip`` accumulates the moments on the GPU block by block
 (vsc_hip/pca_fit.py: fp64 covariance, exact eigendecomposition; no sklearn, no pickle) and writes an ``.npz`` model file.
@@ -18,7 +19,7 @@ import os
 import numpy as np
 
 from src.query_postprocess import HipOps, HipPCA, load_pca_model, save_pca_model
-from vsc.baseline.score_normalization import ref_score_normalize
+from vsc.baseline.score_normalization import DEVICES as SCORE_NORMS, ScoreNormBank, ref_score_normalize
 from vsc.index import VideoFeature
 from vsc.storage import load_features, store_features
 
@@ -112,10 +113,17 @@ def main(args):
     pca = HipPCA(fitted)
     for name in sets:
         store_features(os.path.join(args.root, f"{name}.npz"), merge_set([path(m, name) for m in args.models], pca.transform))
+    score_norm = getattr(args, "score_norm", "host")   # main() is also called with namespaces built by hand, from before --score_norm
+    if score_norm == "hip":
+        # each set is the other's normalisation set: uploaded once, as a handle that serves in both roles
+        banks = {name: ScoreNormBank(load_features(os.path.join(args.root, f"{name}.npz"))) for name in sets}
     for name, other in ((sets[1], sets[0]), (sets[0], sets[1])):
-        refs = load_features(os.path.join(args.root, f"{name}.npz"))
-        norm = load_features(os.path.join(args.root, f"{other}.npz"))
-        store_features(os.path.join(args.root, f"{name}_sn.npz"), ref_score_normalize(refs, norm, nk=NK, beta=BETA))
+        if score_norm == "hip":
+            refs, norm = banks[name], banks[other]
+        else:
+            refs = load_features(os.path.join(args.root, f"{name}.npz"))
+            norm = load_features(os.path.join(args.root, f"{other}.npz"))
+        store_features(os.path.join(args.root, f"{name}_sn.npz"), ref_score_normalize(refs, norm, nk=NK, beta=BETA, device=score_norm))
 
 
 def build_parser():
@@ -128,6 +136,9 @@ def build_parser():
                     help="with --fit_pca: sklearn on the host as the reference (pickle), or the moments on the GPU + exact eigendecomposition "
                          "(vsc_hip/pca_fit.py; --pca_model must end in .npz)")
     ap.add_argument("--dim", type=int, default=512)
+    ap.add_argument("--score_norm", choices=SCORE_NORMS, default="host",
+                    help="the score normalisation's arithmetic in numpy on the host, or on the device (hip: one upload per set, the "
+                         "same <set>_sn.npz)")
     return ap
 
 

@@ -353,3 +353,9 @@ int launch_canny_count_u8(const uint8_t *frames, int64_t n, const int32_t *idx_h
                           uint16_t *out, hipStream_t stream);
 int launch_resize_bicubic_u8(const uint8_t *frames, int64_t n, int h, int w, const int32_t *boxes_host, int k, int size, uint8_t *out,
                              hipStream_t stream);
+// score normalisation (score_norm.hip), contracts at vsc_column_var_f32 / vsc_score_norm_rows_f32 / vsc_score_norm_bias_f32 in include/vsc_hip.h
+int launch_column_var(const float *x, int64_t n, int d, int64_t ld, float *var, hipStream_t stream);
+int launch_score_norm_rows(const float *x, int64_t n, int d, int64_t ldx, int drop, int normalize, int append, const float *last,
+                           float *out, int64_t ldo, hipStream_t stream);
+int launch_score_norm_bias(const float *topk, int64_t nq, int64_t ldk, int nk, float neg_beta, const uint8_t *gate, float *bias,
+                           hipStream_t stream);

@@ -33,7 +33,7 @@ from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
 from src.image_preprocess import HipViews
 from src.query_pipeline import RAW_KEY, VideoScorer, run_query_videos
 from src.query_postprocess import HipPCA, SCORE_THRESHOLD, load_pca_model
-from vsc.baseline.score_normalization import query_score_normalize
+from vsc.baseline.score_normalization import DEVICES as SCORE_NORMS, ScoreNormBank, query_score_normalize
 from vsc.metrics import Dataset
 from vsc.storage import load_features, store_features
 
@@ -122,9 +122,12 @@ def main(args):
         store_features(os.path.join(args.output_dir, key, f"{args.split}_query.npz"), [sub[i] for sub in per_model])
     if args.norm_refs:
         norm_refs = load_features(args.norm_refs, Dataset.REFS)
+        score_norm = getattr(args, "score_norm", "host")   # main() is also called with namespaces built by hand, from before the option
+        if score_norm == "hip":
+            norm_refs = ScoreNormBank(norm_refs)           # uploaded once: the dimension, then the noise bank
         all_scores = {f.video_id: scores.get(f.video_id, 1.0) for f in finals}
-        finals = query_score_normalize(finals, norm_refs, all_scores, args.score_threshold, calclualte_low_var_dim(norm_refs),
-                                       nk=NK, beta=BETA)
+        finals = query_score_normalize(finals, norm_refs, all_scores, args.score_threshold,
+                                       calclualte_low_var_dim(norm_refs, device=score_norm), nk=NK, beta=BETA, device=score_norm)
     store_features(os.path.join(args.output_dir, f"{args.split}_query_sn.npz"), finals)
 
 
@@ -148,6 +151,8 @@ def build_parser():
     ap.add_argument("--workers", type=int, default=6, help="decode / resize worker processes (the reference uses 6)")
     ap.add_argument("--preprocess", default="none", choices=["none", "hip"],
                     help="hip: crop static borders and split stacked views on the GPU before encoding (the reference's image_process)")
+    ap.add_argument("--score_norm", default="host", choices=SCORE_NORMS,
+                    help="with --norm_refs: the query score normalisation in numpy on the host, or on the device (hip; the same file)")
     return ap
 
 

@@ -77,22 +77,28 @@ LOCALIZE_PASSES = ((MATCH_REFINE_THRESHOLD_HIGH, 0.5), (MATCH_REFINE_THRESHOLD_M
 
 
 def run(query_list, score_norm_refs, refs, sn_refs, cls_models, refine_models, query_frames=None, candidates_csv=None,
-        device="cuda", localize="host", maps="host"):
+        device="cuda", localize="host", maps="host", score_norm="host"):
     """Steps 1-5 on loaded VideoFeature lists and HIP models -> rows [query_id, ref_id, query_start, query_end, ref_start,
     ref_end, score] (the reference's output columns, :306-310).  localize="hip": step 5 on the device, the three thresholds in
     one launch over maps that never leave it (src.matching.generate_matching_results_hip).  maps="hip": steps 3 and 4 without a similarity
     matrix or a network input crossing PCIe (src.matching.classify_candidates_hip / refine_candidates_hip) -- the same rows; it needs
-    query videos whose rows form whole views and raises ValueError otherwise."""
+    query videos whose rows form whole views and raises ValueError otherwise.  score_norm="hip": step 1 on the device, the normalisation
+    set uploaded once (vsc.baseline.score_normalization, device="hip") -- the same descriptors."""
     if localize not in ("host", "hip"):
         raise ValueError(f"localize must be 'host' or 'hip', not {localize!r}")
     if maps not in ("host", "hip"):
         raise ValueError(f"maps must be 'host' or 'hip', not {maps!r}")
     from src import matching
-    from vsc.baseline.score_normalization import normalize, query_score_normalize, transform_features
+    from vsc.baseline.score_normalization import DEVICES, ScoreNormBank, normalize, query_score_normalize, transform_features
+    if score_norm not in DEVICES:
+        raise ValueError(f"score_norm must be one of {DEVICES}, not {score_norm!r}")
+    if score_norm == "hip":
+        score_norm_refs = ScoreNormBank(score_norm_refs)   # uploaded once: the dimension, then the noise bank
 
-    low_var_dim = matching.calclualte_low_var_dim(score_norm_refs)                               # :212
+    low_var_dim = matching.calclualte_low_var_dim(score_norm_refs, device=score_norm)            # :212
     keep_all = collections.defaultdict(lambda: 1.0)   # the matching track's normalisation has no video-score gate (:107-115 of its score_normalization.py)
-    sn_query_list = query_score_normalize(query_list, score_norm_refs, keep_all, low_var_dim=low_var_dim, beta=1.5, nk=10)   # :213
+    sn_query_list = query_score_normalize(query_list, score_norm_refs, keep_all, low_var_dim=low_var_dim, beta=1.5, nk=10,
+                                          device=score_norm)                                      # :213
     search_res_list = matching.search_candidate_pairs(sn_query_list, sn_refs, matching.SEARCH_THRESHOLD)              # :216-262
     if candidates_csv:
         with open(candidates_csv, "w", newline="") as f:
@@ -145,7 +151,8 @@ def main(args):
     rows = run(load_features(args.query_features, Dataset.QUERIES), load_features(args.norm_refs, Dataset.REFS),
                load_features(args.refs, Dataset.REFS), load_features(args.sn_refs, Dataset.REFS), cls_models, refine_models,
                query_frames, args.candidates_csv, localize=args.localize,
-               maps=getattr(args, "maps", "host"))   # main() is also called with namespaces built by hand, from before --maps
+               maps=getattr(args, "maps", "host"),   # main() is also called with namespaces built by hand, from before --maps
+               score_norm=getattr(args, "score_norm", "host"))
     os.makedirs(os.path.dirname(os.path.abspath(args.output)), exist_ok=True)
     with open(args.output, "w", newline="") as f:
         w = csv.writer(f)
@@ -159,7 +166,7 @@ def main(args):
         print(f"Matching track pairwise uAP: {metrics.pairwise_micro_ap.ap:.4f}")
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--query_features", required=True)
     ap.add_argument("--norm_refs", required=True, help="NORM_DATA_FILE: descriptors of the normalisation set")
@@ -178,5 +185,11 @@ if __name__ == "__main__":
     ap.add_argument("--segment_metric", choices=("none", "hip"), default="none",
                     help="with --ground_truth: score the written csv by the matching-track segment AP on the device "
                          "(vsc_segment_metric_*; the reference's evaluate_matching_track)")
+    ap.add_argument("--score_norm", choices=("host", "hip"), default="host",
+                    help="step 1, the query score normalisation, in numpy on the host or on the device (hip; the same descriptors)")
     ap.add_argument("--output", required=True)
-    main(ap.parse_args())
+    return ap
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

@@ -22,4 +22,6 @@ done
 # PCA_FIT=hip fits the PCA on the train references on the GPU (implies --fit_pca; the model file is then an .npz, read by infer_query.sh
 # through the same PCA_MODEL); FIT_PCA=1 alone fits with sklearn on the host as the reference does and pickles it
 if [ "${PCA_FIT:-sklearn}" = hip ]; then PCA_MODEL=${PCA_MODEL:-$CKPT/pca_model.npz}; FIT_ARGS="--fit_pca --pca_fit hip"; else PCA_MODEL=${PCA_MODEL:-$CKPT/pca_model.pkl}; FIT_ARGS=${FIT_PCA:+--fit_pca}; fi
-python concat_pca_sn.py --root "$OUT" --models swinv2_v115 swinv2_v107 swinv2_v106 vit_v68 --pca_model "$PCA_MODEL" $FIT_ARGS
+# SCORE_NORM=hip runs the score normalisation of the two merged sets on the GPU (one upload per set; the same <set>_sn.npz)
+python concat_pca_sn.py --root "$OUT" --models swinv2_v115 swinv2_v107 swinv2_v106 vit_v68 --pca_model "$PCA_MODEL" $FIT_ARGS \
+  --score_norm "${SCORE_NORM:-host}"

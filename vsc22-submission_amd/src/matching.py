@@ -39,8 +39,13 @@ TOP_ROWS = 10  # rows whose maxima are averaged to score a query view (utils.py:
 SEARCH_THRESHOLD = -0.1  # infer_matching.py:62
 
 
-def calclualte_low_var_dim(score_norm_refs) -> int:
-    """Index of the descriptor dimension with the smallest variance over all reference frames."""
+def calclualte_low_var_dim(score_norm_refs, device: str = "host") -> int:
+    """Index of the descriptor dimension with the smallest variance over all reference frames.  device="hip": the variance on the
+    device (vsc_column_var_f32, numpy's bits); `score_norm_refs` may then be a `ScoreNormBank`, which keeps the set uploaded for the
+    normalisation that follows."""
+    if device != "host":
+        from vsc.baseline.score_normalization import low_variance_dim
+        return low_variance_dim(score_norm_refs, device=device)
     sn_features = np.concatenate([ref.feature for ref in score_norm_refs], axis=0)
     return int(sn_features.var(axis=0).argmin())
 

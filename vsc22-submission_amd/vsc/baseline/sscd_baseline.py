@@ -38,6 +38,7 @@ def search(queries: List[VideoFeature], refs: List[VideoFeature], retrieve_per_q
 
 ALIGNMENTS = ("vcsl", "hip")
 CANDIDATES = ("host", "hip")
+SCORE_NORMS = ("host", "hip")
 SEGMENT_METRICS = ("none", "hip")
 
 
@@ -95,7 +96,7 @@ def main(args) -> None:
     os.makedirs(args.output_path, exist_ok=True)
     if args.score_norm_features:
         queries, refs = score_normalize(queries, refs, load_features(args.score_norm_features, Dataset.REFS),
-                                        beta=1.2)
+                                        beta=1.2, device=getattr(args, "score_norm", "host"))   # (namespaces from before the option)
         store_features(os.path.join(args.output_path, "sn_queries.npz"), queries)
         store_features(os.path.join(args.output_path, "sn_refs.npz"), refs)
     candidates = search(queries, refs, selection=getattr(args, "candidates", "host"))
@@ -142,6 +143,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="temporal alignment of matches.csv: the reference's VCSL package (vcsl) or the HIP kernel (hip)")
     ap.add_argument("--candidates", choices=CANDIDATES, default="host",
                     help="global top-k selection and video-pair grouping of candidates.csv: on the host (host) or in HIP (hip)")
+    ap.add_argument("--score_norm", choices=SCORE_NORMS, default="host",
+                    help="with --score_norm_features: the normalisation's arithmetic in numpy on the host (host) or on the device (hip: "
+                         "vsc_column_var_f32 / vsc_score_norm_rows_f32 / vsc_score_norm_bias_f32; the same sn_*.npz, and the normalised "
+                         "references stay on the device as the search's bank)")
     ap.add_argument("--segment_metric", choices=SEGMENT_METRICS, default="none",
                     help="with --ground_truth and a written matches.csv: the matching-track segment AP on the device (hip)")
     return ap

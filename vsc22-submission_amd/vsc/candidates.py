@@ -40,7 +40,7 @@ class CandidateGeneration:
             raise ValueError("CandidateGeneration needs at least one reference video")
         self.aggregation = aggregation
         self.index = VideoIndex(references[0].dimensions(), selection=selection)
-        self.index.add(list(references))
+        self.index.add(references if isinstance(references, list) else list(references))   # (a DeviceRows list keeps its rows_dev)
 
     def query(self, queries: List[VideoFeature], global_k: int, limit: int = None) -> List[CandidatePair]:
         """limit: only the first `limit` candidates (== query(...)[:limit]; the caller that keeps 25 per query video of 1 200 does not pay

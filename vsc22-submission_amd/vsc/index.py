@@ -84,6 +84,7 @@ class FlatIPBank:
         self._chunks: list = []
         self._bank = None
         self._bank_max_norm = None      # largest row norm of the bank (METRIC_L2 rounding bound), cached with the bank
+        self.adopted = False            # the device bank was handed over (adopt_device_rows), not uploaded
         self.ntotal = 0
 
     @property
@@ -95,10 +96,24 @@ class FlatIPBank:
         assert x.ndim == 2 and x.shape[1] == self.d, f"expected [n,{self.d}], got {x.shape}"
         self._chunks.append(x)
         self._bank = self._bank_max_norm = None
+        self.adopted = False
         self.ntotal += x.shape[0]
 
     def reset(self) -> None:
-        self._chunks, self._bank, self._bank_max_norm, self.ntotal = [], None, None, 0
+        self._chunks, self._bank, self._bank_max_norm, self.ntotal, self.adopted = [], None, None, 0, False
+
+    def adopt_device_rows(self, rows_dev) -> None:
+        """The rows added so far already stand on the device as `rows_dev` ([ntotal, d] float32, contiguous: the finished array of a
+        device score normalisation): it becomes the device bank and nothing is uploaded.  The caller vouches that it holds the bytes
+        of the added rows.  Valid until the next add(); inner-product banks only (an L2 bank stores augmented rows)."""
+        import torch
+        if not self.is_similarity:
+            raise ValueError("adopt_device_rows: inner-product indexes only")
+        if not (rows_dev.is_cuda and rows_dev.dtype == torch.float32 and rows_dev.is_contiguous()
+                and tuple(rows_dev.shape) == (self.ntotal, self.d)):
+            raise ValueError(f"adopt_device_rows: expected a contiguous float32 [{self.ntotal}, {self.d}] device tensor, got "
+                             f"{rows_dev.dtype} {tuple(rows_dev.shape)}")
+        self._bank, self.adopted = rows_dev, True
 
     def _host_rows(self) -> np.ndarray:
         if len(self._chunks) > 1:
@@ -279,6 +294,11 @@ class VideoIndex:
             self.video_metadata[vf.video_id] = vf.metadata()
             self.index.add(vf.feature)
         self._ref_video_table = None
+        # a device score normalisation hands its finished rows on (score_normalization.DeviceRows): they are this index's bank as they
+        # stand, if the index holds nothing else
+        rows_dev = getattr(db, "rows_dev", None)
+        if rows_dev is not None and self.index.is_similarity and rows_dev.shape[0] == self.index.ntotal == sum(len(vf) for vf in db):
+            self.index.adopt_device_rows(rows_dev)
 
     def search(self, queries: List[VideoFeature], global_k: int) -> List[PairMatches]:
         query_ids, query_rows = [], []

@@ -152,6 +152,12 @@ SIGNATURES = {
     "vsc_range_search_ip_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_float, c_int64,
                                           c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
     "vsc_l2_normalize_f32": (c_int32, [c_void_p, c_int64, c_int32, c_void_p]),
+    "vsc_score_norm_create": (c_int32, [c_void_p, POINTER(c_void_p)]),
+    "vsc_score_norm_destroy": (None, [c_void_p]),
+    "vsc_column_var_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p]),
+    "vsc_score_norm_rows_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                          c_int64]),
+    "vsc_score_norm_bias_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_float, c_void_p, c_void_p]),
     "vsc_gemm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                 c_int32, c_int32, c_int32, c_void_p]),
     "vsc_gemm_resadd_ln_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,

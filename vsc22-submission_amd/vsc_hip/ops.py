@@ -154,6 +154,77 @@ def l2_normalize_(x):
     return x
 
 
+def _rows_f32(t, what: str):
+    """(pointer, rows, width, row stride) of a float32 [n, d] device tensor whose rows are dense: the score-normalisation entries
+    take a row stride >= the width, so a column slice of a wider tensor passes without a copy."""
+    assert t.is_cuda and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] >= 1, f"{what}: a float32 [n, d] device tensor"
+    n, d = t.shape
+    assert d == 1 or t.stride(1) == 1, f"{what}: rows must be dense"
+    ld = t.stride(0) if n > 1 else d
+    assert ld >= d, f"{what}: row stride {ld} below the width {d}"
+    return _lib.c_void_p(t.data_ptr()), n, d, ld
+
+
+_score_norm_handles = {}
+
+
+def score_norm_handle():
+    """The vsc_score_norm handle of the current library on the current stream (made on first use, kept for the process: it is the
+    stream and owns no device memory)."""
+    import ctypes
+    lib = _rd()
+    stream = current_stream()
+    key = (_PRECISION, stream.value or 0)
+    if key not in _score_norm_handles:
+        h = ctypes.c_void_p()
+        check(lib.vsc_score_norm_create(stream, ctypes.byref(h)))
+        _score_norm_handles[key] = h
+    return _score_norm_handles[key]
+
+
+def column_var(x):
+    """numpy's x.var(axis=0) of float32 rows [n, d] (row stride >= d), bit for bit (vsc_column_var_f32) -> float32 [d] on the device."""
+    lib = _rd()
+    px, n, d, ld = _rows_f32(x, "column_var")
+    if n < 1:
+        raise ValueError("column_var: the variance of no rows")
+    var = torch.empty(d, dtype=torch.float32, device=x.device)
+    check(lib.vsc_column_var_f32(score_norm_handle(), px, n, d, ld, ptr(var)))
+    return var
+
+
+def score_norm_rows(x, drop: int = -1, normalize: bool = True, append: int = 0, last=None, out=None):
+    """concatenate([l2_normalize(delete(x, drop, axis=1)), last], axis=1) into a second buffer (vsc_score_norm_rows_f32): drop -1 keeps
+    every column, append 0 / 1 / 2 = no column / the constant 1.0f / last[row].  out: a float32 [n, width] device tensor (row stride
+    >= width) that does not overlap x; allocated when None."""
+    lib = _rd()
+    px, n, d, ldx = _rows_f32(x, "score_norm_rows: x")
+    width = d - (drop >= 0) + (append != 0)
+    if append == 2:
+        assert last is not None and last.is_cuda and last.dtype == torch.float32 and last.is_contiguous() and last.numel() == n
+    if out is None:
+        out = torch.empty((n, width), dtype=torch.float32, device=x.device)
+    po, no, wo, ldo = _rows_f32(out, "score_norm_rows: out")
+    assert (no, wo) == (n, width), f"score_norm_rows: out is {tuple(out.shape)}, not {(n, width)}"
+    check(lib.vsc_score_norm_rows_f32(score_norm_handle(), px, n, d, ldx, int(drop), int(bool(normalize)), int(append),
+                                      ptr(last) if append == 2 else None, po, ldo))
+    return out
+
+
+def score_norm_bias(topk, nk: int, beta: float, gate=None):
+    """-beta * topk[:, :nk].mean(axis=1) with numpy's bits (vsc_score_norm_bias_f32); gate: uint8 [nq] on the device, a non-zero entry
+    makes the row -100.0f.  -> float32 [nq] on the device."""
+    import numpy as np
+    lib = _rd()
+    pk, nq, width, ldk = _rows_f32(topk, "score_norm_bias")
+    assert nk <= width, f"score_norm_bias: nk {nk} of {width} columns"
+    if gate is not None:
+        assert gate.is_cuda and gate.dtype == torch.uint8 and gate.is_contiguous() and gate.numel() == nq
+    bias = torch.empty(nq, dtype=torch.float32, device=topk.device)
+    check(lib.vsc_score_norm_bias_f32(score_norm_handle(), pk, nq, ldk, int(nk), float(np.float32(-beta)), ptr(gate), ptr(bias)))
+    return bias
+
+
 def knn_ip(q, r, k: int, ref_id_offset: int = 0, floor=None):
     """Exact inner-product top-k.  q [nq,d], r [nr,d] float32 on the GPU ->
     (scores [nq,k] float32 descending, ids [nq,k] int64).  Empty inputs follow
