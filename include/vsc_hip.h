@@ -587,6 +587,50 @@ int vsc_segment_metric_deltas_f64(vsc_segment_metric *m, const double *pred_boxe
 int vsc_segment_metric_scan_f64(vsc_segment_metric *m, const double *rows_dev, int64_t n, int32_t cols,
                                 const int64_t *ends_dev, int64_t n_ends, double *out_dev);
 
+/* Descriptor-track micro-AP -- the reference's average_precision (VSC22-Descriptor-Track-1st/infer/vsc/metrics.py:423-494), the
+ * number it logs as "Candidate uAP" -- in two entries (executable contract: tests/uap_contract.py).  A pair is a 64-bit key
+ * query_index << ref_bits | ref_index of the indices the caller interned (ref_bits = 32 in general); every key is below
+ * 2^key_bits, and the key sorts skip the digit passes above that.  Both entries take a handle, which holds the stream it was made
+ * with and owns no device memory, and only enqueue on that stream; scratch is the search's grow-only per-device buffers (callers
+ * on one device are ordered; vsc_search_release_scratch frees it): about 48 n + 16 g bytes.
+ * n, g < 2^31.  n == 0 launches nothing, writes nothing and returns 0.  The outputs are a pure function of the inputs: integer
+ * atomics only count, every position is a scan result, every floating-point sum has a fixed association.
+ *
+ * vsc_uap_rank_f64: scores_dev f64 [n], pred_keys_dev u64 [n], gt_keys_dev u64 [g] in any order.
+ *   perm_dev i64 [n]          the stable descending order of the scores: perm[i] = input position of rank i; equal scores keep
+ *                             their input order and -0.0 equals +0.0 (sorted(reverse=True), argsort(-s, kind="mergesort"))
+ *   scores_ranked_dev f64 [n] scores[perm] (bits kept), correct_dev u8 [n]: 1 where pred_keys[perm[i]] is a ground-truth key
+ *   status_dev i64 [4]        {non-finite scores, adjacent equal keys in the sorted predictions, the same in the sorted ground
+ *                             truth, correct rows}; the first three are the reference's refusals ("Scores must be finite.",
+ *                             "Duplicates detected in ..."), which stay the caller's to raise: the call completes either way (a NaN
+ *                             orders by its bit pattern).
+ *   Sorts are stable 8-bit LSD radix sorts over tiles of VSC_UAP_TILE entries (the scheme of vsc_global_topk_f32 on 64-bit keys).
+ *
+ * vsc_uap_curve_f64: scores_ranked_dev / correct_dev [n] as written above, n_gt >= 1 the number of ground-truth pairs.  With
+ *   cum_i the inclusive count of correct rows and a tie group a maximal run of == scores ending at row last_j with tps_j = cum:
+ *   curve_dev f64 [3][n]      at the k-th correct row i (k = cum_i - 1): [0][k] = cum_i / (i + 1), [1][k] = cum_i / n_gt,
+ *                             [2][k] = score_i; the columns from n_pos on are not touched
+ *   counts_dev i64 [2]        {n_pos, n_groups}
+ *   sums_dev f64 [2]          [0] = np.sum([t_G, ..., t_1]), t_j = (R_j - R_{j-1}) P_j, R_j = tps_j / n_pos (R_0 = 0),
+ *                             P_j = tps_j / (last_j + 1) -- the order in which sklearn's average_precision_score sums its
+ *                             reversed curve; all t_j = 0 when n_pos = 0.  [1] = np.sum(cum_i / (i + 1) * correct_i) over the n
+ *                             rows.  np.sum of a float64 vector: consecutive chunks of 8192 elements (numpy's buffer size) are
+ *                             summed pairwise and the chunks' sums added one after the other, starting from 0.0.  Pairwise:
+ *                             below 8 elements a running sum from 0.0; up to 128 eight interleaved accumulators combined
+ *                             ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)) and the remainder added one by one; above, split at
+ *                             n2 = n / 2, n2 -= n2 % 8.  The divisions are IEEE fp64 divisions, nothing is contracted.
+ *   What the reference does next stays with the caller, in host floats: ap = max(0.0, sums[0]) * (n_pos / n_gt) (0.0 when
+ *   n_pos = 0), simple_ap = sums[1] / n_gt. */
+#define VSC_UAP_TILE 2048
+typedef struct vsc_uap vsc_uap;
+int vsc_uap_create(void *stream, vsc_uap **out);   /* every call of the handle enqueues on this stream */
+void vsc_uap_destroy(vsc_uap *h);
+int vsc_uap_rank_f64(vsc_uap *h, const double *scores_dev, const uint64_t *pred_keys_dev, int64_t n, const uint64_t *gt_keys_dev,
+                     int64_t g, int32_t key_bits, int64_t *perm_dev, double *scores_ranked_dev, uint8_t *correct_dev,
+                     int64_t *status_dev);
+int vsc_uap_curve_f64(vsc_uap *h, const double *scores_ranked_dev, const uint8_t *correct_dev, int64_t n, int64_t n_gt,
+                      double *sums_dev, int64_t *counts_dev, double *curve_dev);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

@@ -334,6 +334,10 @@ enum SearchScratchSlot {
     SCRATCH_GTK_KEYS = 26, SCRATCH_GTK_PAY = 27, SCRATCH_GTK_HIST = 28,   // survivors' keys / positions (two buffers each); [digit][tile] counters
     SCRATCH_PFH_KEYS = 29, SCRATCH_PFH_POS = 30,          // pair first hits: table keys, least position per key
     SCRATCH_PFH_FLAGS = 31, SCRATCH_PFH_BLOCKS = 32,      // first-hit flag per entry; flags per tile
+    // uap.hip; the two entries run one after the other and use the slots in turn
+    SCRATCH_UAP_STATE = 33,                               // rank: the four status counters
+    SCRATCH_UAP_KEYS = 34, SCRATCH_UAP_PAY = 35,          // rank: the sorts' two key buffers; two position buffers + the score keys.  curve: both term lists; (tps, last row) per tie group
+    SCRATCH_UAP_HIST = 36, SCRATCH_UAP_TREE = 37,         // rank: [digit][tile] counters.  curve: counts per tile; the pairwise trees' slots
     SCRATCH_SLOTS
 };
 // temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h

@@ -161,7 +161,7 @@ def main(args):
     print(f"{len(rows)} matches -> {args.output}")
     if getattr(args, "segment_metric", "none") == "hip" and getattr(args, "ground_truth", None):
         from vsc.metrics import evaluate_matching_track
-        metrics = evaluate_matching_track(args.ground_truth, args.output)
+        metrics = evaluate_matching_track(args.ground_truth, args.output, uap=getattr(args, "uap", "host"))
         print(f"Matching track metric: {metrics.segment_ap.ap:.4f}")
         print(f"Matching track pairwise uAP: {metrics.pairwise_micro_ap.ap:.4f}")
 
@@ -185,6 +185,9 @@ def build_parser():
     ap.add_argument("--segment_metric", choices=("none", "hip"), default="none",
                     help="with --ground_truth: score the written csv by the matching-track segment AP on the device "
                          "(vsc_segment_metric_*; the reference's evaluate_matching_track)")
+    ap.add_argument("--uap", choices=("host", "hip"), default="host",
+                    help="the pairwise uAP printed with --ground_truth and --segment_metric hip: the numpy mirror on the host or the "
+                         "device path (hip: vsc_uap_rank_f64 / vsc_uap_curve_f64, the reference's summation order)")
     ap.add_argument("--score_norm", choices=("host", "hip"), default="host",
                     help="step 1, the query score normalisation, in numpy on the host or on the device (hip; the same descriptors)")
     ap.add_argument("--output", required=True)

@@ -40,6 +40,7 @@ ALIGNMENTS = ("vcsl", "hip")
 CANDIDATES = ("host", "hip")
 SCORE_NORMS = ("host", "hip")
 SEGMENT_METRICS = ("none", "hip")
+UAPS = ("host", "hip")
 
 
 def localize_and_verify(queries: List[VideoFeature], refs: List[VideoFeature], candidates: List[CandidatePair],
@@ -115,7 +116,10 @@ def main(args) -> None:
         logger.info("Matches: %s", matches_file)
     if args.ground_truth:
         # the reference logs the canonical `.ap` (tied scores grouped), sscd_baseline.py:213-219
-        uap = average_precision(read_ground_truth_pairs(args.ground_truth), candidates)
+        uap_device = getattr(args, "uap", "host")                       # main() is also called with namespaces from before the option
+        if uap_device not in UAPS:
+            raise ValueError(f"uap {uap_device!r}: one of {UAPS}")
+        uap = average_precision(read_ground_truth_pairs(args.ground_truth), candidates, device=uap_device)
         logger.info("Candidate uAP: %.4f", uap.ap)
         print(f"Candidate uAP: {uap.ap:.4f}")
         segment_metric = getattr(args, "segment_metric", "none")       # main() is also called with namespaces from before the option
@@ -124,7 +128,7 @@ def main(args) -> None:
         if segment_metric == "hip" and matches_file:
             # sscd_baseline.py:224-225 of the matching track: evaluate_matching_track on the file just written
             from vsc.metrics import evaluate_matching_track
-            metrics = evaluate_matching_track(args.ground_truth, matches_file)
+            metrics = evaluate_matching_track(args.ground_truth, matches_file, uap=uap_device)
             logger.info("Matching track metric: %.4f", metrics.segment_ap.ap)
             logger.info("Matching track pairwise uAP: %.4f", metrics.pairwise_micro_ap.ap)
             print(f"Matching track metric: {metrics.segment_ap.ap:.4f}")
@@ -149,6 +153,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "references stay on the device as the search's bank)")
     ap.add_argument("--segment_metric", choices=SEGMENT_METRICS, default="none",
                     help="with --ground_truth and a written matches.csv: the matching-track segment AP on the device (hip)")
+    ap.add_argument("--uap", choices=UAPS, default="host",
+                    help="with --ground_truth: the micro-AP (Candidate uAP and, with --segment_metric hip, the pairwise uAP) by the numpy "
+                         "mirror on the host (host) or on the device in the reference's summation order (hip: vsc_uap_rank_f64 / "
+                         "vsc_uap_curve_f64)")
     return ap
 
 

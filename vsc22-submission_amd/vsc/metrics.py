@@ -1,6 +1,6 @@
 """The slice of the reference's vsc/metrics.py that the descriptor path touches:
 video-id formatting, candidate pairs, predicted matches (the rows of matches.csv) and the
-descriptor-track micro-AP (infer/vsc/metrics.py:21-119, 183-243, 423-494), and the matching-track
+descriptor-track micro-AP (infer/vsc/metrics.py:21-119, 183-243, 423-494; with device="hip" on the device, vsc_hip/uap.py), and the matching-track
 segment AP (VSC22-Matching-Track-1st/infer/vsc/metrics.py:120-420: match_metric, evaluate_matching_track), whose
 interval arithmetic runs on the device (vsc_hip/segment_metric.py) -- there is no CPU implementation of it here."""
 from __future__ import annotations
@@ -162,11 +162,22 @@ def drivendata_average_precision(predicted, ground_truth) -> float:
     return unadjusted * (predicted_n_pos / actual_n_pos)
 
 
+UAP_DEVICES = ("host", "hip")
+
+
 def average_precision(ground_truth: Collection[CandidatePair],
-                      predictions: Collection[CandidatePair]) -> AveragePrecision:
+                      predictions: Collection[CandidatePair], device: str = "host") -> AveragePrecision:
     """The descriptor-track uAP exactly as the reference reports it (metrics.py:423-455):
     `.ap` = drivendata_average_precision (tied scores grouped, rescaled), `.simple_ap` =
-    sum_i P(i) correct(i) / |gt| over the descending-score list, `.pr_curve` at the correct predictions."""
+    sum_i P(i) correct(i) / |gt| over the descending-score list, `.pr_curve` at the correct predictions.
+    device="host": the numpy mirror below, within 1e-12 of the reference (it sums the tie groups forward, sklearn sums them
+    reversed).  device="hip": sort, join, scans and sums on the device in the reference's summation order
+    (vsc_hip/uap.py) -- the reference's bits; needs a device."""
+    if device not in UAP_DEVICES:
+        raise ValueError(f"device {device!r}: one of {UAP_DEVICES}")
+    if device == "hip":
+        from vsc_hip.uap import average_precision_hip
+        return average_precision_hip(ground_truth, predictions)
     gt = {(p.query_id, p.ref_id) for p in ground_truth}
     if len(gt) != len(ground_truth):
         raise AssertionError("Duplicates detected in ground truth")
@@ -189,11 +200,13 @@ def average_precision(ground_truth: Collection[CandidatePair],
 
 
 def micro_average_precision(ground_truth: Collection[CandidatePair],
-                            predictions: Collection[CandidatePair]) -> float:
+                            predictions: Collection[CandidatePair], device: str = "host") -> float:
     """`average_precision(...).simple_ap` (kept for callers of earlier rounds); 0.0 for empty inputs."""
+    if device not in UAP_DEVICES:
+        raise ValueError(f"device {device!r}: one of {UAP_DEVICES}")
     if not len(predictions) or not len(ground_truth):
         return 0.0
-    return float(average_precision(ground_truth, predictions).simple_ap)
+    return float(average_precision(ground_truth, predictions, device=device).simple_ap)
 
 
 def match_metric(gts: Collection[Match], predictions: Collection[Match]) -> AveragePrecision:
@@ -214,12 +227,15 @@ class MatchingTrackMetrics:
     pairwise_micro_ap: AveragePrecision
 
 
-def evaluate_matching_track(ground_truth_filename: str, predictions_filename: str) -> MatchingTrackMetrics:
+def evaluate_matching_track(ground_truth_filename: str, predictions_filename: str, uap: str = "host") -> MatchingTrackMetrics:
     """metrics.py:394-420: both files are csvs with the columns query_id, ref_id, query_start, query_end, ref_start, ref_end
     (+ score for the predictions), in any order.  The numbers are parsed correctly rounded, so a file written by Match.write_csv
-    scores exactly as the list it was written from (pandas' default parser, which the reference uses, can be an ulp off)."""
+    scores exactly as the list it was written from (pandas' default parser, which the reference uses, can be an ulp off).
+    uap: where the pairwise micro-AP is computed ("host" | "hip", as average_precision's `device`)."""
+    if uap not in UAP_DEVICES:
+        raise ValueError(f"uap {uap!r}: one of {UAP_DEVICES}")
     gt = Match.read_csv(ground_truth_filename, is_gt=True, float_precision="round_trip")
     predictions = Match.read_csv(predictions_filename, float_precision="round_trip")
     metric = match_metric(gt, predictions)
-    pair_ap = average_precision(candidate_pairs_from_matches(gt), candidate_pairs_from_matches(predictions))
+    pair_ap = average_precision(candidate_pairs_from_matches(gt), candidate_pairs_from_matches(predictions), device=uap)
     return MatchingTrackMetrics(segment_ap=metric, pairwise_micro_ap=pair_ap)
