@@ -631,6 +631,42 @@ int vsc_uap_rank_f64(vsc_uap *h, const double *scores_dev, const uint64_t *pred_
 int vsc_uap_curve_f64(vsc_uap *h, const double *scores_ranked_dev, const uint8_t *correct_dev, int64_t n, int64_t n_gt,
                       double *sums_dev, int64_t *counts_dev, double *curve_dev);
 
+/* Near-duplicate frame filter of the query ensemble -- the reference's greedy pass over a video's frame x frame similarities
+ * (VSC22-Descriptor-Track-1st/infer/extract_query_feats.py:190-199; here src/query_postprocess.py: greedy_select) -- over the
+ * matrices of vsc_pair_similarity_f32, one workgroup per video, all videos of a call in one launch per VSC_FRAME_FILTER_CHUNK
+ * items.  Executable contract: tests/frame_filter_contract.py.
+ * sims_dev: fp32 similarities (sims_len floats); items_host [n_items][2] = {element offset, rows} (HOST memory): item p is the
+ * row-major [rows, rows] matrix s at sims_dev + offset (any element offset; matrices may be asymmetric).  threshold: float32.
+ * Item p owns the slice [P, P + rows) of kept_dev / means_dev / order_dev, P = the sum of the rows of the items before it.
+ *   v[i][j] = s[i][j] for i != j, v[i][i] = s[i][i] - 1.0f (fp32).
+ *   mean[j] = (((v[0][j] + v[1][j]) + v[2][j]) + ...) / (float)rows: one fp32 add chain per column over the rows in ascending
+ *     order that starts from v[0][j] itself, then one correctly rounded fp32 division -- sim.mean(0) of numpy for float32, bit
+ *     for bit (rows < 2^24; numpy starts from +0.0, which differs only on a column of nothing but -0.0, and v[j][j] is never -0.0).
+ *   Visit order: mean descending; EQUAL means are visited in DESCENDING index -- mean.argsort(kind="stable")[::-1].  -0.0 equals
+ *     +0.0.  The host path's argsort() is numpy's unstable sort and leaves the order of equal means to the numpy build: the
+ *     device equals the host path wherever a video's means are pairwise distinct, and this contract everywhere.
+ *   Greedy pass: removed = {}; for i in visit order, unless i is removed: every j with v[i][j] > threshold (ROW i, fp32 compare,
+ *     j = i included: it matters only for thresholds below about 0) becomes removed.  Kept = the rows not removed, ascending.
+ * Outputs (device): kept_dev int32: the first counts_dev[p] entries of the slice = the kept rows ascending, the rest -1;
+ * counts_dev int32 [n_items]; means_dev float (or NULL): mean[j]; order_dev int32 (or NULL): the visit order.  rows == 0 gives
+ * count 0 and touches nothing else; n_items == 0 launches nothing.  No atomics: the outputs are a pure function of the inputs.
+ * Refused (VSC_ERR_INVALID) before anything is launched: a null handle, rows above VSC_FRAME_FILTER_MAX_ROWS, an item that runs
+ * past sims_len, negative sizes, 2^31 or more rows in all, a null pointer that is needed, a non-finite threshold.  NaN
+ * similarities are outside the contract (they neither fault nor hang; the result is unspecified).
+ * Scratch: a video's adjacency bit matrix, 8 rows ceil(rows / 64) bytes, sits in LDS while 8 rows (1 + ceil(rows / 64)) <=
+ * VSC_FRAME_FILTER_LDS_BYTES (rows <= 1088); larger videos take that many bytes each, rounded up to 128, from the search path's
+ * grow-only per-device buffers (callers on one device are ordered; vsc_search_release_scratch frees them).  The entry takes a
+ * handle that holds the caller's stream (as vsc_score_norm and vsc_uap do) and only enqueues on it: the item table travels in
+ * kernel arguments, nothing is uploaded and the host never waits. */
+#define VSC_FRAME_FILTER_MAX_ROWS 4096
+#define VSC_FRAME_FILTER_CHUNK 128
+#define VSC_FRAME_FILTER_LDS_BYTES (160 * 1024 - 1024)
+typedef struct vsc_frame_filter vsc_frame_filter;
+int vsc_frame_filter_create(void *stream, vsc_frame_filter **out);   /* every call of the handle enqueues on this stream */
+void vsc_frame_filter_destroy(vsc_frame_filter *h);
+int vsc_frame_filter_f32(vsc_frame_filter *h, const float *sims_dev, int64_t sims_len, const int64_t *items_host, int64_t n_items,
+                         float threshold, int32_t *kept_dev, int32_t *counts_dev, float *means_dev, int32_t *order_dev);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

@@ -338,6 +338,7 @@ enum SearchScratchSlot {
     SCRATCH_UAP_STATE = 33,                               // rank: the four status counters
     SCRATCH_UAP_KEYS = 34, SCRATCH_UAP_PAY = 35,          // rank: the sorts' two key buffers; two position buffers + the score keys.  curve: both term lists; (tps, last row) per tie group
     SCRATCH_UAP_HIST = 36, SCRATCH_UAP_TREE = 37,         // rank: [digit][tile] counters.  curve: counts per tile; the pairwise trees' slots
+    SCRATCH_FRAME_FILTER_BITS = 38,                       // frame_filter.hip: adjacency bit matrices too large for LDS
     SCRATCH_SLOTS
 };
 // temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h
@@ -363,3 +364,6 @@ int launch_score_norm_rows(const float *x, int64_t n, int d, int64_t ldx, int dr
                            float *out, int64_t ldo, hipStream_t stream);
 int launch_score_norm_bias(const float *topk, int64_t nq, int64_t ldk, int nk, float neg_beta, const uint8_t *gate, float *bias,
                            hipStream_t stream);
+// greedy near-duplicate frame filter (frame_filter.hip), contract at vsc_frame_filter_f32 in include/vsc_hip.h
+int launch_frame_filter(const float *sims, int64_t sims_len, const int64_t *items_host, int64_t n_items, float threshold, int32_t *kept,
+                        int32_t *counts, float *means, int32_t *order, hipStream_t stream);

@@ -32,7 +32,7 @@ from src.matching import calclualte_low_var_dim
 from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
 from src.image_preprocess import HipViews
 from src.query_pipeline import RAW_KEY, VideoScorer, run_query_videos
-from src.query_postprocess import HipPCA, SCORE_THRESHOLD, load_pca_model
+from src.query_postprocess import FRAME_FILTERS, HipPCA, SCORE_THRESHOLD, load_pca_model
 from vsc.baseline.score_normalization import DEVICES as SCORE_NORMS, ScoreNormBank, query_score_normalize
 from vsc.metrics import Dataset
 from vsc.storage import load_features, store_features
@@ -115,7 +115,8 @@ def main(args):
     videos = zip_videos(vids, args.zip_prefix, sorted({size for _, size in encoders}), with_clip=scorer is not None,
                         workers=args.workers, preprocess=args.preprocess)
     finals, per_model = run_query_videos(videos, encoders, pca.transform, scores, device, score_threshold=args.score_threshold,
-                                         scorer=scorer, views=HipViews(device) if args.preprocess == "hip" else None)
+                                         scorer=scorer, views=HipViews(device) if args.preprocess == "hip" else None,
+                                         frame_filter=getattr(args, "frame_filter", "host"))   # (a hand-built namespace from before the option)
     for i, (_, _, path) in enumerate(specs):
         key = os.path.split(path)[-1].split(".")[0]
         os.makedirs(os.path.join(args.output_dir, key), exist_ok=True)
@@ -153,6 +154,10 @@ def build_parser():
                     help="hip: crop static borders and split stacked views on the GPU before encoding (the reference's image_process)")
     ap.add_argument("--score_norm", default="host", choices=SCORE_NORMS,
                     help="with --norm_refs: the query score normalisation in numpy on the host, or on the device (hip; the same file)")
+    ap.add_argument("--frame_filter", default="host", choices=FRAME_FILTERS,
+                    help="the near-duplicate frame filter in numpy on the host, or on the device (hip: the similarity matrices are not "
+                         "downloaded); the same files wherever a video's frame means are pairwise distinct -- equal means are visited in "
+                         "descending index on the device and in numpy's unspecified order on the host")
     return ap
 
 

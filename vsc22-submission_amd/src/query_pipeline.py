@@ -11,7 +11,7 @@ from typing import Callable, Dict, Iterable, List, Sequence, Tuple
 import numpy as np
 import torch
 
-from src.query_postprocess import HipOps, SCORE_THRESHOLD, process_query_group, process_query_video
+from src.query_postprocess import FRAME_FILTERS, HipOps, SCORE_THRESHOLD, process_query_group, process_query_video
 from vsc.index import VideoFeature
 
 RAW_KEY = "raw"   # frames_by_size key of a video's full-resolution uint8 frames [n, H, W, 3] (--preprocess hip)
@@ -245,7 +245,7 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
                      pca_transform: Callable[[np.ndarray], np.ndarray], video_scores: Dict[str, float], device,
                      ops=HipOps, score_threshold: float = SCORE_THRESHOLD, chunk: int = None,
                      scorer: Callable[[torch.Tensor], float] = None,
-                     group_frames: int = 4096, views=None) -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
+                     group_frames: int = 4096, views=None, frame_filter: str = "host") -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
     """videos yields (video_id, {image_size: frames [S,3,size,size]}, timestamps); encoders = [(model, image_size)].
     ``views`` (``--preprocess hip``, src.image_preprocess.HipViews): videos that carry full-resolution frames under ``RAW_KEY``
     are replaced by their views first (border removal and split views, ``_with_views``): k views of n frames encode as k * n rows.
@@ -254,7 +254,13 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
     Backbones run over groups of consecutive videos (>= ``group_frames`` frames) so their launches stay large and the ragged last chunk of a
     group (16 / 138 / 20 frames at 512 / 902 / 510 per call) is paid once per 4 096 frames: 208 videos x 40 frames end to end at 0.904 / 0.966 /
     0.978 / 0.954 of encoder-bound with groups of 1 024 / 2 048 / 4 096 / 8 192 frames (the last: one group, no look-ahead; tools/micro/ensemble_group_scan.sh).
+    ``frame_filter``: "host" or "hip" (src.query_postprocess.FRAME_FILTERS): where the near-duplicate frame filter runs; "hip" needs
+    the library's own ops.
     -> (final descriptors per video, per-model VideoFeatures per video), in input order."""
+    if frame_filter not in FRAME_FILTERS:
+        raise ValueError(f"frame_filter must be one of {FRAME_FILTERS}, not {frame_filter!r}")
+    if frame_filter == "hip" and ops is not HipOps:
+        raise ValueError("frame_filter='hip' needs the library's own ops (HipOps); other ops take frame_filter='host'")
     finals, per_model = [], []
     rnd_idx = 0
     if views is not None:
@@ -285,7 +291,8 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
                 vals = probs.cpu().tolist() if torch.is_tensor(probs) else list(probs)
                 video_scores.update({v[0]: float(sc) for v, sc in zip(group, vals)})
             f, pm, rnd_idx = process_query_group([v[0] for v in group], subs_by_model, [np.asarray(v[2]) for v in group],
-                                                 [video_scores.get(v[0], 1.0) for v in group], pca_transform, rnd_idx, score_threshold)
+                                                 [video_scores.get(v[0], 1.0) for v in group], pca_transform, rnd_idx, score_threshold,
+                                                 frame_filter=frame_filter)
             finals.extend(f)
             per_model.extend(pm)
 
@@ -313,7 +320,8 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
         for i, (video_id, frames_by_size, timestamps) in enumerate(group):
             subs = [m[i] for m in subs_by_model]
             feat, sub_feats, rnd_idx = process_query_video(video_id, subs, np.asarray(timestamps), video_scores.get(video_id, 1.0),
-                                                           pca_transform, rnd_idx, ops=ops, score_threshold=score_threshold)
+                                                           pca_transform, rnd_idx, ops=ops, score_threshold=score_threshold,
+                                                           frame_filter=frame_filter)
             finals.append(feat)
             per_model.append(sub_feats)
     return finals, per_model

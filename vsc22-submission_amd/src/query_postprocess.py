@@ -21,6 +21,37 @@ from vsc.index import VideoFeature
 
 SCORE_THRESHOLD = 0.001   # extract_query_feats.py:53
 FRAME_THRESHOLD = 0.975   # :55
+# where the greedy near-duplicate filter runs: "host" (numpy on the downloaded matrices, the default) or "hip" (vsc_frame_filter_f32:
+# the matrices stay on the device).  Equal wherever a video's frame means are pairwise distinct; equal means are visited in descending
+# index on the device, in whatever order numpy's unstable argsort yields on the host.
+FRAME_FILTERS = ("host", "hip")
+
+
+def _check_frame_filter(frame_filter: str) -> str:
+    if frame_filter not in FRAME_FILTERS:
+        raise ValueError(f"frame_filter must be one of {FRAME_FILTERS}, not {frame_filter!r}")
+    return frame_filter
+
+
+def check_filter_rows(video_id, rows: int) -> None:
+    """``frame_filter="hip"``: a video above the entry's row limit is refused by name before anything is launched."""
+    from vsc_hip.ops import FRAME_FILTER_MAX_ROWS
+    if rows > FRAME_FILTER_MAX_ROWS:
+        raise ValueError(f"frame_filter='hip': video {video_id} has {rows} descriptor rows (frames x views), the device filter "
+                         f"takes at most {FRAME_FILTER_MAX_ROWS}; use frame_filter='host'")
+
+
+def device_filter(flat, items, frame_threshold: float = FRAME_THRESHOLD) -> List[np.ndarray]:
+    """One vsc_frame_filter_f32 launch over the matrices ``items`` = [(element offset, rows)] of the flat device tensor ``flat`` and
+    ONE device -> host copy (counts and kept rows together) -> the kept row numbers of every item, ascending."""
+    import torch
+    from vsc_hip import ops
+    items = np.asarray(items, dtype=np.int64).reshape(-1, 2)
+    kept, counts = ops.frame_filter(flat, items, frame_threshold)
+    both = torch.cat([counts, kept]).cpu().numpy()
+    n = len(items)
+    starts = np.concatenate([[0], np.cumsum(items[:, 1])])
+    return [both[n + starts[k]:n + starts[k] + both[k]] for k in range(n)]
 
 
 class HipOps:
@@ -131,8 +162,21 @@ def greedy_select(sim: np.ndarray, frame_threshold: float = FRAME_THRESHOLD) -> 
     return [i for i in range(len(sim)) if i not in removed]
 
 
-def select_frames(features: np.ndarray, ops=HipOps, frame_threshold: float = FRAME_THRESHOLD) -> List[int]:
-    """Indices kept by the greedy near-duplicate filter (:197-207)."""
+def select_frames(features: np.ndarray, ops=HipOps, frame_threshold: float = FRAME_THRESHOLD, frame_filter: str = "host",
+                  video_id: str = "?") -> List[int]:
+    """Indices kept by the greedy near-duplicate filter (:197-207).  ``frame_filter="hip"``: the same launches, then the filter on
+    the device (library ops only); L int32 come back instead of the L x L matrix."""
+    if _check_frame_filter(frame_filter) == "hip":
+        import torch
+        from vsc_hip import ops as hip_ops
+        if ops is not HipOps:
+            raise ValueError("frame_filter='hip' needs the library's own ops (HipOps)")
+        check_filter_rows(video_id, len(features))
+        if len(features) == 0:
+            return []
+        feat = hip_ops.l2_normalize_(torch.from_numpy(np.ascontiguousarray(features, np.float32)).cuda())
+        flat, _ = hip_ops.pair_similarity(feat, feat, np.array([[0, feat.shape[0], 0, feat.shape[0]]], dtype=np.int64))
+        return device_filter(flat, [(0, feat.shape[0])], frame_threshold)[0].tolist()
     feat = ops.normalize(features)
     sim = ops.self_similarity(feat) - np.eye(len(feat), dtype=np.float32)
     return greedy_select(sim, frame_threshold)
@@ -140,8 +184,9 @@ def select_frames(features: np.ndarray, ops=HipOps, frame_threshold: float = FRA
 
 def process_query_video(video_id: str, sub_features: Sequence[np.ndarray], timestamps: np.ndarray, score: float,
                         pca_transform: Callable[[np.ndarray], np.ndarray], rnd_idx: int, ops=HipOps,
-                        score_threshold: float = SCORE_THRESHOLD) -> Tuple[VideoFeature, List[VideoFeature], int]:
+                        score_threshold: float = SCORE_THRESHOLD, frame_filter: str = "host") -> Tuple[VideoFeature, List[VideoFeature], int]:
     """-> (descriptor for the video, per-model VideoFeatures, updated rnd_idx)."""
+    _check_frame_filter(frame_filter)
     subs = [ops.normalize(f) for f in sub_features]
     features = np.concatenate(subs, axis=1)
     ratio = len(features) // len(timestamps)
@@ -149,7 +194,7 @@ def process_query_video(video_id: str, sub_features: Sequence[np.ndarray], times
     assert len(stamps) == len(features)
     per_model = [VideoFeature(video_id=video_id, timestamps=stamps, feature=s) for s in subs]
     if score >= score_threshold:
-        keep = select_frames(features, ops)
+        keep = select_frames(features, ops, frame_filter=frame_filter, video_id=video_id)
         return VideoFeature(video_id=video_id, timestamps=stamps[keep],
                             feature=pca_transform(features[keep])), per_model, rnd_idx
     rnd_idx += 1
@@ -162,17 +207,24 @@ def process_query_video(video_id: str, sub_features: Sequence[np.ndarray], times
 
 
 def process_query_group(video_ids: Sequence[str], subs_by_model: Sequence[Sequence], timestamps: Sequence[np.ndarray], scores: Sequence[float],
-                        pca_transform: Callable, rnd_idx: int, score_threshold: float = SCORE_THRESHOLD):
+                        pca_transform: Callable, rnd_idx: int, score_threshold: float = SCORE_THRESHOLD, frame_filter: str = "host"):
     """``process_query_video`` for a whole group of videos with the device work batched: subs_by_model[i][v] is model i's
     feature tensor of video v ON THE DEVICE (encode_group(as_numpy=False)).  One normalisation launch per model, one launch for
     all the videos' frame x frame similarity blocks, one for the PCA of every kept row, four device -> host copies per group --
     per video that was four normalisations, a similarity and a PCA, each a host -> device -> host round trip.
     Row-wise kernels and per-block fma chains: the results equal the per-video path bit for bit.
+    ``frame_filter="hip"``: the similarity blocks stay on the device and one vsc_frame_filter_f32 launch filters every accepted video;
+    4 sum(L) bytes come back instead of 4 sum(L^2), and no Python loop runs per frame.
     -> ([descriptor per video], [per-model VideoFeatures per video], updated rnd_idx)"""
     import torch
     from vsc_hip import ops
+    _check_frame_filter(frame_filter)
     n_vid = len(video_ids)
     lens = [int(subs_by_model[0][v].shape[0]) for v in range(n_vid)]
+    if frame_filter == "hip":
+        for v in range(n_vid):
+            if scores[v] >= score_threshold:
+                check_filter_rows(video_ids[v], lens[v])
     offs = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
     subs_dev = []
     if sum(lens) == 0:      # a group made only of frameless videos: nothing to normalise or compare; every video gets the placeholder below
@@ -188,12 +240,18 @@ def process_query_group(video_ids: Sequence[str], subs_by_model: Sequence[Sequen
         feat2 = ops.l2_normalize_(features.clone())
         pairs = np.array([[offs[v], lens[v], offs[v], lens[v]] for v in accepted], dtype=np.int64)
         flat, poff = ops.pair_similarity(feat2, feat2, pairs)
-        flat = flat.cpu().numpy()
-        for k, v in enumerate(accepted):
-            sim = flat[poff[k]:poff[k + 1]].reshape(lens[v], lens[v]) - np.eye(lens[v], dtype=np.float32)
-            keep = greedy_select(sim)
-            kept_per_video[v] = keep
-            keep_rows.extend(int(offs[v]) + i for i in keep)
+        if frame_filter == "hip":
+            for v, keep in zip(accepted, device_filter(flat, [(poff[k], lens[v]) for k, v in enumerate(accepted)])):
+                kept_per_video[v] = keep
+                keep_rows.append(keep.astype(np.int64) + int(offs[v]))
+            keep_rows = np.concatenate(keep_rows)
+        else:
+            flat = flat.cpu().numpy()
+            for k, v in enumerate(accepted):
+                sim = flat[poff[k]:poff[k + 1]].reshape(lens[v], lens[v]) - np.eye(lens[v], dtype=np.float32)
+                keep = greedy_select(sim)
+                kept_per_video[v] = keep
+                keep_rows.extend(int(offs[v]) + i for i in keep)
         idx = torch.from_numpy(np.asarray(keep_rows, dtype=np.int64)).to(features.device)
         kept = features.index_select(0, idx)
         owner = getattr(pca_transform, "__self__", None)

@@ -459,6 +459,47 @@ def match_maps(sims, items, resolution: int, with_transpose: bool, out=None):
     return out.permute(0, 3, 1, 2), view_start
 
 
+FRAME_FILTER_MAX_ROWS = 4096      # VSC_FRAME_FILTER_MAX_ROWS of include/vsc_hip.h
+_frame_filter_handles = {}
+
+
+def frame_filter_handle():
+    """The vsc_frame_filter handle of the current library on the current stream (made on first use, kept for the process: it is
+    the stream and owns no device memory)."""
+    import ctypes
+    lib = _rd()
+    stream = current_stream()
+    key = (_PRECISION, stream.value or 0)
+    if key not in _frame_filter_handles:
+        h = ctypes.c_void_p()
+        check(lib.vsc_frame_filter_create(stream, ctypes.byref(h)))
+        _frame_filter_handles[key] = h
+    return _frame_filter_handles[key]
+
+
+def frame_filter(sims, items, threshold: float, want_means: bool = False):
+    """Greedy near-duplicate frame filter of every frame x frame matrix of a flat fp32 device tensor, one launch per 128 videos and
+    no host synchronisation.  sims: flat float32 device tensor (ops.pair_similarity's); items: int64 [n, 2] rows (element offset,
+    rows) on the host; threshold: compared as float32.  -> (kept int32 [sum rows], counts int32 [n]) on the device, and with
+    want_means also (means float32 [sum rows], order int32 [sum rows]): video p owns the slice at the prefix sum of the rows; the
+    first counts[p] entries of its kept slice are the kept rows ascending, the rest -1.  Equal frame means are visited in
+    descending index.  Contract, limits and refusals: vsc_frame_filter_f32 in include/vsc_hip.h."""
+    import numpy as np
+    lib = _rd()
+    sims = _dev(sims, torch.float32).reshape(-1)
+    items = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1, 2))
+    n = items.shape[0]
+    total = int(items[:, 1].clip(min=0).sum())
+    kept = torch.empty(total, dtype=torch.int32, device=sims.device)
+    counts = torch.empty(n, dtype=torch.int32, device=sims.device)
+    means = torch.empty(total, dtype=torch.float32, device=sims.device) if want_means else None
+    order = torch.empty(total, dtype=torch.int32, device=sims.device) if want_means else None
+    opt = lambda t: ptr(t) if t is not None and t.numel() else None     # noqa: E731
+    check(lib.vsc_frame_filter_f32(frame_filter_handle(), opt(sims), sims.numel(), items.ctypes.data, n, float(threshold), opt(kept),
+                                   opt(counts), opt(means), opt(order)))
+    return (kept, counts, means, order) if want_means else (kept, counts)
+
+
 def _frames_u8(frames):
     assert frames.is_cuda and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3, \
         "frames must be uint8 [n, H, W, 3] on the GPU"
