@@ -430,7 +430,8 @@ int vsc_match_maps_f32(const float *sims_dev, int64_t sims_len, const int64_t *i
 
 /* Query view preprocessing -- the reference's image_process (VSC22-Descriptor-Track-1st/infer/src/image_preprocess.py:252-275,
  * applied to every query video by infer/src/dataset.py:82-88): the two per-video maps its border / split decisions read, and the
- * crop + resize of every view.  The decisions themselves run on the host (src/image_preprocess.py).  frames_dev: uint8
+ * crop + resize of every view.  The decisions themselves run on the host (src/image_preprocess.py) or, opt-in, in
+ * vsc_view_decide_f64 below.  frames_dev: uint8
  * [n][h][w][3] (RGB, row-major) on the device.
  *
  * Variance map, image_preprocess.py:255-256 (np.stack(frames).var(axis=0).sum(-1)), bit-identical to numpy: out_dev float64
@@ -666,6 +667,49 @@ int vsc_frame_filter_create(void *stream, vsc_frame_filter **out);   /* every ca
 void vsc_frame_filter_destroy(vsc_frame_filter *h);
 int vsc_frame_filter_f32(vsc_frame_filter *h, const float *sims_dev, int64_t sims_len, const int64_t *items_host, int64_t n_items,
                          float threshold, int32_t *kept_dev, int32_t *counts_dev, float *means_dev, int32_t *order_dev);
+
+/* View decisions of the query preprocessing -- the reference's remove_edges, split_imgs and the recursive clean_imgs
+ * (VSC22-Descriptor-Track-1st/infer/src/image_preprocess.py; here src/image_preprocess.py: decide_views and the _borders, _trim,
+ * _static_side, _bands, _line_cuts, _split and _clean it calls) -- on the two maps where vsc_frame_var_u8 and vsc_canny_count_u8
+ * wrote them, one workgroup per video, all videos of a call in one launch per VSC_VIEW_DECIDE_CHUNK items.  Executable contract:
+ * tests/view_decide_contract.py.
+ * var_dev: float64 variances (var_len doubles); count_dev: uint16 edge counts (count_len values); items_host [n_items][6] =
+ * {element offset of the item's dense [h][w] variance map, element offset of its count map, h, w, m, n} (HOST memory; any element
+ * offsets): m = the number of Canny samples behind the counts (counts above m are outside the contract: no fault, result
+ * unspecified), n = the video's frames.
+ * Outputs (device): boxes_dev int32 [n_items][max_views][4] = {y0, y1, x0, x1} of the views in the reference's order, the rest -1;
+ * counts_dev int32 [n_items]; status_dev int32 [n_items]: 0 decided; 1 the item needs more than max_views views or more than
+ * VSC_VIEW_DECIDE_STACK pending regions: count 0, every box -1, and the caller decides it on the host.  An unchanged video is one box
+ * equal to the whole frame.  n < 5 gives the whole frame without reading the maps.  trace_dev (or NULL): float64 [n_items][8], for
+ * the whole-frame _borders call np.quantile(avg, 0.95), avg.mean(), the threshold, edges.mean(), var.mean(1)[h / 2],
+ * var.mean(0)[w / 2], edges.mean(1)[h / 2], edges.mean(0)[w / 2] (float32 values widened); an item with n < 5 leaves its row alone.
+ * Arithmetic: the host path's, which is numpy's (2.2), bit for bit -- avg = count / m in fp64;
+ *   a.mean(1): numpy's pairwise sum per row (under 8 elements a chain from 0.0; up to 128 eight strided accumulators combined
+ *     ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), then the remainder in order; above that split at n / 2 rounded down to a multiple of 8),
+ *     then one division;  a.mean(0): one add chain per column in row order from 0.0, then one division -- a region one column
+ *     wide is summed pairwise down the column;  a.mean() of a region: its row-major flattening in chunks of 8192, pairwise inside,
+ *     the chunk sums chained from 0.0;  np.quantile(avg, 0.95): pos = (N - 1) * 0.95, lo = floor(pos), t = pos - lo, A and B the
+ *     order statistics lo and min(lo + 1, N - 1) (from the (m + 1)-bin histogram), A + (B - A) t below t = 0.5, else
+ *     B - (B - A)(1 - t);  np.median: the middle order statistic, or (a + b) / 2 of the two middle ones;  the edge map is 0/1
+ *     float32: its sums are integer counts, its means float32(count) / float32(size);  float32 too: 0.125 + edge_p.mean(),
+ *     0.45 + edges.mean(), edge_p.mean() < 0.0225 (a float32 pairwise sum), edge_at > 0.65;  round((i - first) * 0.3): the fp64
+ *     product rounded half to even.  No float atomics: the outputs are a pure function of the inputs.
+ * Refused (VSC_ERR_INVALID) before anything is launched -- a bad item after a good one launches nothing: a null handle, h or w
+ * outside 1..VSC_VIEW_DECIDE_MAX_SIDE, m outside 1..VSC_VIEW_DECIDE_MAX_SAMPLES, max_views outside 1..VSC_VIEW_DECIDE_MAX_VIEWS,
+ * negative n, a map that runs past var_len / count_len, a null pointer that is needed.  NaN variances are outside the contract.
+ * No scratch: the four profiles and a work array take 32 max(h, w) bytes of LDS.  The entry takes a handle that holds the caller's
+ * stream and only enqueues on it: the item table travels in kernel arguments, nothing is uploaded and the host never waits. */
+#define VSC_VIEW_DECIDE_MAX_SIDE 4096
+#define VSC_VIEW_DECIDE_MAX_SAMPLES 255
+#define VSC_VIEW_DECIDE_MAX_VIEWS 64
+#define VSC_VIEW_DECIDE_STACK 64
+#define VSC_VIEW_DECIDE_CHUNK 64
+typedef struct vsc_view_decide vsc_view_decide;
+int vsc_view_decide_create(void *stream, vsc_view_decide **out);   /* every call of the handle enqueues on this stream */
+void vsc_view_decide_destroy(vsc_view_decide *h);
+int vsc_view_decide_f64(vsc_view_decide *h, const double *var_dev, int64_t var_len, const uint16_t *count_dev, int64_t count_len,
+                        const int64_t *items_host, int64_t n_items, int32_t max_views, int32_t *boxes_dev, int32_t *counts_dev,
+                        int32_t *status_dev, double *trace_dev);
 
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.

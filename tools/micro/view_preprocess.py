@@ -1,12 +1,16 @@
 """Query view preprocessing (--preprocess hip) on the GPU box: per-video cost of detection and resize, the CPU cost of the parts that
 have a faithful CPU form, and run_query_videos with --preprocess none vs hip on plain videos through the reference's ensemble.
 
-    python tools/micro/view_preprocess.py [--frames 40] [--videos 52] [--skip-ensemble]
+    python tools/micro/view_preprocess.py [--frames 40] [--videos 52] [--skip-ensemble] [--skip-kernels]
 
 Detection = vsc_frame_var_u8 + vsc_canny_count_u8 (20 sampled frames) + one device -> host copy of both maps + the host decisions
 (src/image_preprocess.detect_views); resize = vsc_resize_bicubic_u8 of one whole-frame view to 256 and to 384.  Kernel times come
 from device events (median of 5 after a warm-up), detection's wall time from the host.  Canny's CPU cost under cv2 is not measured:
-cv2 is not installed in this project's environments."""
+cv2 is not installed in this project's environments.
+
+The decisions table (profiles/view_decide_bench.txt) compares ``detect_views`` with the decisions on the host and on the device
+(vsc_view_decide_f64), alternating on plain and letterboxed videos, next to the device time of the decide launch alone; the
+ensemble then runs with --preprocess none, hip with host decisions and hip with device decisions."""
 import argparse
 import os
 import sys
@@ -36,6 +40,47 @@ def plain_frames(n, h, w, seed=0):
             img[y0:y0 + h // 6, x0:x0 + w // 6] = rng.integers(0, 60)
         out[i] = np.clip(img, 0, 255).astype(np.uint8)
     return out
+
+
+def letterbox_frames(n, h, w, seed=0):
+    """plain_frames with a static black band of h / 8 lines above and below"""
+    out = plain_frames(n, h, w, seed)
+    out[:, :h // 8] = 16
+    out[:, h - h // 8:] = 16
+    return out
+
+
+def decisions(n_frames):
+    """detect_views per video with host and with device decisions, alternating, median of 5 wall times each; beside it the device
+    time of the decide launch alone (maps already on the device)"""
+    from src.image_preprocess import canny_frames, detect_views
+    from vsc_hip import ops
+    idx = canny_frames(n_frames)
+    print(f"decisions: {n_frames}-frame videos, detect_views wall ms per video (median of 5, host and device decisions alternating), "
+          f"the decide launch alone from device events (median of 5)", flush=True)
+    rows = []
+    for kind, make in (("plain", plain_frames), ("letterbox", letterbox_frames)):
+        for name, (h, w) in RES.items():
+            d = torch.from_numpy(make(n_frames, h, w)).cuda()
+            want = detect_views(d)
+            assert detect_views(d, decisions="hip") == want, (kind, name)
+            torch.cuda.synchronize()
+            walls = {"host": [], "hip": []}
+            for _ in range(5):
+                for mode in ("host", "hip"):
+                    t0 = time.perf_counter()
+                    detect_views(d, decisions=mode)
+                    walls[mode].append((time.perf_counter() - t0) * 1e3)
+            var, count = ops.view_maps_dev(d, idx)
+            item = [(0, 0, h, w, len(idx), n_frames)]
+            launch_ms = event_ms(lambda: ops.view_decide(var, count, item))
+            maps_ms = event_ms(lambda: ops.view_maps_dev(d, idx))
+            row = dict(kind=kind, res=name, views=len(want[1]), changed=want[0], host_wall_ms=float(np.median(walls["host"])),
+                       hip_wall_ms=float(np.median(walls["hip"])), decide_launch_ms=launch_ms, maps_ms=maps_ms)
+            row["hip_over_host"] = row["hip_wall_ms"] / row["host_wall_ms"]
+            rows.append(row)
+            print(" ".join(f"{k}={v:.3f}" if isinstance(v, float) else f"{k}={v}" for k, v in row.items()), flush=True)
+    return rows
 
 
 def event_ms(fn, reps=5):
@@ -92,8 +137,8 @@ def per_video(n_frames):
 
 
 def ensemble(n_videos, n_frames, res):
-    """run_query_videos on plain videos, alternating --preprocess none (frames resized on the host beforehand, as the workers do) and
-    hip (full-resolution frames; upload, detection and resize inside run_query_videos)"""
+    """run_query_videos on plain videos, alternating --preprocess none (frames resized on the host beforehand, as the workers do),
+    hip (full-resolution frames; upload, detection and resize inside run_query_videos) and hip with the decisions on the device"""
     from PIL import Image
     from src.dataset import clip_transform_u8, vit_transform_u8
     from src.image_preprocess import HipViews
@@ -114,20 +159,21 @@ def ensemble(n_videos, n_frames, res):
     made = {k: v.repeat(reps, 1, 1, 1)[:n_frames].clone() for k, v in made.items()}
     none_items = [(f"Q{v:06d}", dict(made), np.arange(n_frames)) for v in range(n_videos)]
     hip_items = [(f"Q{v:06d}", {RAW_KEY: raw, "clip": made["clip"]}, np.arange(n_frames)) for v in range(n_videos)]
-    views = HipViews(dev)
-    rates = {"none": [], "hip": []}
+    views = {"hip": HipViews(dev), "hip_device": HipViews(dev, decisions="hip")}
+    rates = {"none": [], "hip": [], "hip_device": []}
     for rep in range(4):
-        for mode in ("none", "hip"):
+        for mode in rates:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             run_query_videos(none_items if mode == "none" else hip_items, encoders, pca.transform, {}, dev, scorer=m["scorer"],
-                             views=views if mode == "hip" else None)
+                             views=views.get(mode))
             torch.cuda.synchronize()
             if rep:
                 rates[mode].append(n_videos * n_frames / (time.perf_counter() - t0))
     r = {k: float(np.median(v)) for k, v in rates.items()}
     print(f"ensemble {res}: {n_videos} x {n_frames} frames, none {r['none']:.0f} frames/s, hip {r['hip']:.0f} frames/s "
-          f"(hip / none = {r['hip'] / r['none']:.3f})", flush=True)
+          f"(hip / none = {r['hip'] / r['none']:.3f}), hip with device decisions {r['hip_device']:.0f} frames/s "
+          f"(/ none = {r['hip_device'] / r['none']:.3f}, / hip = {r['hip_device'] / r['hip']:.3f})", flush=True)
     return r
 
 
@@ -136,11 +182,15 @@ def main():
     ap.add_argument("--frames", type=int, default=40)
     ap.add_argument("--videos", type=int, default=52)
     ap.add_argument("--skip-ensemble", action="store_true")
+    ap.add_argument("--skip-kernels", action="store_true", help="only the decisions table and the ensemble")
     ap.add_argument("--ensemble-res", nargs="+", default=["360p", "720p"])
     args = ap.parse_args()
     from vsc_hip import _lib
     _lib.require_device()
-    per_video(args.frames)
+    print(f"tools/micro/view_preprocess.py on {torch.cuda.get_device_name(0)}", flush=True)
+    if not args.skip_kernels:
+        per_video(args.frames)
+    decisions(args.frames)
     if not args.skip_ensemble:
         for res in args.ensemble_res:
             ensemble(args.videos, args.frames, res)

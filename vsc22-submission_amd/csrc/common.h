@@ -367,3 +367,6 @@ int launch_score_norm_bias(const float *topk, int64_t nq, int64_t ldk, int nk, f
 // greedy near-duplicate frame filter (frame_filter.hip), contract at vsc_frame_filter_f32 in include/vsc_hip.h
 int launch_frame_filter(const float *sims, int64_t sims_len, const int64_t *items_host, int64_t n_items, float threshold, int32_t *kept,
                         int32_t *counts, float *means, int32_t *order, hipStream_t stream);
+// view decisions of the query preprocessing on the device's own maps (view_decide.hip), contract at vsc_view_decide_f64 in include/vsc_hip.h
+int launch_view_decide(const double *var, int64_t var_len, const uint16_t *count, int64_t count_len, const int64_t *items_host, int64_t n_items,
+                       int max_views, int32_t *boxes, int32_t *counts, int32_t *status, double *trace, hipStream_t stream);

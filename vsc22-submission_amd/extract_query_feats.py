@@ -30,7 +30,7 @@ import torch
 from src.dataset import CLIP_MEAN, CLIP_STD, clip_transform_u8, vit_transform_u8
 from src.matching import calclualte_low_var_dim
 from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
-from src.image_preprocess import HipViews
+from src.image_preprocess import HipViews, VIEW_DECISIONS
 from src.query_pipeline import RAW_KEY, VideoScorer, run_query_videos
 from src.query_postprocess import FRAME_FILTERS, HipPCA, SCORE_THRESHOLD, load_pca_model
 from vsc.baseline.score_normalization import DEVICES as SCORE_NORMS, ScoreNormBank, query_score_normalize
@@ -115,7 +115,7 @@ def main(args):
     videos = zip_videos(vids, args.zip_prefix, sorted({size for _, size in encoders}), with_clip=scorer is not None,
                         workers=args.workers, preprocess=args.preprocess)
     finals, per_model = run_query_videos(videos, encoders, pca.transform, scores, device, score_threshold=args.score_threshold,
-                                         scorer=scorer, views=HipViews(device) if args.preprocess == "hip" else None,
+                                         scorer=scorer, views=HipViews(device, getattr(args, "view_decisions", "host")) if args.preprocess == "hip" else None,
                                          frame_filter=getattr(args, "frame_filter", "host"))   # (a hand-built namespace from before the option)
     for i, (_, _, path) in enumerate(specs):
         key = os.path.split(path)[-1].split(".")[0]
@@ -152,6 +152,9 @@ def build_parser():
     ap.add_argument("--workers", type=int, default=6, help="decode / resize worker processes (the reference uses 6)")
     ap.add_argument("--preprocess", default="none", choices=["none", "hip"],
                     help="hip: crop static borders and split stacked views on the GPU before encoding (the reference's image_process)")
+    ap.add_argument("--view_decisions", default="host", choices=VIEW_DECISIONS,
+                    help="with --preprocess hip: the border / split decisions in numpy on the host (both maps are downloaded), or on "
+                         "the device (hip: only the boxes come back; the same boxes, hence the same files)")
     ap.add_argument("--score_norm", default="host", choices=SCORE_NORMS,
                     help="with --norm_refs: the query score normalisation in numpy on the host, or on the device (hip; the same file)")
     ap.add_argument("--frame_filter", default="host", choices=FRAME_FILTERS,

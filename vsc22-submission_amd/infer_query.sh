@@ -2,6 +2,7 @@
 # Query-side extraction (stands where the reference's infer/infer_query.sh stands): ensemble + video-score gate + de-duplication + PCA +
 # query score normalisation, per split.  PREPROCESS=hip crops static borders and splits stacked views on the GPU first (the reference's
 # image_process); the default, none, encodes whole frames.  SCORE_NORM=hip runs the query score normalisation on the GPU (the same file).
+# VIEW_DECISIONS=hip (with PREPROCESS=hip) takes the border / split decisions on the GPU too: only the boxes come back (the same files).
 # FRAME_FILTER=hip runs the near-duplicate frame filter on the GPU (the same files wherever a video's frame means are pairwise distinct).
 #   CKPT=../checkpoints ZIPS=../data/jpg_zips META=../data/meta bash infer_query.sh
 set -e
@@ -18,6 +19,6 @@ for split in ${SPLITS:-train val test}; do
              "swinv2_base_256:swin_ref:$CKPT/swinv2_v106.torchscript.pt" "vit_v68:timm_vit:$CKPT/vit_v68.torchscript.pt" \
     --pca_model "$PCA_MODEL" --zip_prefix "$ZIPS" --input_file "$META/$split/${split}_query_ids.txt" --norm_refs "$NORM" \
     --clip_checkpoint "$CKPT/clip.torchscript.pt" --vsm_checkpoint "$CKPT/vsm.torchscript.pt" --output_dir "$OUT" \
-    --preprocess "${PREPROCESS:-none}" --score_norm "${SCORE_NORM:-host}" \
+    --preprocess "${PREPROCESS:-none}" --view_decisions "${VIEW_DECISIONS:-host}" --score_norm "${SCORE_NORM:-host}" \
     --frame_filter "${FRAME_FILTER:-host}"
 done

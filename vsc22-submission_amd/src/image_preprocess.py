@@ -4,7 +4,9 @@ and the ``remove_edges`` / ``split_imgs`` / ``clean_imgs`` it calls; applied to 
 The reference crops and splits the frames themselves.  Here the decisions are taken on the two per-video maps they depend on --
 the per-pixel variance over all frames and the Canny edge frequency over up to 20 sampled frames -- and come out as boxes
 ``(y0, y1, x0, x1)`` in frame coordinates, in the reference's view order.  The GPU computes the maps (``detect_views``:
-vsc_frame_var_u8 and vsc_canny_count_u8) and cuts and resizes the views (vsc_resize_bicubic_u8); only the decisions run here.
+vsc_frame_var_u8 and vsc_canny_count_u8) and cuts and resizes the views (vsc_resize_bicubic_u8); only the decisions run here --
+or, with ``decisions="hip"``, on the device too (vsc_view_decide_f64: the same arithmetic on the maps where the kernels wrote
+them, so that only the boxes come back).
 
 Every threshold, scan order and quirk is the reference's, on the same numpy slices of the same maps, so the floating-point
 results match too.  Where the reference raises inside its ``try`` (frames of different sizes, a sample index past the last
@@ -23,6 +25,8 @@ CANNY_LOW, CANNY_HIGH = 50, 400
 MIN_SIDE = 20           # clean_imgs: a cut under 20 px on a side leaves the region as it was
 MIN_VIEW = 80           # clean_imgs -> split_imgs(min_size=80)
 GAP = 5                 # split_imgs: width of the static band that separates two stacked views
+# where the decisions run: "host" (decide_views in numpy on the downloaded maps, the default) or "hip" (vsc_view_decide_f64)
+VIEW_DECISIONS = ("host", "hip")
 
 
 def canny_frames(n: int) -> Optional[List[int]]:
@@ -167,27 +171,50 @@ def decide_views(var: np.ndarray, count: np.ndarray, m: int, n: int) -> Tuple[bo
     return False, [whole]
 
 
-def detect_views(frames_dev) -> Tuple[bool, List[Box]]:
+def detect_views(frames_dev, decisions: str = "host") -> Tuple[bool, List[Box]]:
     """The views of one video whose uint8 frames [n, H, W, 3] are on the GPU: one vsc_frame_var_u8 and one vsc_canny_count_u8
-    launch, one device -> host copy of both maps, then ``decide_views``.  Launch and device errors propagate."""
+    launch, one device -> host copy of both maps, then ``decide_views``.  ``decisions="hip"``: the maps stay where the kernels
+    wrote them, one vsc_view_decide_f64 launch follows and one copy of the boxes, their count and the status comes back; a video
+    the kernel leaves to the host (status 1: more views or pending regions than it holds) or cannot take (a side above its limit)
+    goes through the host path.  Launch and device errors propagate."""
+    if decisions not in VIEW_DECISIONS:
+        raise ValueError(f"decisions must be one of {VIEW_DECISIONS}, not {decisions!r}")
     n, h, w = (int(s) for s in frames_dev.shape[:3])
     whole = (0, h, 0, w)
     idx = canny_frames(n)
     if n < MIN_FRAMES or idx is None:
         return False, [whole]
     from vsc_hip import ops
+    if decisions == "hip" and max(h, w) <= ops.VIEW_DECIDE_MAX_SIDE:
+        var, count = ops.view_maps_dev(frames_dev, idx, CANNY_LOW, CANNY_HIGH)
+        k = ops.VIEW_DECIDE_MAX_VIEWS
+        out = _flat_i32(ops.view_decide(var, count, [(0, 0, h, w, len(idx), n)], k)).cpu().numpy()
+        if out[4 * k + 1] == 0:
+            views = [tuple(int(v) for v in out[4 * i:4 * i + 4]) for i in range(int(out[4 * k]))]
+            return (len(views) > 1 or views[0] != whole), views
+        return decide_views(var.cpu().numpy(), count.cpu().numpy(), len(idx), n)
     var, count = ops.view_maps(frames_dev, idx, CANNY_LOW, CANNY_HIGH)
     return decide_views(var, count, len(idx), n)
+
+
+def _flat_i32(parts):
+    """the int32 device tensors of one call as one flat tensor: one device -> host copy instead of three"""
+    import torch
+    return torch.cat([p.reshape(-1) for p in parts])
 
 
 class HipViews:
     """``run_query_videos(views=HipViews(device))`` for ``--preprocess hip``: uploads a video's full-resolution uint8 frames,
     ``detect_views`` on them, then one vsc_resize_bicubic_u8 per encoder input size -> (boxes, {size: uint8 [k * n, size, size, 3]
     on the device}).  The work runs on a side stream, so the host's wait for the two maps does not wait for the encoders queued
-    on the caller's stream; the caller's stream is ordered behind the resized views."""
+    on the caller's stream; the caller's stream is ordered behind the resized views.  ``decisions``: "host" or "hip", as
+    ``detect_views`` takes it."""
 
-    def __init__(self, device):
+    def __init__(self, device, decisions: str = "host"):
         import torch
+        if decisions not in VIEW_DECISIONS:
+            raise ValueError(f"decisions must be one of {VIEW_DECISIONS}, not {decisions!r}")
+        self.decisions = decisions
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
 
@@ -197,7 +224,7 @@ class HipViews:
         main = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(self.stream):
             frames = raw.to(self.device)
-            _, boxes = detect_views(frames)
+            _, boxes = detect_views(frames, self.decisions)
             out = {size: ops.resize_bicubic(frames, boxes, size) for size in sizes}
         main.wait_stream(self.stream)
         for t in out.values():

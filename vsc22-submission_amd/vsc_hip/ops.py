@@ -547,6 +547,66 @@ def view_maps(frames, idx, low: float = 50, high: float = 400):
     return host[:h * w * 8].view(np.float64).reshape(h, w), host[h * w * 8:].view(np.uint16).reshape(h, w)
 
 
+def view_maps_dev(frames, idx, low: float = 50, high: float = 400):
+    """view_maps without the copy: -> (variance float64 [H, W], edge count uint16 [H, W]) as views of ONE device buffer (the
+    float64 map first), for ops.view_decide."""
+    import numpy as np
+    lib = _rd()
+    frames = _frames_u8(frames)
+    n, h, w = frames.shape[:3]
+    idx = np.ascontiguousarray(np.asarray(idx, dtype=np.int32).reshape(-1))
+    buf = torch.empty(h * w * 10, dtype=torch.uint8, device=frames.device)     # float64 map, then the uint16 map
+    var, count = buf[:h * w * 8], buf[h * w * 8:]
+    check(lib.vsc_frame_var_u8(ptr(frames), n, h, w, ptr(var), current_stream()))
+    check(lib.vsc_canny_count_u8(ptr(frames), n, idx.ctypes.data, idx.size, h, w, float(low), float(high), ptr(count),
+                                 current_stream()))
+    return var.view(torch.float64).reshape(h, w), count.view(torch.uint16).reshape(h, w)
+
+
+VIEW_DECIDE_MAX_VIEWS = 64        # VSC_VIEW_DECIDE_MAX_VIEWS of include/vsc_hip.h
+VIEW_DECIDE_MAX_SIDE = 4096       # VSC_VIEW_DECIDE_MAX_SIDE
+_view_decide_handles = {}
+
+
+def view_decide_handle():
+    """The vsc_view_decide handle of the current library on the current stream (made on first use, kept for the process: it is
+    the stream and owns no device memory)."""
+    import ctypes
+    lib = _rd()
+    stream = current_stream()
+    key = (_PRECISION, stream.value or 0)
+    if key not in _view_decide_handles:
+        h = ctypes.c_void_p()
+        check(lib.vsc_view_decide_create(stream, ctypes.byref(h)))
+        _view_decide_handles[key] = h
+    return _view_decide_handles[key]
+
+
+def view_decide(var, count, items, max_views: int = VIEW_DECIDE_MAX_VIEWS, trace: bool = False):
+    """The view decisions of src/image_preprocess.py (decide_views) on maps that stay on the device, one launch per 64 videos and
+    no host synchronisation.  var: float64 device tensor, count: uint16 device tensor (any shapes: read flat); items: int64 [n, 6]
+    rows (element offset of the video's [h, w] variance map in var, of its count map in count, h, w, Canny samples m, frames n) on
+    the host.  -> (boxes int32 [n, max_views, 4] = (y0, y1, x0, x1) in the reference's order with -1 tails, counts int32 [n],
+    status int32 [n]: 1 = the video needs more views or pending regions than the kernel holds and is left to the host) on the
+    device, and with trace also float64 [n, 8] (rows of videos under 5 frames are not written).  Contract, limits and refusals:
+    vsc_view_decide_f64 in include/vsc_hip.h."""
+    import numpy as np
+    lib = _rd()
+    var = _dev(var, torch.float64).reshape(-1)
+    assert count.is_cuda and count.dtype == torch.uint16, "count must be a uint16 device tensor"
+    count = count.contiguous().reshape(-1)
+    items = np.ascontiguousarray(np.asarray(items, dtype=np.int64).reshape(-1, 6))
+    n, k = items.shape[0], max(int(max_views), 0)
+    boxes = torch.empty((n, k, 4), dtype=torch.int32, device=var.device)
+    counts = torch.empty(n, dtype=torch.int32, device=var.device)
+    status = torch.empty(n, dtype=torch.int32, device=var.device)
+    tr = torch.empty((n, 8), dtype=torch.float64, device=var.device) if trace else None
+    opt = lambda t: ptr(t) if t is not None and t.numel() else None     # noqa: E731
+    check(lib.vsc_view_decide_f64(view_decide_handle(), opt(var), var.numel(), opt(count), count.numel(), items.ctypes.data, n,
+                                  int(max_views), opt(boxes), opt(counts), opt(status), opt(tr)))
+    return (boxes, counts, status, tr) if trace else (boxes, counts, status)
+
+
 def resize_bicubic(frames, boxes, size: int, out=None):
     """Crop every box (y0, y1, x0, x1) out of every uint8 device frame [n, H, W, 3] and resize it to size x size, PIL-exact
     (Image.fromarray(crop).resize((size, size), Image.BICUBIC)) -> uint8 [len(boxes) * n, size, size, 3], view-major
