@@ -711,6 +711,38 @@ int vsc_view_decide_f64(vsc_view_decide *h, const double *var_dev, int64_t var_l
                         const int64_t *items_host, int64_t n_items, int32_t max_views, int32_t *boxes_dev, int32_t *counts_dev,
                         int32_t *status_dev, double *trace_dev);
 
+/* Every model input of a video from its uploaded frames, in one call: what src/dataset.py's vit_transform_u8 and
+ * clip_transform_u8 do per frame with Pillow in the loader workers.  Executable contract: tests/frame_inputs_contract.py.
+ * frames_dev: uint8 [n][h][w][3].  targets_host int32 [n_targets][10] (HOST memory), a row =
+ * {y0, y1, x0, x1, out_h, out_w, top, left, crop_h, crop_w}; outs_host [n_targets] (HOST memory): device pointers, target t
+ * writes uint8 [n][crop_h][crop_w][3], packed, to outs_host[t]:
+ *   out[i] == np.asarray(Image.fromarray(frame_i[y0:y1, x0:x1]).resize((out_w, out_h), Image.BICUBIC))[top:top + crop_h,
+ *   left:left + crop_w], bit for bit.  The resample is the one stated at vsc_resize_bicubic_u8 (same coefficient tables, same
+ *   cache): taps clamp to the BOX's edges; horizontal pass first, its result rounded and clipped to uint8 as Pillow's intermediate
+ *   image is, then the vertical pass -- except a box more than 100 times taller than wide with out_h below its height: vertical
+ *   first; an axis whose length does not change passes through its identity coefficients.  Only the window is computed.
+ * One fused launch per target, one workgroup per (frame, band of output rows, tile of 64 output columns): the band's horizontally
+ * resampled rows stay in LDS, beside the tile's rows of the horizontal coefficient table, the band's rows of the vertical one and
+ * the staged source rows.  A target for which not even one output row of a tile fits VSC_FRAME_INPUTS_LDS_BYTES that way (its
+ * vertical support x 192 bytes + 64 x (2 + horizontal taps) x 4 bytes + one staged source row: downscales by some hundreds) and
+ * the vertical-first shape run as two launches per chunk of frames over the search path's grow-only scratch (at most 256 MiB, or
+ * one frame's first pass if that is larger; callers on one device are ordered).  The same bytes either way.  No limit on n.
+ * Refused (VSC_ERR_INVALID) before anything is launched, with nothing written -- a bad target after a good one launches nothing:
+ * a null handle, a box outside the frame or empty, out_h or out_w outside 1..VSC_FRAME_INPUTS_MAX_SIDE, a window outside
+ * out_h x out_w or of negative size, a null output for a non-empty target, n below 0, a null pointer that is needed.  n == 0 or
+ * n_targets == 0 launches nothing; a target with crop_h == 0 or crop_w == 0 writes nothing.  No alignment is required of
+ * frames_dev or the outputs (dword-aligned outputs whose crop_w * 3 is a multiple of 4 take the fastest store path).
+ * The entry takes a handle that holds the caller's stream and only enqueues on it, with one exception it shares with
+ * vsc_resize_bicubic_u8: the first time a (device, length, size) triple is seen its coefficient table is built on the host and
+ * uploaded with a synchronous copy; the table is then kept for the life of the process. */
+#define VSC_FRAME_INPUTS_MAX_SIDE 4096
+#define VSC_FRAME_INPUTS_LDS_BYTES (160 * 1024)
+typedef struct vsc_frame_inputs vsc_frame_inputs;
+int vsc_frame_inputs_create(void *stream, vsc_frame_inputs **out);   /* every call of the handle enqueues on this stream */
+void vsc_frame_inputs_destroy(vsc_frame_inputs *h);
+int vsc_frame_inputs_u8(vsc_frame_inputs *h, const uint8_t *frames_dev, int64_t n, int32_t fh, int32_t fw, const int32_t *targets_host,
+                        int32_t n_targets, uint8_t *const *outs_host);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

@@ -327,7 +327,7 @@ enum SearchScratchSlot {
     SCRATCH_PF_QSTATS = 14, SCRATCH_PF_FLAGS = 15,  // per-query norms; max |r| bits + fallback flags + debug counters
     SCRATCH_PF_LISTS = 16, SCRATCH_PF_CAND = 17, SCRATCH_PF_NCAND = 18,   // sweep lists per workgroup; survivors per (query, split), their number
     SCRATCH_TN_TABLE = 19, SCRATCH_TN_NODES = 20,         // tn_align.hip
-    SCRATCH_VIEW_CANNY = 21, SCRATCH_VIEW_RESIZE = 22,    // view_prep.hip
+    SCRATCH_VIEW_CANNY = 21, SCRATCH_VIEW_RESIZE = 22,    // view_prep.hip; the resize slot also serves frame_inputs.hip's two-pass path
     SCRATCH_MS_TABLE = 23,                                // match_segments.hip
     // global_topk.hip
     SCRATCH_GTK_STATE = 24, SCRATCH_GTK_BLOCKS = 25,      // global top-k: select state; (above, equal) counts per tile
@@ -358,6 +358,9 @@ int launch_canny_count_u8(const uint8_t *frames, int64_t n, const int32_t *idx_h
                           uint16_t *out, hipStream_t stream);
 int launch_resize_bicubic_u8(const uint8_t *frames, int64_t n, int h, int w, const int32_t *boxes_host, int k, int size, uint8_t *out,
                              hipStream_t stream);
+// every model input of a video from its uploaded frames (frame_inputs.hip), contract at vsc_frame_inputs_u8 in include/vsc_hip.h
+int launch_frame_inputs_u8(const uint8_t *frames, int64_t n, int h, int w, const int32_t *targets_host, int n_targets, uint8_t *const *outs_host,
+                           hipStream_t stream);
 // score normalisation (score_norm.hip), contracts at vsc_column_var_f32 / vsc_score_norm_rows_f32 / vsc_score_norm_bias_f32 in include/vsc_hip.h
 int launch_column_var(const float *x, int64_t n, int d, int64_t ld, float *var, hipStream_t stream);
 int launch_score_norm_rows(const float *x, int64_t n, int d, int64_t ldx, int drop, int normalize, int append, const float *last,

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "common.h"
+#include "resample_coeffs.h"
 
 namespace {
 
@@ -200,92 +201,15 @@ __global__ __launch_bounds__(BLOCK) void canny_count_kernel(const int32_t *__res
 }
 
 // ---- (c) crop + bicubic resize, Pillow's 8-bit resample ----------------------------------------------------------------
-constexpr int PRECISION_BITS = 32 - 8 - 2;
+constexpr int PRECISION_BITS = RESAMPLE_PRECISION_BITS;
 
-// Pillow's bicubic filter (a = -0.5) and precompute_coeffs + normalize_coeffs_8bpc for a box (0, in) -> out, on the host.
-double bicubic_filter(double x) {
-    const double a = -0.5;
-    if (x < 0.0) x = -x;
-    if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1;
-    if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
-    return 0.0;
-}
+using Coeffs = ResampleCoeffs;
 
-// -> table [out][2 + ksize] int32: first tap, tap count, then the fixed-point weights
-std::vector<int32_t> resample_coeffs(int in, int out, int *ksize_out) {
-    const double scale = (double)in / out;
-    const double filterscale = scale < 1.0 ? 1.0 : scale;
-    const double support = 2.0 * filterscale;
-    const int ksize = (int)ceil(support) * 2 + 1;
-    std::vector<int32_t> table((size_t)out * (2 + ksize), 0);
-    std::vector<double> k(ksize);
-    for (int xx = 0; xx < out; ++xx) {
-        const double center = 0.0 + (xx + 0.5) * scale;
-        const double ss = 1.0 / filterscale;
-        int xmin = (int)(center - support + 0.5);
-        if (xmin < 0) xmin = 0;
-        int xmax = (int)(center + support + 0.5);
-        if (xmax > in) xmax = in;
-        xmax -= xmin;
-        double ww = 0.0;
-        int x = 0;
-        for (; x < xmax; ++x) {
-            const double wgt = bicubic_filter((x + xmin - center + 0.5) * ss);
-            k[x] = wgt;
-            ww += wgt;
-        }
-        for (x = 0; x < xmax; ++x)
-            if (ww != 0.0) k[x] /= ww;
-        int32_t *row = table.data() + (size_t)xx * (2 + ksize);
-        row[0] = xmin;
-        row[1] = xmax;
-        for (x = 0; x < xmax; ++x)
-            row[2 + x] = k[x] < 0 ? (int32_t)(-0.5 + k[x] * (1 << PRECISION_BITS)) : (int32_t)(0.5 + k[x] * (1 << PRECISION_BITS));
-    }
-    *ksize_out = ksize;
-    return table;
-}
-
-struct Coeffs {
-    int32_t *dev = nullptr;
-    int ksize = 0;
-};
-
-// Device copies of the tables, per (device, in length, out length): built and uploaded once (a synchronous copy), then kept for
-// the life of the process.  A table is never freed, so a pointer handed out stays valid for every kernel queued with it, on any
-// thread or device.  The set is bounded by the distinct crop lengths: ~21 KiB per length at 1080p, and at most ~150 MiB per output
-// size even if every length up to 4096 occurs.
+// the process-wide table cache of resample_coeffs.h
 std::map<std::tuple<int, int, int>, Coeffs> g_coeffs;
 std::mutex g_coeffs_mutex;
 
-int coeffs_get(int in, int out, Coeffs *res) {
-    int dev = 0;
-    VSC_CHECK_HIP(hipGetDevice(&dev));
-    std::lock_guard<std::mutex> lock(g_coeffs_mutex);
-    auto key = std::make_tuple(dev, in, out);
-    auto it = g_coeffs.find(key);
-    if (it != g_coeffs.end()) {
-        *res = it->second;
-        return VSC_OK;
-    }
-    Coeffs c;
-    std::vector<int32_t> table = resample_coeffs(in, out, &c.ksize);
-    const size_t bytes = table.size() * sizeof(int32_t);
-    hipError_t e = hipMalloc((void **)&c.dev, bytes);
-    if (e != hipSuccess) {
-        vsc_set_error("resize_bicubic: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-        return VSC_ERR_NOMEM;
-    }
-    e = hipMemcpy(c.dev, table.data(), bytes, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        (void)hipFree(c.dev);
-        vsc_set_error("resize_bicubic: coefficient upload failed: %s", hipGetErrorString(e));
-        return VSC_ERR_HIP;
-    }
-    g_coeffs[key] = c;
-    *res = c;
-    return VSC_OK;
-}
+inline int coeffs_get(int in, int out, Coeffs *res) { return resample_coeffs_get("resize_bicubic", in, out, res); }
 
 __device__ inline uint8_t clip8(int v) {
     v >>= PRECISION_BITS;
@@ -351,6 +275,38 @@ __global__ __launch_bounds__(BLOCK) void resize_v_kernel(const uint8_t *__restri
 inline bool vertical_first(int hc, int wc, int s) { return hc > (int64_t)wc * 100 && s < hc; }
 
 }  // namespace
+
+int resample_coeffs_get(const char *who, int in, int out, ResampleCoeffs *res) {
+    int dev = 0;
+    VSC_CHECK_HIP(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lock(g_coeffs_mutex);
+    auto key = std::make_tuple(dev, in, out);
+    auto it = g_coeffs.find(key);
+    if (it != g_coeffs.end()) {
+        *res = it->second;
+        return VSC_OK;
+    }
+    Coeffs c;
+    auto *table = new std::vector<int32_t>(resample_coeffs(in, out, &c.ksize));     // kept: ResampleCoeffs::host
+    const size_t bytes = table->size() * sizeof(int32_t);
+    hipError_t e = hipMalloc((void **)&c.dev, bytes);
+    if (e != hipSuccess) {
+        delete table;
+        vsc_set_error("%s: hipMalloc(%zu) failed: %s", who, bytes, hipGetErrorString(e));
+        return VSC_ERR_NOMEM;
+    }
+    e = hipMemcpy(c.dev, table->data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)hipFree(c.dev);
+        delete table;
+        vsc_set_error("%s: coefficient upload failed: %s", who, hipGetErrorString(e));
+        return VSC_ERR_HIP;
+    }
+    c.host = table->data();
+    g_coeffs[key] = c;
+    *res = c;
+    return VSC_OK;
+}
 
 int launch_frame_var_u8(const uint8_t *frames_dev, int64_t n, int h, int w, double *out_dev, hipStream_t stream) {
     VSC_REQUIRE(n >= 1 && n < (int64_t(1) << 24), "frame_var: %lld frames (1 .. 2^24 - 1)", (long long)n);

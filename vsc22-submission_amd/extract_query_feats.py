@@ -15,7 +15,11 @@ Outputs, as the reference: ``<output_dir>/<model name>/<split>_query.npz`` per b
 ``--preprocess hip`` adds the reference's query preprocessing (infer/src/image_preprocess.py ``image_process``, applied by
 infer/src/dataset.py:82-88): static borders are cropped and stacked compositions split into views on the GPU
 (src/image_preprocess.py), and every view's frames are encoded -- k views of n frames give k * n descriptor rows, timestamps
-repeated view-major.  The video-score gate keeps the original frames.  The default, ``none``, encodes whole frames."""
+repeated view-major.  The video-score gate keeps the original frames.  The default, ``none``, encodes whole frames.
+
+``--resize hip``: the loader workers only decode; every encoder input and the video-score input are made from the uploaded frames
+on the GPU (vsc_frame_inputs_u8, PIL-exact: the same files), with ``--preprocess hip`` from the same upload as the views.  The
+default, ``host``, resizes with Pillow in the workers."""
 from __future__ import annotations
 
 import argparse
@@ -27,7 +31,7 @@ from zipfile import ZipFile
 import numpy as np
 import torch
 
-from src.dataset import CLIP_MEAN, CLIP_STD, clip_transform_u8, vit_transform_u8
+from src.dataset import CLIP_MEAN, CLIP_STD, RESIZES, check_resize, clip_transform_u8, decode_rgb, vit_transform_u8
 from src.matching import calclualte_low_var_dim
 from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
 from src.image_preprocess import HipViews, VIEW_DECISIONS
@@ -48,11 +52,13 @@ class QueryVideos(torch.utils.data.Dataset):
     worker processes, as the reference does (extract_query_feats.py:138-140).
     ``preprocess="hip"``: the frames stay at the zip's own resolution, uint8 [S,H,W,3] under ``RAW_KEY`` (run_query_videos cuts
     and resizes the views on the GPU), next to the unchanged CLIP frames.  A video whose frames differ in size is resized here as
-    with ``none``: the reference's preprocessing fails on it (np.stack) and leaves it unprocessed."""
+    with ``none``: the reference's preprocessing fails on it (np.stack) and leaves it unprocessed.
+    ``resize="hip"``: the same raw frames and nothing else -- run_query_videos(resize="hip") makes every input, the CLIP frames
+    included, on the GPU; a video whose frames differ in size is again resized here."""
 
-    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False, preprocess="none"):
+    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False, preprocess="none", resize="host"):
         assert preprocess in ("none", "hip"), preprocess
-        self.zip_prefix, self.preprocess = zip_prefix, preprocess
+        self.zip_prefix, self.preprocess, self.resize = zip_prefix, preprocess, check_resize(resize)
         self.video_ids = [v for v in video_ids if os.path.exists(self._path(v))]
         self.transforms = {s: vit_transform_u8(s, s) for s in sizes}
         if with_clip:
@@ -74,16 +80,16 @@ class QueryVideos(torch.utils.data.Dataset):
         # store_features to concatenate them
         n = len(images)
         stamps = np.stack([np.arange(n, dtype=np.float32), np.arange(n, dtype=np.float32) + 1.0], axis=1)
-        if self.preprocess == "hip" and len({im.size for im in images}) == 1:
-            frames = {RAW_KEY: torch.from_numpy(np.stack([np.asarray(im, dtype=np.uint8) for im in images]))}
-            if VideoScorer.KEY in self.transforms:
+        if (self.preprocess == "hip" or self.resize == "hip") and len({im.size for im in images}) == 1:
+            frames = {RAW_KEY: torch.from_numpy(np.stack([decode_rgb(im) for im in images]))}
+            if VideoScorer.KEY in self.transforms and self.resize != "hip":
                 frames[VideoScorer.KEY] = torch.stack([self.transforms[VideoScorer.KEY](im) for im in images])
             return vid, frames, stamps
         return vid, {s: torch.stack([t(im) for im in images]) for s, t in self.transforms.items()}, stamps
 
 
-def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0, preprocess="none"):
-    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip, preprocess)
+def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0, preprocess="none", resize="host"):
+    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip, preprocess, resize)
     kw = {"prefetch_factor": 4} if workers > 0 else {}
     return torch.utils.data.DataLoader(data, batch_size=1, shuffle=False, num_workers=workers, collate_fn=lambda b: b[0], **kw)
 
@@ -96,7 +102,13 @@ def read_video_scores(path):
     return {r[0]: float(r[1]) for r in rows}
 
 
+def resize_of(args) -> str:
+    """``args.resize``, "host" for a namespace built by hand from before the option; ValueError for an unknown value"""
+    return check_resize(getattr(args, "resize", "host"))
+
+
 def main(args):
+    resize = resize_of(args)
     torch.cuda.set_device(0)
     device = torch.device("cuda", 0)
     specs = [parse_model_spec(s) for s in args.models]
@@ -113,10 +125,11 @@ def main(args):
         from src.model_zoo import _state_dict      # a plain / training checkpoint or the TorchScript archive the reference ships (vsm.torchscript.pt)
         scorer = VideoScorer(clip, VideoScoreHead("vsm_roberta_base", from_reference_state(_state_dict(args.vsm_checkpoint))), device)
     videos = zip_videos(vids, args.zip_prefix, sorted({size for _, size in encoders}), with_clip=scorer is not None,
-                        workers=args.workers, preprocess=args.preprocess)
+                        workers=args.workers, preprocess=args.preprocess, resize=resize)
     finals, per_model = run_query_videos(videos, encoders, pca.transform, scores, device, score_threshold=args.score_threshold,
                                          scorer=scorer, views=HipViews(device, getattr(args, "view_decisions", "host")) if args.preprocess == "hip" else None,
-                                         frame_filter=getattr(args, "frame_filter", "host"))   # (a hand-built namespace from before the option)
+                                         frame_filter=getattr(args, "frame_filter", "host"),   # (a hand-built namespace from before the option)
+                                         resize=resize)
     for i, (_, _, path) in enumerate(specs):
         key = os.path.split(path)[-1].split(".")[0]
         os.makedirs(os.path.join(args.output_dir, key), exist_ok=True)
@@ -161,6 +174,9 @@ def build_parser():
                     help="the near-duplicate frame filter in numpy on the host, or on the device (hip: the similarity matrices are not "
                          "downloaded); the same files wherever a video's frame means are pairwise distinct -- equal means are visited in "
                          "descending index on the device and in numpy's unspecified order on the host")
+    ap.add_argument("--resize", default="host", choices=RESIZES,
+                    help="where decoded frames become model inputs: Pillow in the loader workers, or on the device (hip: the workers "
+                         "only decode, one kernel call per video makes every encoder input and the video-score input; the same files)")
     return ap
 
 

@@ -5,7 +5,11 @@
         --input_file ../data/meta/train/train_ref_vids.txt --save_file outputs/train_refs
 
 Same outputs: <save_file>.npz in the reference layout, videos sorted by id.  Videos shard over
-ranks; each rank writes <save_file>_<rank>.npz, rank 0 merges (as the reference does)."""
+ranks; each rank writes <save_file>_<rank>.npz, rank 0 merges (as the reference does).
+
+``--resize hip``: the loader workers only decode; every video's frames are uploaded at the zip's resolution and resized to the
+encoder's input on the GPU (vsc_frame_inputs_u8, PIL-exact: the same file).  The default, ``host``, resizes with Pillow in the
+workers."""
 from __future__ import annotations
 
 import argparse
@@ -14,15 +18,21 @@ import os
 import numpy as np
 import torch
 
-from src.dataset import ZipFrames, collate_fn, vit_transform_u8
-from src.extractor import extract_vsc_feat
+from src.dataset import RESIZES, ZipFrames, check_resize, collate_fn, raw_collate, vit_transform_u8
+from src.extractor import extract_vsc_feat, extract_vsc_feat_raw
 from vsc.storage import load_features, store_features
 from src.model_zoo import DEFAULT_PRECISION, WEIGHT_FORMATS, load_encoder
 from vsc_hip import distributed as vdist
 
 
+def resize_of(args) -> str:
+    """``args.resize``, "host" for a namespace built by hand from before the option; ValueError for an unknown value"""
+    return check_resize(getattr(args, "resize", "host"))
+
+
 def main(args):
     import torch.distributed as dist
+    resize = resize_of(args)
     distributed = "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local_rank)
@@ -35,9 +45,13 @@ def main(args):
     with open(args.input_file, encoding="utf-8") as f:
         vids = [x.strip() for x in f if x.strip()]
     lo, hi = vdist.shard_bounds(len(vids), rank, world_size)
-    data = ZipFrames(vids[lo:hi], args.zip_prefix, vit_transform_u8(image_size, image_size))   # uint8 to the GPU; normalised in patchify
-    loader = torch.utils.data.DataLoader(data, batch_size=args.batch_size, num_workers=4, collate_fn=collate_fn)
-    ids, feats, stamps = extract_vsc_feat(model, loader, device)
+    data = ZipFrames(vids[lo:hi], args.zip_prefix, vit_transform_u8(image_size, image_size), raw=resize == "hip")   # uint8 to the GPU; normalised in patchify
+    loader = torch.utils.data.DataLoader(data, batch_size=args.batch_size, num_workers=4, collate_fn=raw_collate if resize == "hip" else collate_fn)
+    if resize == "hip":
+        from src.image_preprocess import HipResize
+        ids, feats, stamps = extract_vsc_feat_raw(model, loader, device, image_size, HipResize(device))
+    else:
+        ids, feats, stamps = extract_vsc_feat(model, loader, device)
     np.savez(f"{args.save_file}_{rank}.npz", video_ids=ids, features=feats, timestamps=stamps)
     if distributed:
         dist.barrier()
@@ -54,7 +68,7 @@ def main(args):
         store_features(args.save_file + ".npz", sorted(load_features(args.save_file + ".npz"), key=lambda v: v.video_id))
 
 
-if __name__ == "__main__":
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--save_file", default="test_refs")
     ap.add_argument("--zip_prefix", default="")
@@ -67,4 +81,11 @@ if __name__ == "__main__":
                     help="frames per encoder step; default: the backbone's tile-aligned batch (ViT-B/16: 332)")
     ap.add_argument("--precision", default=DEFAULT_PRECISION, choices=["fp16", "bf16"],
                     help="16-bit type of the encoder's MFMA operands (same speed; fp16 = 8 x smaller rounding, DESIGN.md 3a)")
-    main(ap.parse_args())
+    ap.add_argument("--resize", default="host", choices=RESIZES,
+                    help="where decoded frames are resized to the encoder's input: Pillow in the loader workers, or on the device "
+                         "(hip: the workers only decode; the same file)")
+    return ap
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

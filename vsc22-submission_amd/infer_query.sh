@@ -4,6 +4,8 @@
 # image_process); the default, none, encodes whole frames.  SCORE_NORM=hip runs the query score normalisation on the GPU (the same file).
 # VIEW_DECISIONS=hip (with PREPROCESS=hip) takes the border / split decisions on the GPU too: only the boxes come back (the same files).
 # FRAME_FILTER=hip runs the near-duplicate frame filter on the GPU (the same files wherever a video's frame means are pairwise distinct).
+# RESIZE=hip makes every encoder input and the video-score input from the decoded frames on the GPU instead of with Pillow in the
+# loader workers, with or without PREPROCESS=hip (the same files).
 #   CKPT=../checkpoints ZIPS=../data/jpg_zips META=../data/meta bash infer_query.sh
 set -e
 cd "$(dirname "$0")"
@@ -20,5 +22,5 @@ for split in ${SPLITS:-train val test}; do
     --pca_model "$PCA_MODEL" --zip_prefix "$ZIPS" --input_file "$META/$split/${split}_query_ids.txt" --norm_refs "$NORM" \
     --clip_checkpoint "$CKPT/clip.torchscript.pt" --vsm_checkpoint "$CKPT/vsm.torchscript.pt" --output_dir "$OUT" \
     --preprocess "${PREPROCESS:-none}" --view_decisions "${VIEW_DECISIONS:-host}" --score_norm "${SCORE_NORM:-host}" \
-    --frame_filter "${FRAME_FILTER:-host}"
+    --frame_filter "${FRAME_FILTER:-host}" --resize "${RESIZE:-host}"
 done

@@ -73,11 +73,41 @@ def clip_transform_u8(size: int = 224):
     return apply
 
 
+RESIZES = ("host", "hip")   # where decoded frames become model inputs: Pillow in the loader workers, or vsc_frame_inputs_u8
+
+
+def check_resize(resize: str) -> str:
+    if resize not in RESIZES:
+        raise ValueError(f"resize must be one of {RESIZES}, not {resize!r}")
+    return resize
+
+
+def square_target(h: int, w: int, size: int):
+    """The ops.frame_inputs target row (y0, y1, x0, x1, out_h, out_w, top, left, crop_h, crop_w) of ``vit_transform_u8(size, size)``
+    on an h x w frame: the whole frame to size x size."""
+    return (0, h, 0, w, size, size, 0, 0, size, size)
+
+
+def clip_target(h: int, w: int, size: int = 224):
+    """The target row of ``clip_transform_u8(size)`` on an h x w frame: short side to ``size`` (the long side truncated), then the
+    centre window, whose offsets round half to even as Python's round does."""
+    nw, nh = (size, int(size * h / w)) if w <= h else (int(size * w / h), size)
+    left, top = int(round((nw - size) / 2.0)), int(round((nh - size) / 2.0))
+    return (0, h, 0, w, nh, nw, top, left, size, size)
+
+
+def decode_rgb(img) -> np.ndarray:
+    """A decoded Pillow image as uint8 [H, W, 3], the array the transforms' ``img.convert("RGB")`` resizes."""
+    return np.asarray(img.convert("RGB"), dtype=np.uint8)
+
+
 class ZipFrames(torch.utils.data.Dataset):
     """One item = all frames of one video, read from <prefix>/<vid[-2:]>/<vid>.zip of jpgs."""
 
-    def __init__(self, video_ids: Sequence[str], zip_prefix: str, transform):
-        self.zip_prefix, self.transform = zip_prefix, transform
+    def __init__(self, video_ids: Sequence[str], zip_prefix: str, transform, raw: bool = False):
+        """``raw`` (``--resize hip``): the workers only decode -- an item is (uint8 [S, H, W, 3] at the zip's own resolution, video_id)
+        for ``raw_collate``; a video whose frames differ in size is resized by ``transform`` here, as without ``raw``."""
+        self.zip_prefix, self.transform, self.raw = zip_prefix, transform, raw
         self.video_ids = [v for v in video_ids if os.path.exists(self._path(v))]
 
     def _path(self, vid):
@@ -90,6 +120,11 @@ class ZipFrames(torch.utils.data.Dataset):
         from PIL import Image
         vid = self.video_ids[i]
         with ZipFile(self._path(vid), "r") as z:
+            if self.raw:
+                images = [Image.open(io.BytesIO(z.read(n))).convert("RGB") for n in sorted(z.namelist())]
+                if len({im.size for im in images}) == 1:
+                    return torch.from_numpy(np.stack([decode_rgb(im) for im in images])), vid
+                return torch.stack([self.transform(im) for im in images]), vid
             frames = [self.transform(Image.open(io.BytesIO(z.read(n)))) for n in sorted(z.namelist())]
         return torch.stack(frames), vid
 
@@ -105,6 +140,11 @@ class TensorFrames(torch.utils.data.Dataset):
 
     def __getitem__(self, i):
         return self.videos[i]
+
+
+def raw_collate(batch):
+    """``ZipFrames(raw=True)``: the videos of a loader batch as they are, [(frames, video_id)] -- their frames differ in shape"""
+    return list(batch)
 
 
 def collate_fn(batch):

@@ -21,6 +21,35 @@ import torch
 
 
 def extract_vsc_feat(model, batches: Iterable, device, group_frames: int = 4096) -> Tuple[List[str], np.ndarray, np.ndarray]:
+    def videos():
+        for frames, mask, video_id in batches:
+            mask = mask.bool()
+            counts = mask.sum(dim=1).tolist()
+            yield [(v, frames[b][:int(c)] if bool(mask[b, :int(c)].all()) else frames[b][mask[b]])   # (the collate pads at the end: a view, no copy)
+                   for b, (v, c) in enumerate(zip(video_id, counts))]
+    return _extract(model, videos(), device, group_frames)
+
+
+def extract_vsc_feat_raw(model, batches: Iterable, device, image_size: int, resizer, group_frames: int = 4096):
+    """``extract_vsc_feat`` for ``--resize hip``: a loader batch is a list of (frames, video_id) as the workers decoded them, uint8
+    [S, H, W, 3] at the zip's own resolution (``src.dataset.raw_collate``).  Every video is uploaded and resized to the encoder's
+    input by one vsc_frame_inputs_u8 call (``resizer``: src.image_preprocess.HipResize) and the groups are encoded from device
+    tensors.  Groups close at the same loader batches and hold the same frames in the same order as with host resizing, so the
+    same frames share the same encoder calls.  A video the worker already resized (its frames differ in size) arrives as uint8
+    [S, image_size, image_size, 3] and goes through from the host."""
+    def videos():
+        for batch in batches:
+            out = []
+            for frames, v in batch:
+                if frames.shape[0] and tuple(frames.shape[1:3]) != (image_size, image_size):
+                    frames = resizer(frames, [image_size])[1][image_size]
+                out.append((v, frames))
+            yield out
+    return _extract(model, videos(), device, group_frames)
+
+
+def _extract(model, batches: Iterable, device, group_frames: int) -> Tuple[List[str], np.ndarray, np.ndarray]:
+    """batches yields one list of (video_id, valid frames) per loader batch"""
     from src.query_pipeline import encode_group
     feats, vids, stamps = [], [], []
     group, have = [], 0
@@ -47,16 +76,13 @@ def extract_vsc_feat(model, batches: Iterable, device, group_frames: int = 4096)
                 feats.extend(outs)
         group, have = [], 0
 
-    for frames, mask, video_id in batches:
-        mask = mask.bool()
-        counts = mask.sum(dim=1).tolist()
-        for b, (v, c) in enumerate(zip(video_id, counts)):
-            c = int(c)
+    for batch in batches:
+        for v, f in batch:
+            c = int(f.shape[0])
             vids.extend([v] * c)
             stamps.append(np.arange(c))
             if c:
-                f = frames[b]
-                group.append(f[:c] if bool(mask[b, :c].all()) else f[mask[b]])   # (the collate pads at the end: a view, no copy)
+                group.append(f)
                 have += c
         if have >= group_frames:
             flush()

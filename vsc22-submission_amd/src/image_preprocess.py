@@ -218,14 +218,79 @@ class HipViews:
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
 
+    def on_device(self, frames, sizes):
+        """the views of frames that are on the device already, on the current stream"""
+        from vsc_hip import ops
+        _, boxes = detect_views(frames, self.decisions)
+        return boxes, {size: ops.resize_bicubic(frames, boxes, size) for size in sizes}
+
     def __call__(self, raw, sizes):
         import torch
-        from vsc_hip import ops
         main = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(self.stream):
-            frames = raw.to(self.device)
-            _, boxes = detect_views(frames, self.decisions)
-            out = {size: ops.resize_bicubic(frames, boxes, size) for size in sizes}
+            boxes, out = self.on_device(raw.to(self.device), sizes)
+        main.wait_stream(self.stream)
+        for t in out.values():
+            t.record_stream(main)
+        return boxes, out
+
+
+class HipResize:
+    """``--resize hip``: every model input of a video from its decoded frames, on the device.  ``resizer(raw, sizes)`` uploads the
+    uint8 frames [n, H, W, 3] once -- through a pinned buffer with a non-blocking copy -- and one vsc_frame_inputs_u8 call makes the
+    encoder input of every size (vit_transform_u8's resize) and, with ``clip_key``, the video-score input (clip_transform_u8(224))
+    -> (None, {size or clip_key: uint8 [n, s, s, 3] on the device}).  With ``views`` (a HipViews: ``--preprocess hip``) the views
+    are made as HipViews makes them, from the same uploaded frames, and the call returns their boxes; only the video-score input
+    then comes from vsc_frame_inputs_u8.  The work runs on a side stream, as in HipViews; the caller's stream is ordered behind
+    the results."""
+
+    def __init__(self, device, clip_size: int = 224):
+        import torch
+        self.device = torch.device(device)
+        self.clip_size = clip_size
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.pinned = None
+        self.copied = torch.cuda.Event()      # the last copy out of the pinned buffer is done
+        self.used = False
+
+    def upload(self, raw):
+        """host frames -> device, on the current stream; the pinned buffer grows to the largest video seen"""
+        import torch
+        if raw.is_cuda:
+            return raw
+        raw = raw.contiguous()
+        if self.used:
+            self.copied.synchronize()
+        if self.pinned is None or self.pinned.numel() < raw.numel():
+            self.pinned = torch.empty(raw.numel(), dtype=torch.uint8).pin_memory()
+        staged = self.pinned[:raw.numel()].view(raw.shape)
+        staged.copy_(raw)
+        frames = torch.empty(raw.shape, dtype=torch.uint8, device=self.device)
+        frames.copy_(staged, non_blocking=True)
+        self.copied.record(torch.cuda.current_stream(self.device))
+        self.used = True
+        return frames
+
+    def __call__(self, raw, sizes, views=None, clip_key=None):
+        import torch
+        from src.dataset import clip_target, square_target
+        from vsc_hip import ops
+        main = torch.cuda.current_stream(self.device)
+        if raw.is_cuda:
+            self.stream.wait_stream(main)     # frames made on the caller's stream
+        with torch.cuda.stream(self.stream):
+            frames = self.upload(raw)
+            h, w = int(frames.shape[1]), int(frames.shape[2])
+            boxes, out, keys, targets = None, {}, [], []
+            if views is not None:
+                boxes, out = views.on_device(frames, sizes)
+            else:
+                keys, targets = list(sizes), [square_target(h, w, size) for size in sizes]
+            if clip_key is not None:
+                keys.append(clip_key)
+                targets.append(clip_target(h, w, self.clip_size))
+            if targets:
+                out.update(zip(keys, ops.frame_inputs(frames, targets)))
         main.wait_stream(self.stream)
         for t in out.values():
             t.record_stream(main)

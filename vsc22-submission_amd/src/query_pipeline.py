@@ -11,6 +11,7 @@ from typing import Callable, Dict, Iterable, List, Sequence, Tuple
 import numpy as np
 import torch
 
+from src.dataset import check_resize
 from src.query_postprocess import FRAME_FILTERS, HipOps, SCORE_THRESHOLD, process_query_group, process_query_video
 from vsc.index import VideoFeature
 
@@ -228,6 +229,26 @@ def _with_views(videos, sizes: Sequence[int], views):
         yield vid, out, np.tile(stamps, (len(boxes),) + (1,) * (stamps.ndim - 1))
 
 
+def _with_device_inputs(videos, sizes: Sequence[int], views, resizer, with_clip: bool):
+    """``resize="hip"``: a video that carries its decoded frames under ``RAW_KEY`` gets every model input from ``resizer``
+    (src.image_preprocess.HipResize) on the device: the encoder inputs -- its views' with ``views`` (``--preprocess hip``, timestamps
+    tiled as in ``_with_views``), else the whole frames' -- and, for a scorer, the video-score input unless the worker made it.
+    Other videos (frames of different sizes, resized by the worker) pass through as they are."""
+    for vid, frames_by_size, stamps in videos:
+        raw = frames_by_size.get(RAW_KEY)
+        if raw is None:
+            yield vid, frames_by_size, stamps
+            continue
+        clip_key = VideoScorer.KEY if with_clip and VideoScorer.KEY not in frames_by_size else None
+        boxes, made = resizer(raw, sizes, views=views, clip_key=clip_key)
+        out = {key: f for key, f in frames_by_size.items() if key != RAW_KEY}
+        out.update(made)
+        if boxes is not None:
+            stamps = np.asarray(stamps)
+            stamps = np.tile(stamps, (len(boxes),) + (1,) * (stamps.ndim - 1))
+        yield vid, out, stamps
+
+
 def _video_groups(videos, min_frames: int):
     """Consecutive videos grouped until a group holds at least ``min_frames`` frames."""
     group, n = [], 0
@@ -245,7 +266,7 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
                      pca_transform: Callable[[np.ndarray], np.ndarray], video_scores: Dict[str, float], device,
                      ops=HipOps, score_threshold: float = SCORE_THRESHOLD, chunk: int = None,
                      scorer: Callable[[torch.Tensor], float] = None,
-                     group_frames: int = 4096, views=None, frame_filter: str = "host") -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
+                     group_frames: int = 4096, views=None, frame_filter: str = "host", resize="host") -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
     """videos yields (video_id, {image_size: frames [S,3,size,size]}, timestamps); encoders = [(model, image_size)].
     ``views`` (``--preprocess hip``, src.image_preprocess.HipViews): videos that carry full-resolution frames under ``RAW_KEY``
     are replaced by their views first (border removal and split views, ``_with_views``): k views of n frames encode as k * n rows.
@@ -256,14 +277,25 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
     0.978 / 0.954 of encoder-bound with groups of 1 024 / 2 048 / 4 096 / 8 192 frames (the last: one group, no look-ahead; tools/micro/ensemble_group_scan.sh).
     ``frame_filter``: "host" or "hip" (src.query_postprocess.FRAME_FILTERS): where the near-duplicate frame filter runs; "hip" needs
     the library's own ops.
+    ``resize``: "host" (the videos arrive resized to every input, the default), "hip" or a src.image_preprocess.HipResize: videos
+    that carry their decoded frames under ``RAW_KEY`` get every encoder input and the scorer's input on the device
+    (``_with_device_inputs``: vsc_frame_inputs_u8, PIL-exact), with ``views`` from the same uploaded frames.
     -> (final descriptors per video, per-model VideoFeatures per video), in input order."""
     if frame_filter not in FRAME_FILTERS:
         raise ValueError(f"frame_filter must be one of {FRAME_FILTERS}, not {frame_filter!r}")
     if frame_filter == "hip" and ops is not HipOps:
         raise ValueError("frame_filter='hip' needs the library's own ops (HipOps); other ops take frame_filter='host'")
+    resizer = None if isinstance(resize, str) else resize
+    if isinstance(resize, str) and check_resize(resize) == "hip":
+        if torch.device(device).type != "cuda":
+            raise ValueError("resize='hip' needs a GPU device")
+        from src.image_preprocess import HipResize
+        resizer = HipResize(device)
     finals, per_model = [], []
     rnd_idx = 0
-    if views is not None:
+    if resizer is not None:
+        videos = _with_device_inputs(videos, list(dict.fromkeys(sz for _, sz in encoders)), views, resizer, scorer is not None)
+    elif views is not None:
         videos = _with_views(videos, list(dict.fromkeys(sz for _, sz in encoders)), views)
     # on the GPU with the library's own ops the per-video post-processing is batched per group and the features stay on the device
     # in between (process_query_group); anything else (the host-logic tests' numpy ops) takes the reference's per-video steps

@@ -625,6 +625,48 @@ def resize_bicubic(frames, boxes, size: int, out=None):
     return out
 
 
+_frame_inputs_handles = {}
+
+
+def frame_inputs_handle():
+    """The vsc_frame_inputs handle of the current library on the current stream (made on first use, kept for the process: it is
+    the stream and owns no device memory)."""
+    import ctypes
+    lib = _rd()
+    stream = current_stream()
+    key = (_PRECISION, stream.value or 0)
+    if key not in _frame_inputs_handles:
+        h = ctypes.c_void_p()
+        check(lib.vsc_frame_inputs_create(stream, ctypes.byref(h)))
+        _frame_inputs_handles[key] = h
+    return _frame_inputs_handles[key]
+
+
+def frame_inputs(frames, targets, outs=None):
+    """Every model input of a video from its uint8 device frames [n, H, W, 3] in one call: per target row (y0, y1, x0, x1, out_h,
+    out_w, top, left, crop_h, crop_w) -- src.dataset.square_target / clip_target build the loaders' -- the box of every frame
+    resized with Pillow's BICUBIC to out_w x out_h, of which the window is kept -> a list of uint8 device tensors [n, crop_h,
+    crop_w, 3], PIL-exact.  ``outs``: contiguous uint8 device tensors of those shapes to write into (e.g. slices of a group's
+    buffer).  Contract and refusals: vsc_frame_inputs_u8 in include/vsc_hip.h."""
+    import ctypes
+
+    import numpy as np
+    lib = _rd()
+    frames = _frames_u8(frames)
+    n, h, w = frames.shape[:3]
+    targets = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1, 10))
+    k = targets.shape[0]
+    if outs is None:
+        outs = [torch.empty((n, max(int(t[8]), 0), max(int(t[9]), 0), 3), dtype=torch.uint8, device=frames.device) for t in targets]
+    assert len(outs) == k
+    for o, t in zip(outs, targets):
+        assert o.is_cuda and o.dtype == torch.uint8 and o.is_contiguous() and tuple(o.shape) == (n, int(t[8]), int(t[9]), 3), \
+            "outs[t] must be a contiguous uint8 device tensor [n, crop_h, crop_w, 3]"
+    ptrs = (ctypes.c_void_p * max(k, 1))(*[ptr(o) if o.numel() else None for o in outs])
+    check(lib.vsc_frame_inputs_u8(frame_inputs_handle(), ptr(frames) if n else None, n, h, w, targets.ctypes.data, k, ptrs))
+    return list(outs)
+
+
 def video_pair_max(q, q_video, n_q_videos: int, r, r_video, n_r_videos: int, threshold: float, capacity: int = 1 << 20):
     """Largest frame score above ``threshold`` per (query video, reference video).
     q [nq, d], r [nr, d] float32; q_video [nq], r_video [nr] int32 video index of every row.
