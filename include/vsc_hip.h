@@ -743,6 +743,54 @@ void vsc_frame_inputs_destroy(vsc_frame_inputs *h);
 int vsc_frame_inputs_u8(vsc_frame_inputs *h, const uint8_t *frames_dev, int64_t n, int32_t fh, int32_t fw, const int32_t *targets_host,
                         int32_t n_targets, uint8_t *const *outs_host);
 
+/* Baseline JPEG frames to uint8 [H][W][3] on the device, any number of frames of any sizes in one call: what
+ * np.asarray(Image.open(f).convert("RGB")) does per frame in the loader workers (src/dataset.py), bit for bit (Pillow 12 on
+ * libjpeg-turbo 3).  Executable contract: tests/jpeg_decode_contract.py.  The caller parses the headers (vsc_hip/jpeg.py does, and
+ * refuses what this entry does not decode: anything but one sequential 8-bit Huffman scan of one or three components in one of the
+ * four sampling classes) and passes
+ *   bytes_dev    uint8 [bytes_len]: the files' bytes, or at least their entropy-coded segments;
+ *   frames_host  int64 [n_frames][VSC_JPEG_FRAME_ROW] (HOST memory), a row = {segment offset in bytes_dev, segment length (from
+ *                behind the SOS header to the marker that ends the scan), height, width, sampling class (0 one component, 1 4:4:4,
+ *                2 4:2:2 = h2v1, 3 4:2:0 = h2v2), restart interval in MCUs (0: none), table set, output byte offset in out_dev,
+ *                component word (byte c = quantisation table | DC Huffman table << 2 | AC Huffman table << 3 of component c), 0};
+ *   tables_host  uint8 [n_table_sets][VSC_JPEG_TABLE_SET_BYTES] (HOST memory), a set = uint16 quant[4][64] little endian in the
+ *                file's zigzag order, uint8 bits[4][16] and uint8 vals[4][256] as in DHT for the tables DC0, DC1, AC0, AC1, one byte
+ *                whose bit t says quantisation table t is present, one byte whose bit (2 * class + id) says that Huffman table is,
+ *                six zero bytes.  Sets are keyed by content: the lookup tables of a set are built on the host the first time the
+ *                handle sees it; every call uploads its sets and its frame table with one copy.
+ * Frame i is written packed at out_dev + its output offset; status_dev int32 [n_frames] gets 0 or the VSC_JPEG_STATUS_* of the
+ * first fault of its scan.  The decode path: sequential Huffman scan (restart: byte-align, RSTn in sequence, DC predictors to 0),
+ * dequantisation, jpeg_idct_islow (13-bit constants, PASS1_BITS 2), libjpeg's range-limit table read through its 10-bit mask,
+ * "fancy" triangle upsampling of subsampled chroma (edges replicated at the real down-sampled width and height = ceil; rounding
+ * +1 / +2 before >> 2 in h2v1, +8 / +7 before >> 4 in h2v2; plain replication when the down-sampled width is 2 or less), the
+ * 16-bit fixed-point YCbCr -> RGB; one component is replicated to three channels.
+ * Two launches per chunk of frames: one wave per frame decodes the scan and runs the IDCT into uint8 planes in the handle's
+ * scratch (grow-only, at most the cap of vsc_jpeg_decode_scratch per chunk -- 1 GiB unless set -- or one frame's planes if that is
+ * more); one workgroup per (frame, 16 rows, 64 columns) upsamples, converts and stores dwords.  No limit on n_frames (below 2^31).
+ * A frame whose scan is damaged (a code in no table, a run past coefficient 63, a missing or wrong RSTn, no bytes left) stops
+ * with its status set; its pixels are unspecified, nothing outside its own planes and output is written and no byte outside its
+ * segment is read.  Refused (VSC_ERR_INVALID) before anything is launched, with nothing written: a null handle or needed pointer,
+ * a segment or an output outside bytes_len / out_len, a side outside 1..VSC_JPEG_MAX_SIDE, an unknown sampling class, a table set
+ * index outside n_table_sets, a component that uses a table its set does not hold, Huffman code lengths that describe no prefix
+ * code.  n_frames == 0 launches nothing.  No alignment is required of bytes_dev, out_dev or the offsets.
+ * The handle holds the caller's stream and only enqueues on it; it owns the scratch and the uploaded tables, so calls of one
+ * handle are ordered by its stream, and growing either buffer frees the old one (which waits for the device, once per size).
+ * vsc_jpeg_decode_scratch: cap_bytes > 0 sets the cap of later calls; last_chunks / scratch_bytes (either may be null) receive the
+ * number of chunks of the handle's last call and the size of its plane scratch. */
+#define VSC_JPEG_FRAME_ROW 10
+#define VSC_JPEG_TABLE_SET_BYTES 1608
+#define VSC_JPEG_MAX_SIDE 16384
+#define VSC_JPEG_STATUS_DATA 1     /* the scan ran out of bytes */
+#define VSC_JPEG_STATUS_CODE 2     /* a code that is in no table */
+#define VSC_JPEG_STATUS_RUN 3      /* a zero run past coefficient 63 */
+#define VSC_JPEG_STATUS_RESTART 4  /* a missing or wrong RSTn */
+typedef struct vsc_jpeg_decode vsc_jpeg_decode;
+int vsc_jpeg_decode_create(void *stream, vsc_jpeg_decode **out);   /* every call of the handle enqueues on this stream */
+void vsc_jpeg_decode_destroy(vsc_jpeg_decode *h);
+int vsc_jpeg_decode_scratch(vsc_jpeg_decode *h, int64_t cap_bytes, int64_t *last_chunks, int64_t *scratch_bytes);
+int vsc_jpeg_decode_u8(vsc_jpeg_decode *h, const uint8_t *bytes_dev, int64_t bytes_len, const int64_t *frames_host, int64_t n_frames,
+                       const uint8_t *tables_host, int32_t n_table_sets, uint8_t *out_dev, int64_t out_len, int32_t *status_dev);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

@@ -19,7 +19,11 @@ repeated view-major.  The video-score gate keeps the original frames.  The defau
 
 ``--resize hip``: the loader workers only decode; every encoder input and the video-score input are made from the uploaded frames
 on the GPU (vsc_frame_inputs_u8, PIL-exact: the same files), with ``--preprocess hip`` from the same upload as the views.  The
-default, ``host``, resizes with Pillow in the workers."""
+default, ``host``, resizes with Pillow in the workers.
+
+``--decode hip`` (with ``--resize hip``): the workers only read the zip members and parse the jpg headers; each video's files are
+uploaded compressed and decoded on the GPU (vsc_jpeg_decode_u8: Pillow's bytes, so the same files).  A video with a frame that is
+not a baseline JPEG of a supported sampling is decoded by its worker as a whole.  The default, ``host``, decodes with Pillow."""
 from __future__ import annotations
 
 import argparse
@@ -31,7 +35,7 @@ from zipfile import ZipFile
 import numpy as np
 import torch
 
-from src.dataset import CLIP_MEAN, CLIP_STD, RESIZES, check_resize, clip_transform_u8, decode_rgb, vit_transform_u8
+from src.dataset import CLIP_MEAN, CLIP_STD, DECODES, RESIZES, bytes_video, check_decode, check_resize, clip_transform_u8, decode_rgb, vit_transform_u8
 from src.matching import calclualte_low_var_dim
 from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
 from src.image_preprocess import HipViews, VIEW_DECISIONS
@@ -54,11 +58,14 @@ class QueryVideos(torch.utils.data.Dataset):
     and resizes the views on the GPU), next to the unchanged CLIP frames.  A video whose frames differ in size is resized here as
     with ``none``: the reference's preprocessing fails on it (np.stack) and leaves it unprocessed.
     ``resize="hip"``: the same raw frames and nothing else -- run_query_videos(resize="hip") makes every input, the CLIP frames
-    included, on the GPU; a video whose frames differ in size is again resized here."""
+    included, on the GPU; a video whose frames differ in size is again resized here.
+    ``decode="hip"`` (with ``resize="hip"``): the zip members are only read and their headers parsed -- the item carries a
+    src.dataset.BytesVideo under ``RAW_KEY``; a video with a frame the parser refuses is decoded here as a whole."""
 
-    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False, preprocess="none", resize="host"):
+    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False, preprocess="none", resize="host", decode="host"):
         assert preprocess in ("none", "hip"), preprocess
         self.zip_prefix, self.preprocess, self.resize = zip_prefix, preprocess, check_resize(resize)
+        self.decode = check_decode(decode, self.resize)
         self.video_ids = [v for v in video_ids if os.path.exists(self._path(v))]
         self.transforms = {s: vit_transform_u8(s, s) for s in sizes}
         if with_clip:
@@ -74,7 +81,12 @@ class QueryVideos(torch.utils.data.Dataset):
         from PIL import Image
         vid = self.video_ids[i]
         with ZipFile(self._path(vid), "r") as z:
-            images = [Image.open(io.BytesIO(z.read(n))).convert("RGB") for n in sorted(z.namelist())]
+            files = [z.read(n) for n in sorted(z.namelist())]
+        video = bytes_video(files) if self.decode == "hip" else None
+        if video is not None:
+            n = video.shape[0]
+            return vid, {RAW_KEY: video}, np.stack([np.arange(n, dtype=np.float32), np.arange(n, dtype=np.float32) + 1.0], axis=1)
+        images = [Image.open(io.BytesIO(f)).convert("RGB") for f in files]
         # [start, end] seconds per frame at 1 fps, the layout the reference's FFmpeg reader yields (infer/src/dataset.py:97-102):
         # a video rejected by the score gate gets a [1, 2] placeholder, so every video's timestamps must be 2-D for
         # store_features to concatenate them
@@ -88,8 +100,8 @@ class QueryVideos(torch.utils.data.Dataset):
         return vid, {s: torch.stack([t(im) for im in images]) for s, t in self.transforms.items()}, stamps
 
 
-def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0, preprocess="none", resize="host"):
-    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip, preprocess, resize)
+def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0, preprocess="none", resize="host", decode="host"):
+    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip, preprocess, resize, decode)
     kw = {"prefetch_factor": 4} if workers > 0 else {}
     return torch.utils.data.DataLoader(data, batch_size=1, shuffle=False, num_workers=workers, collate_fn=lambda b: b[0], **kw)
 
@@ -109,6 +121,7 @@ def resize_of(args) -> str:
 
 def main(args):
     resize = resize_of(args)
+    decode = check_decode(getattr(args, "decode", "host"), resize)
     torch.cuda.set_device(0)
     device = torch.device("cuda", 0)
     specs = [parse_model_spec(s) for s in args.models]
@@ -125,11 +138,11 @@ def main(args):
         from src.model_zoo import _state_dict      # a plain / training checkpoint or the TorchScript archive the reference ships (vsm.torchscript.pt)
         scorer = VideoScorer(clip, VideoScoreHead("vsm_roberta_base", from_reference_state(_state_dict(args.vsm_checkpoint))), device)
     videos = zip_videos(vids, args.zip_prefix, sorted({size for _, size in encoders}), with_clip=scorer is not None,
-                        workers=args.workers, preprocess=args.preprocess, resize=resize)
+                        workers=args.workers, preprocess=args.preprocess, resize=resize, decode=decode)
     finals, per_model = run_query_videos(videos, encoders, pca.transform, scores, device, score_threshold=args.score_threshold,
                                          scorer=scorer, views=HipViews(device, getattr(args, "view_decisions", "host")) if args.preprocess == "hip" else None,
                                          frame_filter=getattr(args, "frame_filter", "host"),   # (a hand-built namespace from before the option)
-                                         resize=resize)
+                                         resize=resize, decode=decode)
     for i, (_, _, path) in enumerate(specs):
         key = os.path.split(path)[-1].split(".")[0]
         os.makedirs(os.path.join(args.output_dir, key), exist_ok=True)
@@ -177,6 +190,9 @@ def build_parser():
     ap.add_argument("--resize", default="host", choices=RESIZES,
                     help="where decoded frames become model inputs: Pillow in the loader workers, or on the device (hip: the workers "
                          "only decode, one kernel call per video makes every encoder input and the video-score input; the same files)")
+    ap.add_argument("--decode", default="host", choices=DECODES,
+                    help="where the zips' jpgs are decoded: Pillow in the loader workers, or on the device (hip, needs --resize hip: the "
+                         "workers hand the compressed files on; the same files)")
     return ap
 
 

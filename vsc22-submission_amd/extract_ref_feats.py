@@ -9,7 +9,11 @@ ranks; each rank writes <save_file>_<rank>.npz, rank 0 merges (as the reference 
 
 ``--resize hip``: the loader workers only decode; every video's frames are uploaded at the zip's resolution and resized to the
 encoder's input on the GPU (vsc_frame_inputs_u8, PIL-exact: the same file).  The default, ``host``, resizes with Pillow in the
-workers."""
+workers.
+
+``--decode hip`` (with ``--resize hip``): the workers only read the zip members and parse the jpg headers; a loader batch's files
+are uploaded compressed and decoded on the GPU (vsc_jpeg_decode_u8: Pillow's bytes, so the same file).  A video with a frame that
+is not a baseline JPEG of a supported sampling is decoded by its worker as a whole.  The default, ``host``, decodes with Pillow."""
 from __future__ import annotations
 
 import argparse
@@ -18,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from src.dataset import RESIZES, ZipFrames, check_resize, collate_fn, raw_collate, vit_transform_u8
+from src.dataset import DECODES, RESIZES, ZipFrames, check_decode, check_resize, collate_fn, raw_collate, vit_transform_u8
 from src.extractor import extract_vsc_feat, extract_vsc_feat_raw
 from vsc.storage import load_features, store_features
 from src.model_zoo import DEFAULT_PRECISION, WEIGHT_FORMATS, load_encoder
@@ -33,6 +37,7 @@ def resize_of(args) -> str:
 def main(args):
     import torch.distributed as dist
     resize = resize_of(args)
+    decode = check_decode(getattr(args, "decode", "host"), resize)
     distributed = "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local_rank)
@@ -45,11 +50,11 @@ def main(args):
     with open(args.input_file, encoding="utf-8") as f:
         vids = [x.strip() for x in f if x.strip()]
     lo, hi = vdist.shard_bounds(len(vids), rank, world_size)
-    data = ZipFrames(vids[lo:hi], args.zip_prefix, vit_transform_u8(image_size, image_size), raw=resize == "hip")   # uint8 to the GPU; normalised in patchify
-    loader = torch.utils.data.DataLoader(data, batch_size=args.batch_size, num_workers=4, collate_fn=raw_collate if resize == "hip" else collate_fn)
+    data = ZipFrames(vids[lo:hi], args.zip_prefix, vit_transform_u8(image_size, image_size), raw="bytes" if decode == "hip" else resize == "hip")   # uint8 to the GPU; normalised in patchify
+    loader = torch.utils.data.DataLoader(data, batch_size=args.batch_size, num_workers=getattr(args, "workers", 4), collate_fn=raw_collate if resize == "hip" else collate_fn)
     if resize == "hip":
-        from src.image_preprocess import HipResize
-        ids, feats, stamps = extract_vsc_feat_raw(model, loader, device, image_size, HipResize(device))
+        from src.image_preprocess import HipDecode, HipResize
+        ids, feats, stamps = extract_vsc_feat_raw(model, loader, device, image_size, HipResize(device), decoder=HipDecode(device) if decode == "hip" else None)
     else:
         ids, feats, stamps = extract_vsc_feat(model, loader, device)
     np.savez(f"{args.save_file}_{rank}.npz", video_ids=ids, features=feats, timestamps=stamps)
@@ -84,6 +89,10 @@ def build_parser():
     ap.add_argument("--resize", default="host", choices=RESIZES,
                     help="where decoded frames are resized to the encoder's input: Pillow in the loader workers, or on the device "
                          "(hip: the workers only decode; the same file)")
+    ap.add_argument("--workers", type=int, default=4, help="loader worker processes (0: the main process reads and decodes the zips itself)")
+    ap.add_argument("--decode", default="host", choices=DECODES,
+                    help="where the zips' jpgs are decoded: Pillow in the loader workers, or on the device (hip, needs --resize hip: the "
+                         "workers hand the compressed files on; the same file)")
     return ap
 
 

@@ -96,6 +96,50 @@ def clip_target(h: int, w: int, size: int = 224):
     return (0, h, 0, w, nh, nw, top, left, size, size)
 
 
+DECODES = ("host", "hip")   # where the zips' jpgs are decoded: Pillow in the loader workers, or vsc_jpeg_decode_u8
+
+
+def check_decode(decode: str, resize: str = "hip") -> str:
+    """``decode`` if it is a known value; "hip" hands compressed bytes to the main process and so needs ``resize="hip"``"""
+    if decode not in DECODES:
+        raise ValueError(f"decode must be one of {DECODES}, not {decode!r}")
+    if decode == "hip" and resize != "hip":
+        raise ValueError("decode='hip' needs resize='hip': the frames it decodes are on the device, where vsc_frame_inputs_u8 resizes them")
+    return decode
+
+
+class BytesVideo:
+    """A video as its loader worker read it for ``--decode hip``: ``data`` uint8 [bytes], the jpg files one after the other,
+    ``offsets`` int64 [S + 1] where each starts and ``records`` the vsc_hip.jpeg.Frame of each.  Every file has been accepted by
+    the parser and all have one size (``shape`` = (S, H, W))."""
+
+    def __init__(self, data, offsets, records):
+        self.data, self.offsets, self.records = data, offsets, records
+
+    @property
+    def shape(self):
+        return len(self.records), self.records[0].height, self.records[0].width
+
+    def files(self):
+        raw = self.data.numpy()
+        return [raw[a:b].tobytes() for a, b in zip(self.offsets[:-1].tolist(), self.offsets[1:].tolist())]
+
+
+def bytes_video(files, warn=None):
+    """The jpg files of one video -> a BytesVideo, or None where the video stays with Pillow as a whole: a file the parser
+    refuses (``warn(message)`` is told why), frames of different sizes, no frames."""
+    from vsc_hip import jpeg
+    data, offsets, records = jpeg.pack(files)
+    for i, r in enumerate(records):
+        if not isinstance(r, jpeg.Frame):
+            if warn is not None:
+                warn(f"frame {i} stays with the host decoder: {r.reason} ({r.message})")
+            return None
+    if len({(r.height, r.width) for r in records}) != 1:
+        return None
+    return BytesVideo(torch.from_numpy(data), offsets, records)
+
+
 def decode_rgb(img) -> np.ndarray:
     """A decoded Pillow image as uint8 [H, W, 3], the array the transforms' ``img.convert("RGB")`` resizes."""
     return np.asarray(img.convert("RGB"), dtype=np.uint8)
@@ -104,9 +148,11 @@ def decode_rgb(img) -> np.ndarray:
 class ZipFrames(torch.utils.data.Dataset):
     """One item = all frames of one video, read from <prefix>/<vid[-2:]>/<vid>.zip of jpgs."""
 
-    def __init__(self, video_ids: Sequence[str], zip_prefix: str, transform, raw: bool = False):
+    def __init__(self, video_ids: Sequence[str], zip_prefix: str, transform, raw=False):
         """``raw`` (``--resize hip``): the workers only decode -- an item is (uint8 [S, H, W, 3] at the zip's own resolution, video_id)
-        for ``raw_collate``; a video whose frames differ in size is resized by ``transform`` here, as without ``raw``."""
+        for ``raw_collate``; a video whose frames differ in size is resized by ``transform`` here, as without ``raw``.
+        ``raw="bytes"`` (``--decode hip``): the workers only read the zip members and parse their headers -- an item is
+        (BytesVideo, video_id); a video with a frame the parser refuses is decoded here as a whole, as with ``raw=True``."""
         self.zip_prefix, self.transform, self.raw = zip_prefix, transform, raw
         self.video_ids = [v for v in video_ids if os.path.exists(self._path(v))]
 
@@ -121,7 +167,12 @@ class ZipFrames(torch.utils.data.Dataset):
         vid = self.video_ids[i]
         with ZipFile(self._path(vid), "r") as z:
             if self.raw:
-                images = [Image.open(io.BytesIO(z.read(n))).convert("RGB") for n in sorted(z.namelist())]
+                files = [z.read(n) for n in sorted(z.namelist())]
+                if self.raw == "bytes":
+                    video = bytes_video(files)
+                    if video is not None:
+                        return video, vid
+                images = [Image.open(io.BytesIO(f)).convert("RGB") for f in files]
                 if len({im.size for im in images}) == 1:
                     return torch.from_numpy(np.stack([decode_rgb(im) for im in images])), vid
                 return torch.stack([self.transform(im) for im in images]), vid

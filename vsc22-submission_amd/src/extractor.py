@@ -30,15 +30,26 @@ def extract_vsc_feat(model, batches: Iterable, device, group_frames: int = 4096)
     return _extract(model, videos(), device, group_frames)
 
 
-def extract_vsc_feat_raw(model, batches: Iterable, device, image_size: int, resizer, group_frames: int = 4096):
+def extract_vsc_feat_raw(model, batches: Iterable, device, image_size: int, resizer, group_frames: int = 4096, decoder=None):
     """``extract_vsc_feat`` for ``--resize hip``: a loader batch is a list of (frames, video_id) as the workers decoded them, uint8
     [S, H, W, 3] at the zip's own resolution (``src.dataset.raw_collate``).  Every video is uploaded and resized to the encoder's
     input by one vsc_frame_inputs_u8 call (``resizer``: src.image_preprocess.HipResize) and the groups are encoded from device
     tensors.  Groups close at the same loader batches and hold the same frames in the same order as with host resizing, so the
     same frames share the same encoder calls.  A video the worker already resized (its frames differ in size) arrives as uint8
-    [S, image_size, image_size, 3] and goes through from the host."""
+    [S, image_size, image_size, 3] and goes through from the host.
+    ``decoder`` (``--decode hip``: src.image_preprocess.HipDecode): the batch's videos that arrive as compressed bytes
+    (src.dataset.BytesVideo) are decoded on the device first, all of them in one vsc_jpeg_decode_u8 call."""
+    from src.dataset import BytesVideo
+
     def videos():
         for batch in batches:
+            packed = [i for i, (frames, _) in enumerate(batch) if isinstance(frames, BytesVideo)]
+            if packed:
+                if decoder is None:
+                    raise ValueError("the loader yields compressed videos (raw='bytes') and there is no decoder")
+                batch = list(batch)
+                for i, frames in zip(packed, decoder([batch[i][0] for i in packed])):
+                    batch[i] = (frames, batch[i][1])
             out = []
             for frames, v in batch:
                 if frames.shape[0] and tuple(frames.shape[1:3]) != (image_size, image_size):

@@ -295,3 +295,69 @@ class HipResize:
         for t in out.values():
             t.record_stream(main)
         return boxes, out
+
+
+class HipDecode:
+    """``--decode hip``: the jpg files of a loader batch decoded on the device.  ``decoder(videos)`` takes the batch's BytesVideo
+    items (src.dataset), copies their bytes into one pinned buffer, uploads it with one non-blocking copy on a side stream and
+    decodes every frame of every video with one vsc_jpeg_decode_u8 call -> per video uint8 [S, H, W, 3] on the device, bit for bit
+    what Pillow gives the workers; HipResize and HipViews take them as they are.  The per-frame status comes back with one small
+    copy that waits for the side stream only.  A video with a frame whose scan the kernel gave up on is decoded by Pillow here,
+    in the main process, as a whole (host frames; Pillow raises or decodes leniently as it does in the workers) and a warning
+    names it.  The caller's stream is ordered behind the results."""
+
+    def __init__(self, device):
+        import torch
+        self.device = torch.device(device)
+        self.stream = torch.cuda.Stream(device=self.device)
+        self.pinned = None
+        self.copied = torch.cuda.Event()      # the last copy out of the pinned buffer is done
+        self.used = False
+
+    def __call__(self, videos):
+        import io
+        import warnings
+
+        import torch
+        from PIL import Image
+        from src.dataset import decode_rgb
+        from vsc_hip import jpeg, ops
+        if not videos:
+            return []
+        sets = jpeg.TableSets()
+        rows, spans, at_bytes, at_out = [], [], 0, 0
+        for v in videos:
+            n, h, w = v.shape
+            rows.append(jpeg.frame_rows(v.records, (v.offsets[:-1] + at_bytes).tolist(), [at_out + i * h * w * 3 for i in range(n)], sets))
+            spans.append((at_out, n, h, w))
+            at_bytes += int(v.data.numel())
+            at_out += n * h * w * 3
+        main = torch.cuda.current_stream(self.device)
+        with torch.cuda.stream(self.stream):
+            if self.used:
+                self.copied.synchronize()
+            if self.pinned is None or self.pinned.numel() < at_bytes:
+                self.pinned = torch.empty(at_bytes, dtype=torch.uint8).pin_memory()
+            at = 0
+            for v in videos:
+                self.pinned[at:at + v.data.numel()].copy_(v.data)
+                at += int(v.data.numel())
+            data = torch.empty(at_bytes, dtype=torch.uint8, device=self.device)
+            data.copy_(self.pinned[:at_bytes], non_blocking=True)
+            self.copied.record(torch.cuda.current_stream(self.device))
+            self.used = True
+            out, status = ops.jpeg_decode(data, np.concatenate(rows), sets.array(), at_out)
+            status = status.cpu().numpy()          # waits for this stream only
+        main.wait_stream(self.stream)
+        out.record_stream(main)
+        frames, first = [], 0
+        for v, (at, n, h, w) in zip(videos, spans):
+            bad = np.flatnonzero(status[first:first + n])
+            first += n
+            if len(bad):
+                warnings.warn(f"--decode hip: frame {int(bad[0])} of a video of {n} frames has a damaged scan (status {int(status[first - n + bad[0]])}); "
+                              "the video is decoded on the host")
+                frames.append(torch.from_numpy(np.stack([decode_rgb(Image.open(io.BytesIO(f))) for f in v.files()])))
+            else:
+                frames.append(out[at:at + n * h * w * 3].view(n, h, w, 3))
+        return frames

@@ -11,7 +11,7 @@ from typing import Callable, Dict, Iterable, List, Sequence, Tuple
 import numpy as np
 import torch
 
-from src.dataset import check_resize
+from src.dataset import BytesVideo, check_decode, check_resize
 from src.query_postprocess import FRAME_FILTERS, HipOps, SCORE_THRESHOLD, process_query_group, process_query_video
 from vsc.index import VideoFeature
 
@@ -229,16 +229,22 @@ def _with_views(videos, sizes: Sequence[int], views):
         yield vid, out, np.tile(stamps, (len(boxes),) + (1,) * (stamps.ndim - 1))
 
 
-def _with_device_inputs(videos, sizes: Sequence[int], views, resizer, with_clip: bool):
+def _with_device_inputs(videos, sizes: Sequence[int], views, resizer, with_clip: bool, decoder=None):
     """``resize="hip"``: a video that carries its decoded frames under ``RAW_KEY`` gets every model input from ``resizer``
     (src.image_preprocess.HipResize) on the device: the encoder inputs -- its views' with ``views`` (``--preprocess hip``, timestamps
     tiled as in ``_with_views``), else the whole frames' -- and, for a scorer, the video-score input unless the worker made it.
-    Other videos (frames of different sizes, resized by the worker) pass through as they are."""
+    Other videos (frames of different sizes, resized by the worker) pass through as they are.  A video that arrives as compressed
+    bytes (``decode="hip"``: a src.dataset.BytesVideo under ``RAW_KEY``) is decoded by ``decoder`` (src.image_preprocess.HipDecode)
+    first; its frames are then on the device already."""
     for vid, frames_by_size, stamps in videos:
         raw = frames_by_size.get(RAW_KEY)
         if raw is None:
             yield vid, frames_by_size, stamps
             continue
+        if isinstance(raw, BytesVideo):
+            if decoder is None:
+                raise ValueError("a video arrives as compressed bytes and there is no decoder: run_query_videos(decode='hip')")
+            raw = decoder([raw])[0]
         clip_key = VideoScorer.KEY if with_clip and VideoScorer.KEY not in frames_by_size else None
         boxes, made = resizer(raw, sizes, views=views, clip_key=clip_key)
         out = {key: f for key, f in frames_by_size.items() if key != RAW_KEY}
@@ -266,7 +272,7 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
                      pca_transform: Callable[[np.ndarray], np.ndarray], video_scores: Dict[str, float], device,
                      ops=HipOps, score_threshold: float = SCORE_THRESHOLD, chunk: int = None,
                      scorer: Callable[[torch.Tensor], float] = None,
-                     group_frames: int = 4096, views=None, frame_filter: str = "host", resize="host") -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
+                     group_frames: int = 4096, views=None, frame_filter: str = "host", resize="host", decode="host") -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
     """videos yields (video_id, {image_size: frames [S,3,size,size]}, timestamps); encoders = [(model, image_size)].
     ``views`` (``--preprocess hip``, src.image_preprocess.HipViews): videos that carry full-resolution frames under ``RAW_KEY``
     are replaced by their views first (border removal and split views, ``_with_views``): k views of n frames encode as k * n rows.
@@ -280,6 +286,9 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
     ``resize``: "host" (the videos arrive resized to every input, the default), "hip" or a src.image_preprocess.HipResize: videos
     that carry their decoded frames under ``RAW_KEY`` get every encoder input and the scorer's input on the device
     (``_with_device_inputs``: vsc_frame_inputs_u8, PIL-exact), with ``views`` from the same uploaded frames.
+    ``decode``: "host" (the default), "hip" or a src.image_preprocess.HipDecode: videos that carry their jpg files under ``RAW_KEY``
+    (src.dataset.BytesVideo) are decoded on the device (vsc_jpeg_decode_u8, Pillow's bytes) before ``resize`` takes them; needs
+    ``resize`` on the device.
     -> (final descriptors per video, per-model VideoFeatures per video), in input order."""
     if frame_filter not in FRAME_FILTERS:
         raise ValueError(f"frame_filter must be one of {FRAME_FILTERS}, not {frame_filter!r}")
@@ -291,10 +300,16 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
             raise ValueError("resize='hip' needs a GPU device")
         from src.image_preprocess import HipResize
         resizer = HipResize(device)
+    decoder = None if isinstance(decode, str) else decode
+    if isinstance(decode, str) and check_decode(decode, "hip" if resizer is not None else "host") == "hip":
+        from src.image_preprocess import HipDecode
+        decoder = HipDecode(device)
+    if decoder is not None and resizer is None:
+        raise ValueError("a decoder needs resize on the device")
     finals, per_model = [], []
     rnd_idx = 0
     if resizer is not None:
-        videos = _with_device_inputs(videos, list(dict.fromkeys(sz for _, sz in encoders)), views, resizer, scorer is not None)
+        videos = _with_device_inputs(videos, list(dict.fromkeys(sz for _, sz in encoders)), views, resizer, scorer is not None, decoder)
     elif views is not None:
         videos = _with_views(videos, list(dict.fromkeys(sz for _, sz in encoders)), views)
     # on the GPU with the library's own ops the per-video post-processing is batched per group and the features stay on the device

@@ -1,0 +1,249 @@
+"""Header parser of ``--decode hip`` (vsc_jpeg_decode_u8, csrc/jpeg_decode.hip): numpy only, and nothing here opens the GPU --
+the loader workers call it.  ``parse(data)`` reads the markers of one JPEG file up to its scan and returns either a ``Frame``
+(what the device needs to decode it: size, sampling class, the tables each component uses, the restart interval, the byte range of
+the entropy-coded segment, and the content of its tables as one fixed-size ``table set``) or a ``Refusal`` whose ``reason`` names
+why the file stays with Pillow.  Nothing is approximated: what the device path cannot decode to Pillow's bytes is refused.
+
+``TableSets`` de-duplicates table sets by content (all frames an encoder wrote with its default tables share one), and
+``frame_rows`` packs the frame table of one vsc_jpeg_decode_u8 call.  The formats are those of include/vsc_hip.h."""
+from __future__ import annotations
+
+from typing import List, NamedTuple, Sequence, Tuple, Union
+
+import numpy as np
+
+# sampling classes
+GRAY, S444, S422, S420 = 0, 1, 2, 3
+SAMPLING_NAMES = ("gray", "4:4:4", "4:2:2", "4:2:0")
+MCU_SIDE = ((8, 8), (8, 8), (8, 16), (16, 16))       # (rows, columns) of luma one MCU covers, per class
+
+# one table set: uint16 quant[4][64] (little endian, in the file's zigzag order), uint8 bits[4][16] and uint8 vals[4][256] of the
+# Huffman tables DC0, DC1, AC0, AC1, then one byte of quantisation tables present (bit = table id), one of Huffman tables present
+# (bit = 2 * class + id) and six bytes of zero
+TABLE_SET_BYTES = 512 + 64 + 1024 + 8
+FRAME_ROW = 10                                        # int64 per frame of the call's frame table
+MAX_SIDE = 16384                                      # vsc_jpeg_decode_u8 takes frames up to this many pixels a side
+
+ZIGZAG = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                   35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62,
+                   63], dtype=np.int32)                # natural (row-major) position of the k-th coefficient of a block
+
+
+class Frame(NamedTuple):
+    height: int
+    width: int
+    sampling: int                                  # GRAY, S444, S422 (h2v1) or S420 (h2v2)
+    comp_tables: Tuple[Tuple[int, int, int], ...]  # per component: (quantisation table, DC Huffman table, AC Huffman table)
+    restart: int                                   # MCUs per restart interval, 0: none
+    seg_start: int                                 # the entropy-coded segment is data[seg_start:seg_end]: from behind the SOS header to the
+    seg_end: int                                   # marker that ends the scan (EOI), or to the end of a file that has none
+    tables: bytes                                  # TABLE_SET_BYTES
+
+    @property
+    def comp_word(self) -> int:
+        """the frame row's component word: byte c = quantisation table | DC table << 2 | AC table << 3 of component c"""
+        return sum((tq | td << 2 | ta << 3) << (8 * c) for c, (tq, td, ta) in enumerate(self.comp_tables))
+
+
+class Refusal(NamedTuple):
+    reason: str                                    # one of REASONS
+    message: str
+
+
+REASONS = ("not_jpeg", "truncated_header", "progressive", "arithmetic", "lossless", "hierarchical", "precision", "components", "adobe_rgb",
+           "rgb_component_ids", "sampling", "multiple_scans", "missing_tables", "quant16", "huffman_table_id", "bad_header", "size")
+
+_SOF_REFUSED = {0xC2: ("progressive", "progressive DCT (SOF2)"), 0xC3: ("lossless", "lossless (SOF3)"),
+                0xC5: ("hierarchical", "differential sequential (SOF5)"), 0xC6: ("hierarchical", "differential progressive (SOF6)"),
+                0xC7: ("hierarchical", "differential lossless (SOF7)"), 0xC9: ("arithmetic", "arithmetic coding (SOF9)"),
+                0xCA: ("arithmetic", "arithmetic progressive (SOF10)"), 0xCB: ("arithmetic", "arithmetic lossless (SOF11)"),
+                0xCD: ("arithmetic", "differential arithmetic (SOF13)"), 0xCE: ("arithmetic", "differential arithmetic (SOF14)"),
+                0xCF: ("arithmetic", "differential arithmetic (SOF15)")}
+
+
+def scan_end(a: np.ndarray, start: int) -> Tuple[int, int]:
+    """(position, marker) of the first marker behind ``start`` that is neither a stuffed zero, a fill byte nor RSTn;
+    (len(a), -1) when the data ends first"""
+    ff = np.flatnonzero(a[start:len(a) - 1] == 0xFF) + start
+    nxt = a[ff + 1]
+    ends = ff[(nxt != 0) & (nxt != 0xFF) & ((nxt < 0xD0) | (nxt > 0xD7))]
+    if len(ends) == 0:
+        return len(a), -1
+    return int(ends[0]), int(a[ends[0] + 1])
+
+
+def parse(data) -> Union[Frame, Refusal]:
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    n = len(a)
+    if n < 4 or a[0] != 0xFF or a[1] != 0xD8:
+        return Refusal("not_jpeg", "no SOI marker")
+    quant = np.zeros((4, 64), np.uint16)
+    bits = np.zeros((4, 16), np.uint8)
+    vals = np.zeros((4, 256), np.uint8)
+    qmask = hmask = 0
+    sof = None
+    restart = 0
+    jfif = False
+    adobe = None
+    pos = 2
+    while True:
+        if pos + 2 > n:
+            return Refusal("truncated_header", "the file ends before its scan")
+        if a[pos] != 0xFF:
+            return Refusal("bad_header", f"byte {int(a[pos]):#x} at {pos} where a marker should be")
+        m = int(a[pos + 1])
+        if m == 0xFF:                                 # a fill byte
+            pos += 1
+            continue
+        if m == 0x01 or 0xD0 <= m <= 0xD7:            # TEM, RSTn: no length
+            pos += 2
+            continue
+        if m == 0xD9:
+            return Refusal("truncated_header", "EOI before any scan")
+        if pos + 4 > n:
+            return Refusal("truncated_header", "the file ends inside a marker segment")
+        length = int(a[pos + 2]) << 8 | int(a[pos + 3])
+        if length < 2:
+            return Refusal("bad_header", f"marker {m:#x} with length {length}")
+        if pos + 2 + length > n:
+            return Refusal("truncated_header", f"the file ends inside the segment of marker {m:#x}")
+        seg = a[pos + 4:pos + 2 + length]
+        if m in _SOF_REFUSED:
+            return Refusal(*_SOF_REFUSED[m])
+        if m == 0xCC:
+            return Refusal("arithmetic", "arithmetic conditioning (DAC)")
+        if m in (0xC0, 0xC1):
+            if sof is not None:
+                return Refusal("hierarchical", "a second frame header")
+            if len(seg) < 6 or len(seg) < 6 + 3 * int(seg[5]):
+                return Refusal("bad_header", "short SOF segment")
+            sof = (int(seg[0]), int(seg[1]) << 8 | int(seg[2]), int(seg[3]) << 8 | int(seg[4]),
+                   [(int(seg[6 + 3 * c]), int(seg[7 + 3 * c]) >> 4, int(seg[7 + 3 * c]) & 15, int(seg[8 + 3 * c])) for c in range(int(seg[5]))])
+        elif m == 0xDB:
+            at = 0
+            while at < len(seg):
+                pq, tq = int(seg[at]) >> 4, int(seg[at]) & 15
+                if pq != 0:
+                    return Refusal("quant16", "a 16-bit quantisation table")
+                if tq > 3 or at + 65 > len(seg):
+                    return Refusal("bad_header", "bad DQT segment")
+                quant[tq] = seg[at + 1:at + 65]
+                qmask |= 1 << tq
+                at += 65
+        elif m == 0xC4:
+            at = 0
+            while at < len(seg):
+                tc, th = int(seg[at]) >> 4, int(seg[at]) & 15
+                if tc > 1 or at + 17 > len(seg):
+                    return Refusal("bad_header", "bad DHT segment")
+                if th > 1:
+                    return Refusal("huffman_table_id", f"Huffman table id {th} (0 and 1 are taken)")
+                count = int(seg[at + 1:at + 17].sum())
+                if count > 256 or at + 17 + count > len(seg):
+                    return Refusal("bad_header", "bad DHT segment")
+                t = 2 * tc + th
+                bits[t] = seg[at + 1:at + 17]
+                vals[t] = 0
+                vals[t, :count] = seg[at + 17:at + 17 + count]
+                hmask |= 1 << t
+                at += 17 + count
+        elif m == 0xDD:
+            if len(seg) < 2:
+                return Refusal("bad_header", "short DRI segment")
+            restart = int(seg[0]) << 8 | int(seg[1])
+        elif m == 0xE0:
+            jfif = jfif or (len(seg) >= 5 and bytes(seg[:5]) == b"JFIF\0")
+        elif m == 0xEE:
+            if len(seg) >= 12 and bytes(seg[:5]) == b"Adobe":
+                adobe = int(seg[11])
+        elif m == 0xDA:
+            break
+        pos += 2 + length
+
+    if sof is None:
+        return Refusal("bad_header", "a scan without a frame header")
+    precision, height, width, comps = sof
+    if precision != 8:
+        return Refusal("precision", f"{precision}-bit samples")
+    if len(comps) not in (1, 3):
+        return Refusal("components", f"{len(comps)} components")
+    if height < 1 or width < 1 or height > MAX_SIDE or width > MAX_SIDE:
+        return Refusal("size", f"{height} x {width} pixels (1 .. {MAX_SIDE} a side; a height of 0 is set by a DNL marker)")
+    if len(comps) == 1:
+        sampling = GRAY
+    else:
+        if adobe is not None and adobe == 0:
+            return Refusal("adobe_rgb", "Adobe APP14 transform 0: the three components are RGB")
+        if adobe is None and not jfif and tuple(c[0] for c in comps) == (82, 71, 66):
+            return Refusal("rgb_component_ids", "components named R, G, B without a JFIF or Adobe marker")
+        fac = tuple((c[1], c[2]) for c in comps)
+        if fac[1:] != ((1, 1), (1, 1)) or fac[0] not in ((1, 1), (2, 1), (2, 2)):
+            return Refusal("sampling", f"sampling factors {fac}")
+        sampling = {(1, 1): S444, (2, 1): S422, (2, 2): S420}[fac[0]]
+    ns = int(seg[0]) if len(seg) else 0
+    if len(seg) < 1 + 2 * ns + 3:
+        return Refusal("bad_header", "short SOS segment")
+    if ns != len(comps):
+        return Refusal("multiple_scans", f"a scan of {ns} of the {len(comps)} components")
+    tables = []
+    for c in range(ns):
+        cs, tdta = int(seg[1 + 2 * c]), int(seg[2 + 2 * c])
+        if cs != comps[c][0]:
+            return Refusal("bad_header", "the scan lists the components in another order than the frame")
+        td, ta = tdta >> 4, tdta & 15
+        if td > 1 or ta > 1:
+            return Refusal("huffman_table_id", f"Huffman table ids {td}, {ta} (0 and 1 are taken)")
+        tq = comps[c][3]
+        if tq > 3 or not (qmask >> tq & 1) or not (hmask >> td & 1) or not (hmask >> (2 + ta) & 1):
+            return Refusal("missing_tables", f"component {c} uses a table the file does not define")
+        tables.append((tq, td, ta))
+    ss, se, ahal = (int(v) for v in seg[1 + 2 * ns:4 + 2 * ns])
+    if (ss, se, ahal) != (0, 63, 0):
+        return Refusal("progressive", f"a scan of coefficients {ss} .. {se}, approximation {ahal:#x}")
+    seg_start = pos + 2 + length
+    seg_end, marker = scan_end(a, seg_start)
+    if marker not in (-1, 0xD9):
+        return Refusal("multiple_scans", f"marker {marker:#x} follows the scan")
+    blob = quant.astype("<u2").tobytes() + bits.tobytes() + vals.tobytes() + bytes([qmask, hmask, 0, 0, 0, 0, 0, 0])
+    return Frame(height, width, sampling, tuple(tables), restart, seg_start, seg_end, blob)
+
+
+class TableSets:
+    """table sets of a call, de-duplicated by content"""
+
+    def __init__(self):
+        self.index = {}
+        self.blobs: List[bytes] = []
+
+    def add(self, blob: bytes) -> int:
+        i = self.index.get(blob)
+        if i is None:
+            assert len(blob) == TABLE_SET_BYTES
+            i = self.index[blob] = len(self.blobs)
+            self.blobs.append(blob)
+        return i
+
+    def __len__(self):
+        return len(self.blobs)
+
+    def array(self) -> np.ndarray:
+        """uint8 [n_table_sets, TABLE_SET_BYTES]"""
+        return np.frombuffer(b"".join(self.blobs), dtype=np.uint8).reshape(len(self.blobs), TABLE_SET_BYTES).copy()
+
+
+def frame_rows(frames: Sequence[Frame], file_offsets: Sequence[int], out_offsets: Sequence[int], sets: TableSets) -> np.ndarray:
+    """the frame table of one call, int64 [n, FRAME_ROW]: (segment offset, segment length, height, width, sampling class, restart
+    interval, table set, output byte offset, component word, 0); ``file_offsets[i]`` is where file i starts in the call's bytes"""
+    rows = np.zeros((len(frames), FRAME_ROW), np.int64)
+    for i, (f, at, out) in enumerate(zip(frames, file_offsets, out_offsets)):
+        rows[i] = (at + f.seg_start, f.seg_end - f.seg_start, f.height, f.width, f.sampling, f.restart, sets.add(f.tables), out, f.comp_word, 0)
+    return rows
+
+
+def pack(files: Sequence) -> Tuple[np.ndarray, np.ndarray, List[Union[Frame, Refusal]]]:
+    """The files of one video (bytes each) -> (uint8 concatenation, int64 offsets [n + 1], [Frame or Refusal per file])"""
+    arrays = [np.frombuffer(f, dtype=np.uint8) for f in files]
+    offsets = np.zeros(len(arrays) + 1, np.int64)
+    np.cumsum([len(x) for x in arrays], out=offsets[1:])
+    data = np.concatenate(arrays) if arrays else np.zeros(0, np.uint8)
+    return data, offsets, [parse(x) for x in arrays]

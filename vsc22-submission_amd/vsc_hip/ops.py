@@ -667,6 +667,45 @@ def frame_inputs(frames, targets, outs=None):
     return list(outs)
 
 
+_jpeg_decode_handles = {}
+
+
+def jpeg_decode_handle():
+    """The vsc_jpeg_decode handle of the current library on the current stream (made on first use, kept for the process: it owns
+    the plane scratch and the uploaded tables of its stream's calls)."""
+    import ctypes
+    lib = _rd()
+    stream = current_stream()
+    key = (_PRECISION, torch.cuda.current_device(), stream.value or 0)
+    if key not in _jpeg_decode_handles:
+        h = ctypes.c_void_p()
+        check(lib.vsc_jpeg_decode_create(stream, ctypes.byref(h)))
+        _jpeg_decode_handles[key] = h
+    return _jpeg_decode_handles[key]
+
+
+def jpeg_decode(data, rows, tables, out_len: int, out=None):
+    """Baseline JPEG frames decoded on the device in one call (vsc_jpeg_decode_u8): ``data`` uint8 device tensor holding the files'
+    bytes, ``rows`` int64 [n, 10] the frame table and ``tables`` uint8 [s, 1608] its table sets, both host arrays as
+    vsc_hip.jpeg.frame_rows / TableSets.array build them -> (uint8 device tensor [out_len] with frame i packed at its row's output
+    offset, bit for bit Pillow's ``convert("RGB")`` array; int32 device tensor [n], 0 or the VSC_JPEG_STATUS_* of a damaged scan).
+    Contract and refusals: vsc_jpeg_decode_u8 in include/vsc_hip.h."""
+    import numpy as np
+    lib = _rd()
+    assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
+    rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 10))
+    tables = np.ascontiguousarray(np.asarray(tables, dtype=np.uint8).reshape(-1, 1608))
+    n = rows.shape[0]
+    if out is None:
+        out = torch.empty(int(out_len), dtype=torch.uint8, device=data.device)
+    assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == int(out_len)
+    status = torch.empty(n, dtype=torch.int32, device=data.device)
+    check(lib.vsc_jpeg_decode_u8(jpeg_decode_handle(), ptr(data) if data.numel() else None, data.numel(), rows.ctypes.data if n else None, n,
+                                 tables.ctypes.data if len(tables) else None, len(tables), ptr(out) if out.numel() else None, out.numel(),
+                                 ptr(status) if n else None))
+    return out, status
+
+
 def video_pair_max(q, q_video, n_q_videos: int, r, r_video, n_r_videos: int, threshold: float, capacity: int = 1 << 20):
     """Largest frame score above ``threshold`` per (query video, reference video).
     q [nq, d], r [nr, d] float32; q_video [nq], r_video [nr] int32 video index of every row.
