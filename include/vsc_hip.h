@@ -791,6 +791,37 @@ int vsc_jpeg_decode_scratch(vsc_jpeg_decode *h, int64_t cap_bytes, int64_t *last
 int vsc_jpeg_decode_u8(vsc_jpeg_decode *h, const uint8_t *bytes_dev, int64_t bytes_len, const int64_t *frames_host, int64_t n_frames,
                        const uint8_t *tables_host, int32_t n_table_sets, uint8_t *out_dev, int64_t out_len, int32_t *status_dev);
 
+/* The same decode in parallel inside a frame (csrc/jpeg_split.hip; executable contract: tests/jpeg_split_contract.py): the bytes
+ * of out_dev and the status of every frame are those of vsc_jpeg_decode_u8, bit for bit.  The unit of work is the item, a run of
+ * consecutive blocks of one frame with a known start state (bit position in the segment, first block in scan order, number of
+ * blocks, DC predictors), one wave each; vsc_jpeg_decode_u8 is "one item per frame from bit 0".
+ * vsc_jpeg_decode_split sets how frames are cut: mode bit 1 (value 1) by restart markers, bit 2 (value 2) by self-synchronising
+ * sub-streams, 0 not at all; sub_bytes (a multiple of 4, >= 32; default 1024) the raw bytes of a sub-stream; rounds (1 .. 128;
+ * default 2) the verification rounds; item_bytes (default 1024) the entropy bytes consecutive restart intervals are grouped up
+ * to.  0 keeps sub_bytes, rounds or item_bytes as they are.  A new handle has mode 3.
+ * vsc_jpeg_decode_split_u8 takes vsc_jpeg_decode_u8's operands plus a CSR of restart-marker offsets in HOST memory:
+ * restart_ptr_host int64 [n_frames + 1] (null: no frame has any), restart_off_host int32 [ptr[n_frames]], row i = the offsets in
+ * frame i's segment of its FF D0..D7, ascending.  Every row is checked before anything is launched (VSC_ERR_INVALID: an offset
+ * outside [0, segment length - 2] or less than two bytes behind its predecessor).  A frame with a restart interval Ri is cut at
+ * its markers only if its row holds ceil(MCUs / Ri) - 1 offsets; any other such frame is one item (and a missing marker is
+ * VSC_JPEG_STATUS_RESTART, as in vsc_jpeg_decode_u8).  An item that is not its frame's last ends with the check made before a
+ * marker is crossed (byte-aligned, less than a byte of padding, the RSTn in sequence) and the marker must stand at the offset
+ * the row gives: an offset that lies is VSC_JPEG_STATUS_RESTART.  A frame without restart interval is cut every sub_bytes raw
+ * bytes: one wave per sub-stream decodes symbols only from (raw bit position of a block start, slot of the block in its MCU) to
+ * the first block start at or behind its end, moving the block start one bit on at a code in no table, a run past coefficient 63
+ * or when the bytes run out; round 0 starts sub-stream i at (8 i sub_bytes, 0), each verification round at its predecessor's
+ * exit of the round before.  The frame keeps its cut iff the last round changed no exit, the block counts add up to the frame's
+ * and every start slot fits; otherwise it is decoded as one item in the same launch.  rounds >= the number of sub-streams always
+ * converges.  No host synchronisation anywhere; launches per call: rounds + 1 (if any frame has sub-streams) + 1, then three per
+ * chunk.  vsc_jpeg_decode_stats waits for the handle's stream and reports its last split call: out[0] frames cut at markers,
+ * out[1] frames cut into sub-streams, out[2] frames the mode wanted cut that were decoded as one item, out[3] items launched
+ * (empty ones included).  For tests and measurements. */
+int vsc_jpeg_decode_split(vsc_jpeg_decode *h, int32_t mode, int32_t sub_bytes, int32_t rounds, int32_t item_bytes);
+int vsc_jpeg_decode_split_u8(vsc_jpeg_decode *h, const uint8_t *bytes_dev, int64_t bytes_len, const int64_t *frames_host, int64_t n_frames,
+                             const uint8_t *tables_host, int32_t n_table_sets, const int64_t *restart_ptr_host, const int32_t *restart_off_host,
+                             uint8_t *out_dev, int64_t out_len, int32_t *status_dev);
+int vsc_jpeg_decode_stats(vsc_jpeg_decode *h, int64_t *out);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

@@ -5,7 +5,7 @@
 # VIEW_DECISIONS=hip (with PREPROCESS=hip) takes the border / split decisions on the GPU too: only the boxes come back (the same files).
 # FRAME_FILTER=hip runs the near-duplicate frame filter on the GPU (the same files wherever a video's frame means are pairwise distinct).
 # RESIZE=hip makes every encoder input and the video-score input from the decoded frames on the GPU instead of with Pillow in the
-# loader workers, with or without PREPROCESS=hip (the same files).  DECODE=hip (with RESIZE=hip) decodes the jpgs on the GPU too: the
+# loader workers, with or without PREPROCESS=hip (the same files).  DECODE_SPLIT=markers|substreams|all (with DECODE=hip) decodes in parallel inside a frame.  DECODE=hip (with RESIZE=hip) decodes the jpgs on the GPU too: the
 # workers hand the compressed files on (the same files; a video with a frame that is no baseline JPEG is decoded by its worker).
 #   CKPT=../checkpoints ZIPS=../data/jpg_zips META=../data/meta bash infer_query.sh
 set -e
@@ -23,5 +23,5 @@ for split in ${SPLITS:-train val test}; do
     --pca_model "$PCA_MODEL" --zip_prefix "$ZIPS" --input_file "$META/$split/${split}_query_ids.txt" --norm_refs "$NORM" \
     --clip_checkpoint "$CKPT/clip.torchscript.pt" --vsm_checkpoint "$CKPT/vsm.torchscript.pt" --output_dir "$OUT" \
     --preprocess "${PREPROCESS:-none}" --view_decisions "${VIEW_DECISIONS:-host}" --score_norm "${SCORE_NORM:-host}" \
-    --frame_filter "${FRAME_FILTER:-host}" --resize "${RESIZE:-host}" --decode "${DECODE:-host}"
+    --frame_filter "${FRAME_FILTER:-host}" --resize "${RESIZE:-host}" --decode "${DECODE:-host}" --decode_split "${DECODE_SPLIT:-none}"
 done

@@ -108,13 +108,27 @@ def check_decode(decode: str, resize: str = "hip") -> str:
     return decode
 
 
+DECODE_SPLITS = ("none", "markers", "substreams", "all")   # --decode_split (vsc_hip.jpeg.SPLITS): how --decode hip cuts a frame into items
+
+
+def check_decode_split(split: str, decode: str = "hip") -> str:
+    """``split`` if it is a known value; anything but "none" cuts the frames that ``decode="hip"`` decodes and so needs it"""
+    if split not in DECODE_SPLITS:
+        raise ValueError(f"decode_split must be one of {DECODE_SPLITS}, not {split!r}")
+    if split != "none" and decode != "hip":
+        raise ValueError("decode_split needs decode='hip' (--decode hip): it is the device decoder whose frames it cuts into items")
+    return split
+
+
 class BytesVideo:
     """A video as its loader worker read it for ``--decode hip``: ``data`` uint8 [bytes], the jpg files one after the other,
     ``offsets`` int64 [S + 1] where each starts and ``records`` the vsc_hip.jpeg.Frame of each.  Every file has been accepted by
-    the parser and all have one size (``shape`` = (S, H, W))."""
+    the parser and all have one size (``shape`` = (S, H, W)).  ``restarts``: the CSR (int64 ptr [S + 1], int32 off) of the
+    restart-marker offsets in every frame's segment (vsc_hip.jpeg.restart_rows), which ``--decode_split`` cuts frames at."""
 
-    def __init__(self, data, offsets, records):
+    def __init__(self, data, offsets, records, restarts=None):
         self.data, self.offsets, self.records = data, offsets, records
+        self.restarts = restarts if restarts is not None else (np.zeros(len(records) + 1, np.int64), np.zeros(0, np.int32))
 
     @property
     def shape(self):
@@ -137,7 +151,7 @@ def bytes_video(files, warn=None):
             return None
     if len({(r.height, r.width) for r in records}) != 1:
         return None
-    return BytesVideo(torch.from_numpy(data), offsets, records)
+    return BytesVideo(torch.from_numpy(data), offsets, records, jpeg.restart_rows(files, records))
 
 
 def decode_rgb(img) -> np.ndarray:

@@ -304,10 +304,14 @@ class HipDecode:
     what Pillow gives the workers; HipResize and HipViews take them as they are.  The per-frame status comes back with one small
     copy that waits for the side stream only.  A video with a frame whose scan the kernel gave up on is decoded by Pillow here,
     in the main process, as a whole (host frames; Pillow raises or decodes leniently as it does in the workers) and a warning
-    names it.  The caller's stream is ordered behind the results."""
+    names it.  The caller's stream is ordered behind the results.
+    ``split`` (``--decode_split``: "none", "markers", "substreams" or "all"): frames are decoded in parallel inside, at their
+    restart markers and / or as self-synchronising sub-streams (vsc_jpeg_decode_split_u8: the same bytes and status)."""
 
-    def __init__(self, device):
+    def __init__(self, device, split="none"):
         import torch
+        from src.dataset import check_decode_split
+        self.split = check_decode_split(split)
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.pinned = None
@@ -346,7 +350,8 @@ class HipDecode:
             data.copy_(self.pinned[:at_bytes], non_blocking=True)
             self.copied.record(torch.cuda.current_stream(self.device))
             self.used = True
-            out, status = ops.jpeg_decode(data, np.concatenate(rows), sets.array(), at_out)
+            restarts = jpeg.concat_restart_rows([v.restarts for v in videos]) if self.split != "none" else None
+            out, status = ops.jpeg_decode(data, np.concatenate(rows), sets.array(), at_out, restarts=restarts, split=self.split)
             status = status.cpu().numpy()          # waits for this stream only
         main.wait_stream(self.stream)
         out.record_stream(main)

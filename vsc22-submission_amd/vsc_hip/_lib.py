@@ -133,6 +133,9 @@ SIGNATURES = {
     "vsc_jpeg_decode_destroy": (None, [c_void_p]),
     "vsc_jpeg_decode_scratch": (c_int32, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "vsc_jpeg_decode_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "vsc_jpeg_decode_split": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
+    "vsc_jpeg_decode_split_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "vsc_jpeg_decode_stats": (c_int32, [c_void_p, c_void_p]),
     "vsc_frame_var_u8":(c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "vsc_canny_count_u8": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
                                      c_void_p, c_void_p]),

@@ -247,3 +247,48 @@ def pack(files: Sequence) -> Tuple[np.ndarray, np.ndarray, List[Union[Frame, Ref
     np.cumsum([len(x) for x in arrays], out=offsets[1:])
     data = np.concatenate(arrays) if arrays else np.zeros(0, np.uint8)
     return data, offsets, [parse(x) for x in arrays]
+
+
+# ---- cutting a frame into items (vsc_jpeg_decode_split_u8, csrc/jpeg_split.hip) ----------------------------------------------------
+SPLITS = ("none", "markers", "substreams", "all")    # --decode_split; the entry's mode is the index: bit 1 markers, bit 2 sub-streams
+SPLIT_SUB_BYTES, SPLIT_ROUNDS, SPLIT_ITEM_BYTES = 1024, 2, 1024
+
+
+def mcus(frame: Frame) -> int:
+    mcu_h, mcu_w = MCU_SIDE[frame.sampling]
+    return -(-frame.height // mcu_h) * -(-frame.width // mcu_w)
+
+
+def restart_offsets(data, frame: Frame) -> np.ndarray:
+    """int32 offsets, from the start of the frame's entropy-coded segment, of every FF D0..D7 in it, ascending"""
+    a = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data
+    seg = a[frame.seg_start:frame.seg_end]
+    if len(seg) < 2:
+        return np.zeros(0, np.int32)
+    return np.flatnonzero((seg[:-1] == 0xFF) & (seg[1:] >= 0xD0) & (seg[1:] <= 0xD7)).astype(np.int32)
+
+
+def expected_restarts(frame: Frame) -> int:
+    """how many RSTn a frame with a restart interval holds; -1 for a frame without one.  Only a frame whose marker scan finds
+    exactly this many is cut at its markers"""
+    return -(-mcus(frame) // frame.restart) - 1 if frame.restart else -1
+
+
+def restart_rows(files: Sequence, records: Sequence) -> Tuple[np.ndarray, np.ndarray]:
+    """the CSR of marker offsets of one call or video: (int64 ptr [n + 1], int32 off); a Refusal or a frame without restart
+    interval has an empty row"""
+    rows = [restart_offsets(np.frombuffer(f, dtype=np.uint8), r) if isinstance(r, Frame) and r.restart else np.zeros(0, np.int32)
+            for f, r in zip(files, records)]
+    ptr = np.zeros(len(rows) + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=ptr[1:])
+    return ptr, (np.concatenate(rows) if rows else np.zeros(0, np.int32)).astype(np.int32)
+
+
+def concat_restart_rows(parts: Sequence[Tuple[np.ndarray, np.ndarray]]) -> Tuple[np.ndarray, np.ndarray]:
+    """the CSRs of several videos -> the CSR of the call that decodes them together"""
+    ptr, at = [np.zeros(1, np.int64)], 0
+    for p, _ in parts:
+        ptr.append(p[1:] + at)
+        at += int(p[-1])
+    off = [o for _, o in parts if len(o)]
+    return np.concatenate(ptr), (np.concatenate(off) if off else np.zeros(0, np.int32)).astype(np.int32)

@@ -684,12 +684,40 @@ def jpeg_decode_handle():
     return _jpeg_decode_handles[key]
 
 
-def jpeg_decode(data, rows, tables, out_len: int, out=None):
+def jpeg_decode_split_mode(split):
+    """``split`` of jpeg_decode -> (mode, sub_bytes, rounds, item_bytes) for vsc_jpeg_decode_split: one of vsc_hip.jpeg.SPLITS, or a
+    dict with "mode" (a name or 0 .. 3) and any of the three numbers; a number that is not given is vsc_hip.jpeg's default, never
+    what an earlier call left in the handle"""
+    from . import jpeg
+    if isinstance(split, str):
+        split = {"mode": split}
+    mode = split.get("mode", "all")
+    if isinstance(mode, str):
+        if mode not in jpeg.SPLITS:
+            raise ValueError(f"split must be one of {jpeg.SPLITS}, not {mode!r}")
+        mode = jpeg.SPLITS.index(mode)
+    return (int(mode), int(split.get("sub_bytes", jpeg.SPLIT_SUB_BYTES)), int(split.get("rounds", jpeg.SPLIT_ROUNDS)),
+            int(split.get("item_bytes", jpeg.SPLIT_ITEM_BYTES)))
+
+
+def jpeg_decode_stats():
+    """vsc_jpeg_decode_stats of the current handle's last jpeg_decode(split=...) call (waits for its stream): (frames cut at
+    restart markers, frames cut into sub-streams, frames the mode wanted cut that were decoded as one item, items launched)"""
+    import numpy as np
+    out = np.zeros(4, np.int64)
+    check(_rd().vsc_jpeg_decode_stats(jpeg_decode_handle(), out.ctypes.data))
+    return tuple(int(v) for v in out)
+
+
+def jpeg_decode(data, rows, tables, out_len: int, out=None, restarts=None, split=None):
     """Baseline JPEG frames decoded on the device in one call (vsc_jpeg_decode_u8): ``data`` uint8 device tensor holding the files'
     bytes, ``rows`` int64 [n, 10] the frame table and ``tables`` uint8 [s, 1608] its table sets, both host arrays as
     vsc_hip.jpeg.frame_rows / TableSets.array build them -> (uint8 device tensor [out_len] with frame i packed at its row's output
     offset, bit for bit Pillow's ``convert("RGB")`` array; int32 device tensor [n], 0 or the VSC_JPEG_STATUS_* of a damaged scan).
-    Contract and refusals: vsc_jpeg_decode_u8 in include/vsc_hip.h."""
+    Contract and refusals: vsc_jpeg_decode_u8 in include/vsc_hip.h.
+    ``split`` (None or "none": one wave per frame, the default): frames are decoded in parallel inside (vsc_jpeg_decode_split_u8, the
+    same bytes and status) -- "markers", "substreams", "all" or a dict (jpeg_decode_split_mode); ``restarts`` is then the CSR of
+    restart-marker offsets (int64 ptr [n + 1], int32 off) as vsc_hip.jpeg.restart_rows builds it, None: no frame has markers."""
     import numpy as np
     lib = _rd()
     assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
@@ -700,6 +728,19 @@ def jpeg_decode(data, rows, tables, out_len: int, out=None):
         out = torch.empty(int(out_len), dtype=torch.uint8, device=data.device)
     assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == int(out_len)
     status = torch.empty(n, dtype=torch.int32, device=data.device)
+    if split is not None and split != "none":
+        h = jpeg_decode_handle()
+        check(lib.vsc_jpeg_decode_split(h, *jpeg_decode_split_mode(split)))
+        rptr = roff = None
+        if restarts is not None:
+            rptr = np.ascontiguousarray(np.asarray(restarts[0], dtype=np.int64))
+            roff = np.ascontiguousarray(np.asarray(restarts[1], dtype=np.int32))
+            assert rptr.shape == (n + 1,) and roff.shape == (int(rptr[-1]),), "restarts must be (int64 ptr [n + 1], int32 off [ptr[n]])"
+        check(lib.vsc_jpeg_decode_split_u8(h, ptr(data) if data.numel() else None, data.numel(), rows.ctypes.data if n else None, n,
+                                           tables.ctypes.data if len(tables) else None, len(tables), rptr.ctypes.data if rptr is not None else None,
+                                           roff.ctypes.data if roff is not None and len(roff) else None, ptr(out) if out.numel() else None, out.numel(),
+                                           ptr(status) if n else None))
+        return out, status
     check(lib.vsc_jpeg_decode_u8(jpeg_decode_handle(), ptr(data) if data.numel() else None, data.numel(), rows.ctypes.data if n else None, n,
                                  tables.ctypes.data if len(tables) else None, len(tables), ptr(out) if out.numel() else None, out.numel(),
                                  ptr(status) if n else None))
