@@ -1,8 +1,6 @@
 // A stand-alone program around the emulated csrc/frame_filter.hip for a host sanitizer run (it is no part of the test suite):
-//   sed -e '/^#pragma clang fp contract(off)$/d' -e 's/^#include "common.h"$/#include "frame_filter.h"/' \
-//       -e '/extern __shared__ __align__(16) unsigned char ff_smem\[\];/d' vsc22-submission_amd/csrc/frame_filter.hip > frame_filter_emu.inc
-//   g++ -std=c++20 -O1 -g -ffp-contract=off -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-//       -I tests/hip_emu -I . [-DFF_EMU_LDS_BYTES=2048] tests/hip_emu/frame_filter_sanitize_main.cpp -o ff_san && ./ff_san
+//   python tests/hip_emu_build.py frame_filter [-DFF_EMU_LDS_BYTES=2048]
+// builds it with -fsanitize=address,undefined (frame_filter_emu.inc is the emulated source) and runs it.
 // Seeded asymmetric matrices of 0 .. 300 rows in one flat buffer at odd offsets, exactly sized allocations (an access one element
 // outside any operand is an error), then the refusals.  It checks only what needs no second implementation: counts in range, kept
 // rows ascending, tails of -1, the visit order a permutation in descending mean.

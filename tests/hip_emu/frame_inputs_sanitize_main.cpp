@@ -1,9 +1,6 @@
 // A stand-alone program around the emulated csrc/frame_inputs.hip for a host sanitizer run (it is no part of the test suite):
-//   sed -e '/^#pragma clang fp contract(off)$/d' -e 's/^#include "common.h"$/#include "frame_inputs.h"/' \
-//       -e '/extern __shared__ __align__(16) unsigned char fi_smem\[\];/d' vsc22-submission_amd/csrc/frame_inputs.hip > frame_inputs_emu.inc
-//   g++ -std=c++20 -O1 -g -ffp-contract=off -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-//       -I tests/hip_emu -I vsc22-submission_amd/csrc -I . [-DFI_EMU_LDS_BYTES=4096 | -DFI_EMU_LDS_BYTES=8] \
-//       tests/hip_emu/frame_inputs_sanitize_main.cpp -o fi_san && ./fi_san
+//   python tests/hip_emu_build.py frame_inputs [-DFI_EMU_LDS_BYTES=4096 | -DFI_EMU_LDS_BYTES=8]
+// builds it with -fsanitize=address,undefined (frame_inputs_emu.inc is the emulated source) and runs it.
 // Seeded frames and every output in exactly sized allocations (an access one byte outside any operand is an error; the staging
 // loads round down to dwords, so the frames' first and last bytes are what they must not step over), downscales, upscales, an
 // identity, windows at odd byte offsets, more than one tile of output columns, the vertical-first shape, then the refusals.  It
@@ -73,6 +70,6 @@ int main() {
     if (vsc_frame_inputs_u8(h, frame, 0, 37, 53, good, 1, outp) != 0 || vsc_frame_inputs_u8(h, frame, 1, 37, 53, nullptr, 0, nullptr) != 0) return 11;
     if (vsc_frame_inputs_u8(h, frame, 1, 37, 53, good, 1, outp) != 0) return 12;
     vsc_frame_inputs_destroy(h);
-    printf("frame_inputs emulated under the sanitizers: ok (%zu calls, %zu launches, LDS budget %d)\n", calls, fi_emu_launches(), (int)VSC_FRAME_INPUTS_LDS_BYTES);
+    printf("frame_inputs emulated under the sanitizers: ok (%zu calls, %zu launches, LDS budget %d)\n", calls, emu_launches(), (int)VSC_FRAME_INPUTS_LDS_BYTES);
     return 0;
 }

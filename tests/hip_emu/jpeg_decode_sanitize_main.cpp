@@ -1,13 +1,12 @@
 // A stand-alone program around the emulated csrc/jpeg_decode.hip for a host sanitizer run; tests/test_jpeg_decode_emulated.py builds
-// and runs it as a child process (no sanitizer runtime is loaded into Python):
-//   sed -e 's/^#include "common.h"$/#include "jpeg_decode.h"/' vsc22-submission_amd/csrc/jpeg_decode.hip > jpeg_decode_emu.inc
-//   g++ -std=c++20 -O1 -g -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined -I tests/hip_emu \
-//       -I vsc22-submission_amd/csrc -I . tests/hip_emu/jpeg_decode_sanitize_main.cpp -o jd_san && ./jd_san calls.bin
+// it with -fsanitize=address,undefined (tests/hip_emu_build.py: build_sanitized; jpeg_decode_emu.inc is the emulated source) and
+// runs it as a child process: no sanitizer runtime is loaded into Python.  By hand, with the test's calls file:
+//   python tests/hip_emu_build.py jpeg_decode calls.bin
 // calls.bin is written by the test from tests/jpeg_decode_cases.py (the files are made by Pillow's encoder at test time), int64
 // little endian throughout: the number of calls, then per call {n_frames, bytes_len, n_table_sets, out_len, scratch cap or 0,
 // chunks expected or 0}, the frame table [n_frames][10], per frame 0 (must decode: status 0 and the expected bytes) or 1 (a damaged
 // scan: status not 0), the table sets, the bytes and the expected output (padded to whole int64s each).  Every operand sits in an
-// allocation of exactly its size, so does the kernels' scratch (jpeg_decode.h): an access one byte outside any of them is an error.
+// allocation of exactly its size, so does the kernels' scratch (common.h's hipMalloc): an access one byte outside any of them is an error.
 // Every call runs over outputs pre-filled with 0x00 and with 0xFF: a frame that decodes is written completely and from the inputs
 // alone, and the bytes between and around the frames' outputs keep their fill (a damaged frame's own output is unspecified).
 #include "jpeg_decode_emu.inc"
@@ -85,7 +84,7 @@ int main(int argc, char **argv) {
     // the refusals: nothing is launched
     vsc_jpeg_decode *h = nullptr;
     if (vsc_jpeg_decode_create(nullptr, &h) != 0 || vsc_jpeg_decode_create(nullptr, nullptr) == 0) return 7;
-    const size_t launches = jd_emu_launches();
+    const size_t launches = emu_launches();
     uint8_t bytes[16] = {0}, tables[VSC_JPEG_TABLE_SET_BYTES] = {0}, out[3] = {0x5A, 0x5A, 0x5A};
     int32_t status = 77;
     tables[1600] = 1, tables[1601] = 5, tables[512] = 1, tables[512 + 32] = 1;     // one code of length 1 in DC0 and in AC0
@@ -102,11 +101,11 @@ int main(int argc, char **argv) {
     tables[512] = 3;                                                                // three codes of length 1: no prefix code
     if (vsc_jpeg_decode_u8(h, bytes, 16, good, 1, tables, 1, out, 3, &status) == 0) return 11;
     if (vsc_jpeg_decode_u8(h, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, 0, nullptr) != 0) return 12;
-    if (jd_emu_launches() != launches || status != 77 || out[0] != 0x5A || out[1] != 0x5A || out[2] != 0x5A) return 13;
+    if (emu_launches() != launches || status != 77 || out[0] != 0x5A || out[1] != 0x5A || out[2] != 0x5A) return 13;
     tables[512] = 1;
     if (vsc_jpeg_decode_u8(h, bytes, 16, good, 1, tables, 1, out, 3, &status) != 0 || status != 0) return 14;     // sixteen zero bytes: a 1 x 1 gray frame
     vsc_jpeg_decode_destroy(h);
     printf("jpeg_decode emulated under the sanitizers: ok (%lld calls, %zu frames, %zu of them damaged, %zu launches)\n", (long long)n_calls, frames_run, damaged,
-           jd_emu_launches());
+           emu_launches());
     return 0;
 }

@@ -1,14 +1,14 @@
 // A stand-alone program around the emulated csrc/jpeg_decode.hip + csrc/jpeg_split.hip for a host sanitizer run;
-// tests/test_jpeg_split_emulated.py builds it with -fsanitize=address,undefined and runs it as a child process (no sanitizer
-// runtime is loaded into Python).  jpeg_split_emu.inc is the two sources, one behind the other, each with its
-// `#include "common.h"` replaced by `#include "jpeg_split.h"`.
+// tests/test_jpeg_split_emulated.py builds it with -fsanitize=address,undefined (tests/hip_emu_build.py: build_sanitized) and runs
+// it as a child process (no sanitizer runtime is loaded into Python).  jpeg_split_emu.inc is the two emulated sources, one behind
+// the other.  By hand, with the test's calls file: python tests/hip_emu_build.py jpeg_split calls.bin
 // calls.bin is written by the test, int64 little endian throughout: the number of calls, then per call {n_frames, bytes_len,
 // n_table_sets, out_len, scratch cap or 0, mode, sub_bytes, rounds, item_bytes, number of marker offsets, the four statistics
 // expected}, the frame table [n_frames][10], per frame what is expected (0: status 0 and the expected bytes; 1: a damaged scan, the
 // status vsc_jpeg_decode_u8 gives for it, which is not 0; 2: VSC_JPEG_STATUS_RESTART; 3: a flipped byte, the status
 // vsc_jpeg_decode_u8 gives for it, which may be 0), the marker rows' ptr [n_frames + 1], the
 // offsets (int32, padded), the table sets, the bytes and the expected output (padded to whole int64s each).  Every operand sits in
-// an allocation of exactly its size, so does the kernels' scratch (jpeg_decode.h): an access one byte outside any of them is an
+// an allocation of exactly its size, so does the kernels' scratch (common.h's hipMalloc): an access one byte outside any of them is an
 // error.  Every call runs twice on one handle, over outputs pre-filled with 0x00 and with 0xFF: a frame that decodes is written
 // completely and from the inputs alone, and the bytes between and around the frames' outputs keep their fill.
 #include "jpeg_split_emu.inc"
@@ -106,7 +106,7 @@ int main(int argc, char **argv) {
     // the refusals: nothing is launched
     vsc_jpeg_decode *h = nullptr;
     if (vsc_jpeg_decode_create(nullptr, &h) != 0) return 7;
-    const size_t launches = jd_emu_launches();
+    const size_t launches = emu_launches();
     uint8_t bytes[16] = {0}, tables[VSC_JPEG_TABLE_SET_BYTES] = {0}, out[3] = {0x5A, 0x5A, 0x5A};
     int32_t status = 77;
     tables[1600] = 1, tables[1601] = 5, tables[512] = 1, tables[512 + 32] = 1;     // one code of length 1 in DC0 and in AC0
@@ -135,7 +135,7 @@ int main(int argc, char **argv) {
     if (vsc_jpeg_decode_stats(h, nullptr) == 0 || vsc_jpeg_decode_stats(nullptr, st) == 0) return 10;
     if (vsc_jpeg_decode_split_u8(h, nullptr, 0, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr) != 0) return 12;
     if (vsc_jpeg_decode_stats(h, st) != 0 || st[0] || st[1] || st[2] || st[3]) return 12;
-    if (jd_emu_launches() != launches || status != 77 || out[0] != 0x5A || out[1] != 0x5A || out[2] != 0x5A) return 13;
+    if (emu_launches() != launches || status != 77 || out[0] != 0x5A || out[1] != 0x5A || out[2] != 0x5A) return 13;
     // sixteen zero bytes: a 1 x 1 frame; two offsets where none are expected: taken as unsplit
     if (vsc_jpeg_decode_split_u8(h, bytes, 16, good, 1, tables, 1, ptr2, in, out, 3, &status) != 0 || status != 0) return 14;
     if (vsc_jpeg_decode_stats(h, st) != 0 || st[0] != 0 || st[1] != 0 || st[2] != 1 || st[3] != 1) return 15;
@@ -143,6 +143,6 @@ int main(int argc, char **argv) {
     if (vsc_jpeg_decode_stats(h, st) != 0 || st[0] != 1 || st[3] != 1) return 17;
     vsc_jpeg_decode_destroy(h);
     printf("jpeg_split emulated under the sanitizers: ok (%lld calls, %zu frames, %zu of them damaged, %zu launches)\n", (long long)n_calls, frames_run, damaged,
-           jd_emu_launches());
+           emu_launches());
     return 0;
 }

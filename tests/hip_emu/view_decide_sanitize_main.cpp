@@ -1,8 +1,6 @@
 // A stand-alone program around the emulated csrc/view_decide.hip for a host sanitizer run (it is no part of the test suite):
-//   sed -e '/^#pragma clang fp contract(off)$/d' -e 's/^#include "common.h"$/#include "view_decide.h"/' \
-//       -e '/extern __shared__ __align__(16) unsigned char vd_smem\[\];/d' vsc22-submission_amd/csrc/view_decide.hip > view_decide_emu.inc
-//   g++ -std=c++20 -O1 -g -ffp-contract=off -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-//       -I tests/hip_emu -I . tests/hip_emu/view_decide_sanitize_main.cpp -o vd_san && ./vd_san
+//   python tests/hip_emu_build.py view_decide
+// builds it with -fsanitize=address,undefined (view_decide_emu.inc is the emulated source) and runs it.
 // Seeded maps of 1 .. 300 pixels on a side -- plain, letterboxed, stacked, a 2 x 2 grid, thin ones around 8192 pixels -- in two flat
 // buffers at odd offsets, exactly sized allocations (an access one element outside any operand is an error), then the refusals.  It
 // checks only what needs no second implementation: status 0 or 1, counts in range, boxes inside the frame and non-empty, tails of -1.

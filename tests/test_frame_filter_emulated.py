@@ -1,54 +1,32 @@
-"""csrc/frame_filter.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one OS
-thread per GPU thread, barriers for __syncthreads and the wave intrinsics) plus tests/hip_emu/frame_filter.h (the dynamic LDS as a
-static buffer, the scratch slot filled with 0xFF when fresh) with -ffp-contract=off, and must equal the executable contract
+"""csrc/frame_filter.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics, LDS filled with a pattern
+before every launch, the scratch slot filled with 0xFF when fresh) with -ffp-contract=off, and must equal the executable contract
 (tests/frame_filter_contract.py): kept rows, counts, the bits of the means, the visit order -- every case up to 300 rows, single and
 batched at odd offsets, more items than one launch holds, outputs between 0xFF guard bands with the -1 tails intact, the refusals.
 A second build with the LDS budget lowered to 2 KiB sends every matrix of 86 rows and more through the scratch path, which on the
 device begins at 1 089 rows (tests/test_gpu_frame_filter.py runs those)."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
 import frame_filter_cases as cases  # noqa: E402
 import frame_filter_contract as C  # noqa: E402
+import hip_emu_build  # noqa: E402
+from hip_emu_build import guarded, guards_intact  # noqa: E402     (guards of 8 elements of 0xFF bytes: -1 as int32, NaN as float32)
 
-KERNEL = os.path.join(ROOT, "vsc22-submission_amd", "csrc", "frame_filter.hip")
-P, I64, F32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_float
-GUARD = 8
+P = ctypes.c_void_p
 SMALL = cases.names(cases.EMULATED_MAX)
-
-
-def guarded(count, dtype):
-    """(buffer, view of `count` elements) with GUARD elements of 0xFF bytes on both sides; 0xFF is -1 as int32 and NaN as float32"""
-    buf = np.full((count + 2 * GUARD) * np.dtype(dtype).itemsize, 0xFF, np.uint8).view(dtype)
-    return buf, buf[GUARD:GUARD + count]
-
-
-def guards_intact(buf):
-    raw = buf.view(np.uint8)
-    g = GUARD * buf.dtype.itemsize
-    return bool((raw[:g] == 0xFF).all() and (raw[len(raw) - g:] == 0xFF).all())
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_frame_filter_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_frame_filter_destroy.argtypes = [P]
-        lib.vsc_frame_filter_destroy.restype = None
-        lib.vsc_frame_filter_f32.argtypes = [P, P, I64, P, I64, F32, P, P, P, P]
-        lib.ff_emu_scratch_allocs.restype = ctypes.c_size_t
-        lib.ff_emu_scratch_bytes.restype = ctypes.c_size_t
         self.handle = P()
         assert lib.vsc_frame_filter_create(None, ctypes.byref(self.handle)) == 0
 
@@ -69,22 +47,8 @@ class Emulated:
         return (rc, *(v for _, v in bufs))
 
 
-def build(tmp_path_factory, tag, extra=()):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu_frame_filter_" + tag)
-    src = open(KERNEL).read()
-    src, n = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)     # the build passes -ffp-contract=off
-    assert n == 1, "frame_filter.hip no longer has the line the emulation replaces"
-    src, n = re.subn(r'^#include "common.h"\n', '#include "frame_filter.h"\n', src, flags=re.M)
-    assert n == 1
-    src, n = re.subn(r"^ *extern __shared__ __align__\(16\) unsigned char ff_smem\[\];\n", "", src, flags=re.M)   # frame_filter.h's buffer
-    assert n == 1
-    (work / "frame_filter.cpp").write_text(src)
-    lib = str(work / "libframe_filter_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", *extra, "-I", os.path.join(HERE, "hip_emu"),
-                           "-o", lib, str(work / "frame_filter.cpp")])
-    return Emulated(ctypes.CDLL(lib))
+def build(tmp_path_factory, tag, defines=()):
+    return Emulated(hip_emu_build.build_shared(tmp_path_factory, "frame_filter_" + tag, hip_emu_build.source("frame_filter"), defines))
 
 
 @pytest.fixture(scope="module")
@@ -134,13 +98,13 @@ def test_emulated_kernel_equals_contract(emulated, name):
 @pytest.mark.parametrize("name", [n for n in SMALL if len(cases.get(n)["s"]) >= 63])
 def test_emulated_scratch_path_equals_contract(emulated_scratch, name):
     """the same source with the adjacency bits in the scratch (0xFF when fresh, larger leftovers afterwards)"""
-    before = emulated_scratch.lib.ff_emu_scratch_bytes()
+    before = emulated_scratch.lib.emu_scratch_bytes(-1)
     check_case(emulated_scratch, name)
     L = len(cases.get(name)["s"])
     if 8 * L * (1 + (L + 63) // 64) > 2048:
-        assert emulated_scratch.lib.ff_emu_scratch_bytes() >= max(before, 8 * L * ((L + 63) // 64))
+        assert emulated_scratch.lib.emu_scratch_bytes(-1) >= max(before, 8 * L * ((L + 63) // 64))
     else:
-        assert emulated_scratch.lib.ff_emu_scratch_bytes() == before
+        assert emulated_scratch.lib.emu_scratch_bytes(-1) == before
 
 
 def check_batch(emu, flat, items, mats, thr):

@@ -1,6 +1,6 @@
-"""csrc/frame_inputs.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one OS
-thread per GPU thread, barriers for __syncthreads) plus tests/hip_emu/frame_inputs.h (the dynamic LDS as a static buffer filled
-with a pattern before every launch, the scratch slot filled with 0xFF when fresh, the coefficient cache on the host) and must equal
+"""csrc/frame_inputs.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads, LDS filled with a pattern before every launch, the
+scratch slot filled with 0xFF when fresh) plus tests/hip_emu/frame_inputs.h (the coefficient cache on the host) and must equal
 the executable contract (tests/frame_inputs_contract.py) bit for bit on every case of tests/frame_inputs_cases.py small enough for
 one OS thread per lane: outputs between 0xFF guard bands at odd byte addresses, all targets of a case in one call, the refusals.
 A second build with the LDS budget lowered to 8 bytes sends every target through the two-pass path, which on the device begins
@@ -8,46 +8,33 @@ where one output row's vertical support no longer fits 160 KiB (tests/test_gpu_f
 4 KiB splits the fused targets into bands of a few rows fed by one staged source row at a time."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
 import frame_inputs_cases as cases  # noqa: E402
+import hip_emu_build  # noqa: E402
 
-CSRC = os.path.join(ROOT, "vsc22-submission_amd", "csrc")
-KERNEL = os.path.join(CSRC, "frame_inputs.hip")
-P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+P = ctypes.c_void_p
 GUARD = 13          # bytes of 0xFF on both sides of every buffer: odd, so that inputs and outputs start at odd addresses
 SMALL = cases.names()
 
 
-def guarded(nbytes):
-    """(buffer, view of nbytes) with GUARD bytes of 0xFF on both sides"""
-    buf = np.full(nbytes + 2 * GUARD, 0xFF, np.uint8)
-    return buf, buf[GUARD:GUARD + nbytes]
+def guarded(nbytes, fill=0xFF):
+    return hip_emu_build.guarded(nbytes, np.uint8, GUARD, fill)
 
 
 def guards_intact(buf):
-    return bool((buf[:GUARD] == 0xFF).all() and (buf[len(buf) - GUARD:] == 0xFF).all())
+    return hip_emu_build.guards_intact(buf, GUARD)
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_frame_inputs_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_frame_inputs_destroy.argtypes = [P]
-        lib.vsc_frame_inputs_destroy.restype = None
-        lib.vsc_frame_inputs_u8.argtypes = [P, P, I64, I32, I32, P, I32, P]
-        for f in (lib.fi_emu_scratch_bytes, lib.fi_emu_launches, lib.fi_emu_blocks, lib.fi_emu_tables):
-            f.restype = ctypes.c_size_t
         self.handle = P()
         assert lib.vsc_frame_inputs_create(None, ctypes.byref(self.handle)) == 0
 
@@ -61,35 +48,15 @@ class Emulated:
         fbuf, fview = guarded(frames.size)
         fview[:] = frames.reshape(-1)
         t = np.ascontiguousarray(np.asarray(targets, np.int32).reshape(-1, 10))
-        bufs = [guarded(n * int(r[8]) * int(r[9]) * 3) for r in t]
-        for _, v in bufs:
-            v[:] = fill
+        bufs = [guarded(n * int(r[8]) * int(r[9]) * 3, fill) for r in t]
         ptrs = (P * max(len(t), 1))(*[v.ctypes.data for _, v in bufs])
         rc = self.lib.vsc_frame_inputs_u8(self.handle if handle == "own" else handle, fview.ctypes.data, n, h, w, t.ctypes.data, len(t), ptrs)
         assert guards_intact(fbuf) and all(guards_intact(b) for b, _ in bufs), "a guard band was written"
         return rc, [v.reshape(n, int(r[8]), int(r[9]), 3) for (_, v), r in zip(bufs, t)]
 
 
-def build(tmp_path_factory, tag, extra=()):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu_frame_inputs_" + tag)
-    (work / "frame_inputs.cpp").write_text(emulated_source())
-    lib = str(work / "libframe_inputs_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", *extra,
-                           "-I", os.path.join(HERE, "hip_emu"), "-I", CSRC, "-o", lib, str(work / "frame_inputs.cpp")])
-    return Emulated(ctypes.CDLL(lib))
-
-
-def emulated_source():
-    src = open(KERNEL).read()
-    src, n = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)     # the build passes -ffp-contract=off
-    assert n == 1, "frame_inputs.hip no longer has the line the emulation replaces"
-    src, n = re.subn(r'^#include "common.h"\n', '#include "frame_inputs.h"\n', src, flags=re.M)
-    assert n == 1
-    src, n = re.subn(r"^ *extern __shared__ __align__\(16\) unsigned char fi_smem\[\];\n", "", src, flags=re.M)   # frame_inputs.h's buffer
-    assert n == 1
-    return src
+def build(tmp_path_factory, tag, defines=()):
+    return Emulated(hip_emu_build.build_shared(tmp_path_factory, "frame_inputs_" + tag, hip_emu_build.source("frame_inputs"), defines))
 
 
 @pytest.fixture(scope="module")
@@ -123,18 +90,18 @@ def vertical_first(target):
 @pytest.mark.parametrize("name", SMALL)
 def test_emulated_kernel_equals_contract(emulated, name):
     """all targets of the case in one call; one launch per fused target, two per vertical-first one"""
-    before = emulated.lib.fi_emu_launches()
+    before = emulated.lib.emu_launches()
     check_case(emulated, name)
     targets = cases.get(name)["targets"]
-    assert emulated.lib.fi_emu_launches() - before == sum(2 if vertical_first(t) else 1 for t in targets)
+    assert emulated.lib.emu_launches() - before == sum(2 if vertical_first(t) else 1 for t in targets)
 
 
 @pytest.mark.parametrize("name", SMALL)
 def test_emulated_two_pass_path_equals_contract(emulated_two_pass, name):
-    before = emulated_two_pass.lib.fi_emu_launches()
+    before = emulated_two_pass.lib.emu_launches()
     check_case(emulated_two_pass, name)
-    assert emulated_two_pass.lib.fi_emu_launches() - before == 2 * len(cases.get(name)["targets"])
-    assert emulated_two_pass.lib.fi_emu_scratch_bytes() > 0
+    assert emulated_two_pass.lib.emu_launches() - before == 2 * len(cases.get(name)["targets"])
+    assert emulated_two_pass.lib.emu_scratch_bytes(-1) > 0
 
 
 @pytest.fixture(scope="module")
@@ -153,18 +120,18 @@ def test_emulated_small_bands_equal_contract(emulated_bands, name):
 def test_emulated_band_count_does_not_divide_the_rows(emulated_bands):
     """64 x 48 -> a 23 x 19 window under 4 KiB: one fused launch whose 23 output rows (a prime) split into several bands per frame"""
     lib = emulated_bands.lib
-    launches, blocks = lib.fi_emu_launches(), lib.fi_emu_blocks()
+    launches, blocks = lib.emu_launches(), lib.emu_blocks()
     check_case(emulated_bands, "64x48_rect_window")
-    assert lib.fi_emu_launches() - launches == 1
-    bands = (lib.fi_emu_blocks() - blocks) // 2
-    assert bands > 1 and (lib.fi_emu_blocks() - blocks) % 2 == 0 and 23 % bands != 0, bands
+    assert lib.emu_launches() - launches == 1
+    bands = (lib.emu_blocks() - blocks) // 2
+    assert bands > 1 and (lib.emu_blocks() - blocks) % 2 == 0 and 23 % bands != 0, bands
 
 
 def test_emulated_tables_are_built_once(emulated):
     check_case(emulated, "64x48_rect_window")
-    tables = emulated.lib.fi_emu_tables()
+    tables = emulated.lib.emu_coeff_tables()
     check_case(emulated, "64x48_rect_window")
-    assert emulated.lib.fi_emu_tables() == tables
+    assert emulated.lib.emu_coeff_tables() == tables
 
 
 def test_emulated_refusals_write_nothing(emulated, emulated_two_pass):
@@ -197,11 +164,11 @@ def test_emulated_refusals_write_nothing(emulated, emulated_two_pass):
         assert lib.vsc_frame_inputs_u8(h, f.ctypes.data, 2, 37, 53, t.ctypes.data, 1, None) != 0           # no output table
         assert lib.vsc_frame_inputs_u8(h, f.ctypes.data, 2, 0, 53, t.ctypes.data, 1, ptrs) != 0
         assert (out == 0x5A).all(), "a refused call wrote"
-        launches = lib.fi_emu_launches()
+        launches = lib.emu_launches()
         assert lib.vsc_frame_inputs_u8(h, f.ctypes.data, 0, 37, 53, t.ctypes.data, 1, ptrs) == 0           # no frames: nothing launched
         assert lib.vsc_frame_inputs_u8(h, f.ctypes.data, 2, 37, 53, None, 0, None) == 0                    # no targets
         empty = np.asarray([good[:8] + (0, 17)], np.int32)
         assert lib.vsc_frame_inputs_u8(h, f.ctypes.data, 2, 37, 53, empty.ctypes.data, 1, (P * 1)(None)) == 0   # an empty window needs no output
-        assert lib.fi_emu_launches() == launches and (out == 0x5A).all()
+        assert lib.emu_launches() == launches and (out == 0x5A).all()
         assert lib.vsc_frame_inputs_create(None, None) != 0
         check_case(emu, "37x53_sq17_sq24_clip24")                               # and the entry still works

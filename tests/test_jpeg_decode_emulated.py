@@ -1,15 +1,13 @@
-"""csrc/jpeg_decode.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one OS
-thread per GPU thread, barriers for __syncthreads) plus tests/hip_emu/jpeg_decode.h (device allocations as exactly sized host
-allocations filled with 0xFF, the wave-uniform marker as the identity) and must equal the executable contract
-(tests/jpeg_decode_contract.py) bit for bit on every case of tests/jpeg_decode_cases.py small enough for one OS thread per lane:
+"""csrc/jpeg_decode.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads, device allocations as exactly sized host
+allocations filled with 0xFF) plus tests/hip_emu/jpeg_decode.h (the wave-uniform marker as the identity) and must equal the executable
+contract (tests/jpeg_decode_contract.py) bit for bit on every case of tests/jpeg_decode_cases.py small enough for one OS thread per lane:
 bytes and outputs between 0xFF guard bands at odd addresses, frames at odd output offsets.  Damaged scans (a scan cut at a third,
 a flipped byte, a deleted RSTn) give a status other than 0, leave the guards and the bytes between the frames alone and do not
 disturb the other frames of their call.  The same cases then run in a stand-alone program built with -fsanitize=address,undefined
 (tests/hip_emu/jpeg_decode_sanitize_main.cpp), started as a child process."""
 import ctypes
 import os
-import re
-import shutil
 import subprocess
 import sys
 
@@ -17,50 +15,27 @@ import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import jpeg_decode_cases as cases  # noqa: E402
 
-CSRC = os.path.join(ROOT, "vsc22-submission_amd", "csrc")
-KERNEL = os.path.join(CSRC, "jpeg_decode.hip")
-P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
+P, I64 = ctypes.c_void_p, ctypes.c_int64
 GUARD = 13          # bytes of 0xFF on both sides of every buffer: odd, so that inputs and outputs start at odd addresses
 SMALL = cases.names(emulated=True)
 
 
 def guarded(nbytes, fill=0xFF):
-    buf = np.full(nbytes + 2 * GUARD, 0xFF, np.uint8)
-    buf[GUARD:GUARD + nbytes] = fill
-    return buf, buf[GUARD:GUARD + nbytes]
+    return hip_emu_build.guarded(nbytes, np.uint8, GUARD, fill)
 
 
 def guards_intact(buf):
-    return bool((buf[:GUARD] == 0xFF).all() and (buf[len(buf) - GUARD:] == 0xFF).all())
-
-
-def compiler():
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    return cxx
-
-
-def emulated_source():
-    src, n = re.subn(r'^#include "common.h"\n', '#include "jpeg_decode.h"\n', open(KERNEL).read(), flags=re.M)
-    assert n == 1, "jpeg_decode.hip no longer has the line the emulation replaces"
-    return src
+    return hip_emu_build.guards_intact(buf, GUARD)
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_jpeg_decode_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_jpeg_decode_destroy.argtypes = [P]
-        lib.vsc_jpeg_decode_destroy.restype = None
-        lib.vsc_jpeg_decode_scratch.argtypes = [P, I64, ctypes.POINTER(I64), ctypes.POINTER(I64)]
-        lib.vsc_jpeg_decode_u8.argtypes = [P, P, I64, P, I64, P, I32, P, I64, P]
-        for f in (lib.jd_emu_launches, lib.jd_emu_blocks, lib.jd_emu_allocs):
-            f.restype = ctypes.c_size_t
 
     def run(self, file_list, first_offset=1, gap=5, cap=0, fill=0x5A):
         """one call on a handle of its own -> (rc, status, [frame], chunks); frames packed from an odd offset with a gap between
@@ -90,33 +65,28 @@ class Emulated:
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    work = tmp_path_factory.mktemp("hip_emu_jpeg_decode")
-    (work / "jpeg_decode.cpp").write_text(emulated_source())
-    lib = str(work / "libjpeg_decode_emu.so")
-    subprocess.check_call([compiler(), "-std=c++20", "-O2", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", "-I", os.path.join(HERE, "hip_emu"), "-I", CSRC,
-                           "-o", lib, str(work / "jpeg_decode.cpp")])
-    return Emulated(ctypes.CDLL(lib))
+    return Emulated(hip_emu_build.build_shared(tmp_path_factory, "jpeg_decode", hip_emu_build.source("jpeg_decode")))
 
 
 @pytest.mark.parametrize("name", SMALL)
 def test_emulated_kernels_equal_contract(emulated, name):
     """the whole case in one call: two launches per call, none for the empty one"""
-    before = emulated.lib.jd_emu_launches()
+    before = emulated.lib.emu_launches()
     rc, status, frames, chunks = emulated.run(cases.files(name))
     assert rc == 0 and (status == 0).all(), (rc, status.tolist())
     want = cases.contract(name)
     assert len(frames) == len(want)
     for i, (got, ref) in enumerate(zip(frames, want)):
         assert got.shape == ref.shape and np.array_equal(got, ref), (name, i, int((got != ref).sum()), np.argwhere(got != ref)[:4].tolist())
-    assert emulated.lib.jd_emu_launches() - before == (2 if want else 0) and chunks == (1 if want else 0)
+    assert emulated.lib.emu_launches() - before == (2 if want else 0) and chunks == (1 if want else 0)
 
 
 def test_emulated_chunks(emulated):
     """five small frames under a scratch cap of 3500 bytes: (768 + 1728) + 2048 + (2304 + 1152) bytes of planes -> three chunks, six
     launches, the same bytes"""
-    before = emulated.lib.jd_emu_launches()
+    before = emulated.lib.emu_launches()
     rc, status, frames, chunks = emulated.run(cases.files("five_small"), cap=3500)
-    assert rc == 0 and (status == 0).all() and chunks == 3 and emulated.lib.jd_emu_launches() - before == 6
+    assert rc == 0 and (status == 0).all() and chunks == 3 and emulated.lib.emu_launches() - before == 6
     assert all(np.array_equal(a, b) for a, b in zip(frames, cases.contract("five_small")))
     rc, _, frames, chunks = emulated.run(cases.files("five_small"), cap=1)        # every frame exceeds the cap: a chunk each
     assert rc == 0 and chunks == 5 and all(np.array_equal(a, b) for a, b in zip(frames, cases.contract("five_small")))
@@ -160,15 +130,8 @@ def calls_file(path):
 
 
 def test_emulated_under_the_sanitizers_as_a_child_process(tmp_path):
-    work = tmp_path
-    (work / "jpeg_decode_emu.inc").write_text(emulated_source())
-    exe = str(work / "jd_san")
-    cxx = compiler()
-    static = ["-static-libasan", "-static-libubsan"] if os.path.basename(cxx).startswith("g++") else []      # the runtimes inside the program: no load order to get wrong
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", *static,
-                           "-Wno-unknown-pragmas", "-I", str(work), "-I", os.path.join(HERE, "hip_emu"), "-I", CSRC, "-I", ROOT,
-                           os.path.join(HERE, "hip_emu", "jpeg_decode_sanitize_main.cpp"), "-o", exe])
-    n = calls_file(str(work / "calls.bin"))
-    r = subprocess.run([exe, str(work / "calls.bin")], capture_output=True, text=True)
+    exe = hip_emu_build.build_sanitized(tmp_path, hip_emu_build.source("jpeg_decode"), "jpeg_decode_sanitize_main.cpp")
+    n = calls_file(str(tmp_path / "calls.bin"))
+    r = subprocess.run([exe, str(tmp_path / "calls.bin")], capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert f"ok ({n} calls" in r.stdout, r.stdout

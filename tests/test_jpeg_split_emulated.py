@@ -1,6 +1,6 @@
 """csrc/jpeg_split.hip without a GPU: csrc/jpeg_decode.hip and csrc/jpeg_split.hip are compiled as ONE host translation unit
-against tests/hip_emu/jpeg_split.h (tests/hip_emu/common.h and jpeg_decode.h unchanged: one OS thread per GPU thread, barriers for
-__syncthreads, device allocations as exactly sized host allocations filled with 0xFF) and vsc_jpeg_decode_split_u8 must equal the
+against tests/hip_emu/jpeg_decode.h by tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads, device
+allocations as exactly sized host allocations filled with 0xFF) and vsc_jpeg_decode_split_u8 must equal the
 executable contract (tests/jpeg_split_contract.py) on every case of tests/jpeg_split_cases.py: output bytes between 0xFF guard
 bands at odd addresses, status 0, and the four statistics of vsc_jpeg_decode_stats.
 
@@ -14,7 +14,6 @@ The same calls and the entry's refusals then run in a stand-alone program built 
 (tests/hip_emu/jpeg_split_sanitize_main.cpp), started as a child process."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -24,36 +23,28 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import jpeg_decode_cases as cases  # noqa: E402
 import jpeg_split_cases as sc  # noqa: E402
 import jpeg_split_contract as contract  # noqa: E402
-from test_jpeg_decode_emulated import CSRC, GUARD, I32, I64, P, compiler, guarded, guards_intact  # noqa: E402
 from vsc_hip import jpeg  # noqa: E402
 
 RESTART = 4
+P, I64 = ctypes.c_void_p, ctypes.c_int64
+GUARD = 13          # bytes of 0xFF on both sides of every buffer: odd, so that inputs and outputs start at odd addresses
 
 
-def emulated_source():
-    out = []
-    for name in ("jpeg_decode.hip", "jpeg_split.hip"):
-        src, n = re.subn(r'^#include "common.h"\n', '#include "jpeg_split.h"\n', open(os.path.join(CSRC, name)).read(), flags=re.M)
-        assert n == 1, f"{name} no longer has the line the emulation replaces"
-        out.append(src)
-    return "\n".join(out)
+def guarded(nbytes, fill=0xFF):
+    return hip_emu_build.guarded(nbytes, np.uint8, GUARD, fill)
+
+
+def guards_intact(buf):
+    return hip_emu_build.guards_intact(buf, GUARD)
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_jpeg_decode_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_jpeg_decode_destroy.argtypes = [P]
-        lib.vsc_jpeg_decode_destroy.restype = None
-        lib.vsc_jpeg_decode_scratch.argtypes = [P, I64, ctypes.POINTER(I64), ctypes.POINTER(I64)]
-        lib.vsc_jpeg_decode_u8.argtypes = [P, P, I64, P, I64, P, I32, P, I64, P]
-        lib.vsc_jpeg_decode_split.argtypes = [P, I32, I32, I32, I32]
-        lib.vsc_jpeg_decode_split_u8.argtypes = [P, P, I64, P, I64, P, I32, P, P, P, I64, P]
-        lib.vsc_jpeg_decode_stats.argtypes = [P, P]
-        lib.jd_emu_launches.restype = ctypes.c_size_t
 
     def run(self, file_list, mode=3, sub_bytes=sc.SUB_BYTES, rounds=2, item_bytes=1, cap=0, restarts=None, entry="split", repeat=1, fill=0x5A):
         """``repeat`` calls on one handle of its own -> (rc, status, [frame], chunks, stats) of the last; frames packed from an
@@ -96,12 +87,7 @@ class Emulated:
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    work = tmp_path_factory.mktemp("hip_emu_jpeg_split")
-    (work / "jpeg_split.cpp").write_text(emulated_source())
-    lib = str(work / "libjpeg_split_emu.so")
-    subprocess.check_call([compiler(), "-std=c++20", "-O2", "-fPIC", "-shared", "-pthread", "-Wno-unknown-pragmas", "-I", os.path.join(HERE, "hip_emu"), "-I", CSRC,
-                           "-o", lib, str(work / "jpeg_split.cpp")])
-    return Emulated(ctypes.CDLL(lib))
+    return Emulated(hip_emu_build.build_shared(tmp_path_factory, "jpeg_split", hip_emu_build.source("jpeg_split")))
 
 
 def nsub(data, sub_bytes=sc.SUB_BYTES):
@@ -125,11 +111,11 @@ def test_emulated_substreams_equal_contract(emulated, name):
     data = sc.substream()[name]
     rounds = nsub(data)
     want = contract.split(data, sc.SUB_BYTES, rounds)
-    before = emulated.lib.jd_emu_launches()
+    before = emulated.lib.emu_launches()
     rc, status, frames, _, stats = emulated.run([data], rounds=rounds)
     assert rc == 0 and status.tolist() == [0] and np.array_equal(frames[0], sc.reference(name))
     assert want.kind == "substreams" and stats == (0, 1, 0, rounds) == contract.stats([want]), (stats, contract.stats([want]))
-    assert emulated.lib.jd_emu_launches() - before == rounds + 1 + 1 + 3       # sync rounds, item table, then items, statuses, colour
+    assert emulated.lib.emu_launches() - before == rounds + 1 + 1 + 3       # sync rounds, item table, then items, statuses, colour
 
 
 def test_emulated_too_few_rounds_fall_back(emulated):
@@ -260,15 +246,8 @@ def calls_file(path):
 
 
 def test_emulated_under_the_sanitizers_as_a_child_process(tmp_path):
-    work = tmp_path
-    (work / "jpeg_split_emu.inc").write_text(emulated_source())
-    exe = str(work / "js_san")
-    cxx = compiler()
-    static = ["-static-libasan", "-static-libubsan"] if os.path.basename(cxx).startswith("g++") else []      # the runtimes inside the program: no load order to get wrong
-    subprocess.check_call([cxx, "-std=c++20", "-O1", "-g", "-pthread", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", *static,
-                           "-Wno-unknown-pragmas", "-I", str(work), "-I", os.path.join(HERE, "hip_emu"), "-I", CSRC, "-I", os.path.dirname(HERE),
-                           os.path.join(HERE, "hip_emu", "jpeg_split_sanitize_main.cpp"), "-o", exe])
-    n = calls_file(str(work / "calls.bin"))
-    r = subprocess.run([exe, str(work / "calls.bin")], capture_output=True, text=True)
+    exe = hip_emu_build.build_sanitized(tmp_path, hip_emu_build.source("jpeg_split"), "jpeg_split_sanitize_main.cpp")
+    n = calls_file(str(tmp_path / "calls.bin"))
+    r = subprocess.run([exe, str(tmp_path / "calls.bin")], capture_output=True, text=True)
     assert r.returncode == 0, (r.returncode, r.stdout[-2000:], r.stderr[-4000:])
     assert f"ok ({n} calls" in r.stdout, r.stdout

@@ -1,45 +1,25 @@
-"""csrc/match_maps.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one OS
-thread per GPU thread, barriers for __syncthreads and the wave intrinsics) and must equal the executable contract
-(tests/match_maps_contract.py) bit for bit.  This checks the kernels' logic -- the sorted top-ten in the lanes, the summation
+"""csrc/match_maps.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics) and must equal the executable
+contract (tests/match_maps_contract.py) bit for bit.  This checks the kernels' logic -- the sorted top-ten in the lanes, the summation
 order, the choice among the waves, the tile walk of both slices, the launcher's chunks and refusals; the GPU suite
 (tests/test_gpu_match_maps.py) checks the same on the device on every planted item."""
-import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import match_maps_cases as cases  # noqa: E402
 import match_maps_contract as C  # noqa: E402
-
-KERNEL = os.path.join(ROOT, "vsc22-submission_amd", "csrc", "match_maps.hip")
 
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu_mm")
-    src = open(KERNEL).read()
-    src, n = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)     # the build passes -ffp-contract=off
-    assert n == 1, "match_maps.hip no longer has the line the emulation replaces"
-    shutil.copy(os.path.join(HERE, "hip_emu", "common.h"), work / "common.h")
-    (work / "mm.cpp").write_text(src)
-    lib = str(work / "libmm_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-o", lib, str(work / "mm.cpp")])
-    fn = ctypes.CDLL(lib).vsc_match_maps_f32
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p,
-                   ctypes.c_void_p, ctypes.c_void_p]
-    return fn
+    return hip_emu_build.build_shared(tmp_path_factory, "match_maps", hip_emu_build.source("match_maps")).vsc_match_maps_f32
 
 
 def _run(fn, flat, table, resolution, with_transpose):

@@ -1,32 +1,21 @@
-"""csrc/match_segments.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (one OS
-thread per GPU thread, barriers for __syncthreads and the wave intrinsics) and must equal the executable contract
-(tests/seg_contract.py) on small fixture maps.  This checks the kernel's logic phase by phase -- the label sweeps, the size
+"""csrc/match_segments.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics) and must equal the executable
+contract (tests/seg_contract.py) on small fixture maps.  This checks the kernel's logic phase by phase -- the label sweeps, the size
 counters, the ranking, the point lookup, the MT19937 subset stream, the trial loop and the final fit; the GPU suite
 (tests/test_gpu_match_segments.py) checks the same on the device for every fixture entry."""
-import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import seg_cases  # noqa: E402
 import seg_contract  # noqa: E402
 
-KERNEL = os.path.join(ROOT, "vsc22-submission_amd", "csrc", "match_segments.hip")
-ENTRY = '''
-extern "C" int emu_match_segments(const float *maps, int64_t maps_len, const int64_t *items, int64_t n, const float *thr,
-                                  const double *ratio, int n_thr, int max_seg, int32_t *seg, double *score, int32_t *counts) {
-    return launch_match_segments(maps, maps_len, items, n, thr, ratio, n_thr, max_seg, seg, score, counts, nullptr);
-}
-'''
 # One small map per phase variant, so the run stays under a minute (every workgroup is 512 OS threads): a group below 200 points
 # (permutation head), groups above it (tracking selection), several large components, dx = 0 trials, degenerate shapes.
 CASES = ["clean_00_40x50", "thick_05_40x50", "edge_empty", "edge_1x1", "edge_4x4", "edge_specks_only", "edge_query_frame_rows_only",
@@ -35,23 +24,8 @@ CASES = ["clean_00_40x50", "thick_05_40x50", "edge_empty", "edge_1x1", "edge_4x4
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu")
-    src = open(KERNEL).read()
-    # the two lines that only a device compiler understands; the shim defines ms_smem and the build passes -ffp-contract=off
-    src, n1 = re.subn(r"^\s*extern __shared__ __align__\(16\) unsigned char ms_smem\[\];\n", "", src, flags=re.M)
-    src, n2 = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)
-    assert n1 == 1 and n2 == 1, "match_segments.hip no longer has the lines the emulation replaces"
-    shutil.copy(os.path.join(HERE, "hip_emu", "common.h"), work / "common.h")
-    (work / "ms.cpp").write_text(src + ENTRY)
-    lib = str(work / "libms_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-o", lib, str(work / "ms.cpp")])
-    fn = ctypes.CDLL(lib).emu_match_segments
-    fn.restype = ctypes.c_int
-    fn.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                   ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    return fn
+    lib = hip_emu_build.build_shared(tmp_path_factory, "match_segments", hip_emu_build.source("match_segments"))
+    return lib.vsc_match_segments_f32
 
 
 def _run(fn, m, slots=8):
@@ -61,7 +35,7 @@ def _run(fn, m, slots=8):
     flat = np.ascontiguousarray(m.reshape(-1)) if m.size else np.zeros(1, np.float32)
     seg, sc, cnt = np.zeros((3, slots, 4), np.int32), np.zeros((3, slots), np.float64), np.full(3, -1, np.int32)
     assert fn(flat.ctypes.data, m.size, items.ctypes.data, 1, thr.ctypes.data, ratio.ctypes.data, 3, slots, seg.ctypes.data,
-              sc.ctypes.data, cnt.ctypes.data) == 0
+              sc.ctypes.data, cnt.ctypes.data, None) == 0
     return seg, sc, cnt
 
 

@@ -1,40 +1,30 @@
-"""csrc/score_norm.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one OS
-thread per GPU thread, barriers for __syncthreads and the wave intrinsics) plus tests/hip_emu/score_norm.h (the launchers'
-prototypes and the forwarding C entry points) with -ffp-contract=off, and must equal the executable contract
+"""csrc/score_norm.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics), its own C entry points
+included, with -ffp-contract=off, and must equal the executable contract
 (tests/score_norm_contract.py) bit for bit: the staging of row tiles and which rows and columns are read, the order of the chains,
 the logical column index of the narrowed row, the lane sums and the butterfly, the three summation forms of the bias, the refusals.
 The GPU suite (tests/test_gpu_score_norm.py) checks the same on the device."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import score_norm_cases as cases  # noqa: E402
 import score_norm_contract as C  # noqa: E402
 
-KERNEL = os.path.join(ROOT, "vsc22-submission_amd", "csrc", "score_norm.hip")
-P, I32, I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-GUARD = 8       # NaN floats before and behind every output
+P = ctypes.c_void_p
+GUARD = 8       # floats of 0xFF bytes (NaN) before and behind every output, which is filled with them too
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_score_norm_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_score_norm_destroy.argtypes = [P]
-        lib.vsc_score_norm_destroy.restype = None
-        lib.vsc_column_var_f32.argtypes = [P, P, I64, I32, I64, P]
-        lib.vsc_score_norm_rows_f32.argtypes = [P, P, I64, I32, I64, I32, I32, I32, P, P, I64]
-        lib.vsc_score_norm_bias_f32.argtypes = [P, P, I64, I64, I32, ctypes.c_float, P, P]
         self.handle = P()
         assert lib.vsc_score_norm_create(None, ctypes.byref(self.handle)) == 0
 
@@ -43,12 +33,11 @@ class Emulated:
 
     @staticmethod
     def guarded(count):
-        buf = np.full(count + 2 * GUARD, np.nan, np.float32)
-        return buf, buf[GUARD:GUARD + count]
+        return hip_emu_build.guarded(count, np.float32, GUARD)
 
     @staticmethod
     def guards_intact(buf):
-        return bool(np.isnan(buf[:GUARD]).all() and np.isnan(buf[len(buf) - GUARD:]).all())
+        return hip_emu_build.guards_intact(buf, GUARD)
 
     def column_var(self, x, n, d, ld):
         buf, out = self.guarded(d)
@@ -75,19 +64,7 @@ class Emulated:
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu_sn")
-    src = open(KERNEL).read()
-    src, n = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)     # the build passes -ffp-contract=off
-    assert n == 1, "score_norm.hip no longer has the line the emulation replaces"
-    src, n = re.subn(r'^#include "common.h"\n', '#include "score_norm.h"\n', src, flags=re.M)
-    assert n == 1
-    (work / "sn.cpp").write_text(src)
-    lib = str(work / "libsn_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I", os.path.join(HERE, "hip_emu"),
-                           "-o", lib, str(work / "sn.cpp")])
-    emu = Emulated(ctypes.CDLL(lib))
+    emu = Emulated(hip_emu_build.build_shared(tmp_path_factory, "score_norm", hip_emu_build.source("score_norm")))
     yield emu
     emu.close()
 

@@ -1,37 +1,28 @@
-"""csrc/segment_metric.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one
-OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics) plus tests/hip_emu/segment_metric.h (the handle's
-allocations) and must equal the executable contract (tests/segment_metric_contract.py) bit for bit: the sorted inserts over chunks
-of 64, the fusing of components, the considered flags, the summation order, the scan's tiles and its walk over `ends`, the
-refusals.  The GPU suite (tests/test_gpu_segment_metric.py) checks the same on the device."""
+"""csrc/segment_metric.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics, the handle's allocations
+filled with 0xFF when fresh) and must equal the executable contract (tests/segment_metric_contract.py) bit for bit: the sorted
+inserts over chunks of 64, the fusing of components, the considered flags, the summation order, the scan's tiles and its walk over
+`ends`, the refusals.  The GPU suite (tests/test_gpu_segment_metric.py) checks the same on the device."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import segment_metric_cases as cases  # noqa: E402
 import segment_metric_contract as C  # noqa: E402
 
-KERNEL = os.path.join(ROOT, "vsc22-submission_amd", "csrc", "segment_metric.hip")
 P = ctypes.c_void_p
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_segment_metric_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_segment_metric_destroy.argtypes = [P]
-        lib.vsc_segment_metric_destroy.restype = None
-        lib.vsc_segment_metric_deltas_f64.argtypes = [P, P, P, P, ctypes.c_int64, P, P, ctypes.c_int64, ctypes.c_int64, P, P]
-        lib.vsc_segment_metric_scan_f64.argtypes = [P, P, ctypes.c_int64, ctypes.c_int32, P, ctypes.c_int64, P]
         self.handle = P()
         assert lib.vsc_segment_metric_create(None, ctypes.byref(self.handle)) == 0
 
@@ -56,19 +47,7 @@ class Emulated:
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu_sm")
-    src = open(KERNEL).read()
-    src, n = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)     # the build passes -ffp-contract=off
-    assert n == 1, "segment_metric.hip no longer has the line the emulation replaces"
-    src, n = re.subn(r'^#include "common.h"\n', '#include "segment_metric.h"\n', src, flags=re.M)
-    assert n == 1
-    (work / "sm.cpp").write_text(src)
-    lib = str(work / "libsm_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I", os.path.join(HERE, "hip_emu"),
-                           "-o", lib, str(work / "sm.cpp")])
-    emu = Emulated(ctypes.CDLL(lib))
+    emu = Emulated(hip_emu_build.build_shared(tmp_path_factory, "segment_metric", hip_emu_build.source("segment_metric")))
     yield emu
     emu.close()
 

@@ -1,52 +1,30 @@
-"""csrc/uap.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one OS thread
-per GPU thread, barriers for __syncthreads and the wave intrinsics) plus tests/hip_emu/uap.h (one scratch buffer per slot, filled
-with 0xFF when fresh) with -ffp-contract=off, and must equal the executable contract (tests/uap_contract.py) on uint64 views:
-the sort key, the stable ranking over tiles, the skipped digit passes, the duplicate counts, the join, the two scans, where the curve
-is written, the reversed group terms, the walk through numpy's summation tree, the refusals.  Every case up to 2 500 predictions;
+"""csrc/uap.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics, one scratch buffer per
+slot, filled with 0xFF when fresh) with -ffp-contract=off, and must equal the executable contract (tests/uap_contract.py) on uint64
+views: the sort key, the stable ranking over tiles, the skipped digit passes, the duplicate counts, the join, the two scans, where the
+curve is written, the reversed group terms, the walk through numpy's summation tree, the refusals.  Every case up to 2 500 predictions;
 the GPU suite (tests/test_gpu_uap.py) checks the same, and the larger cases, on the device."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import uap_cases as cases  # noqa: E402
 import uap_contract as C  # noqa: E402
+from hip_emu_build import guarded, guards_intact  # noqa: E402     (guards of 8 elements of 0xFF bytes; as floats NaN)
 
-KERNEL = os.path.join(ROOT, "vsc22-submission_amd", "csrc", "uap.hip")
-P, I32, I64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64
-GUARD = 8
-
-
-def guarded(count, dtype):
-    """(buffer, view of `count` elements) with GUARD elements of 0xFF bytes on both sides; float views of 0xFF are NaN"""
-    buf = np.full((count + 2 * GUARD) * np.dtype(dtype).itemsize, 0xFF, np.uint8).view(dtype)
-    return buf, buf[GUARD:GUARD + count]
-
-
-def guards_intact(buf):
-    raw = buf.view(np.uint8)
-    g = GUARD * buf.dtype.itemsize
-    return bool((raw[:g] == 0xFF).all() and (raw[len(raw) - g:] == 0xFF).all())
+P = ctypes.c_void_p
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_uap_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_uap_destroy.argtypes = [P]
-        lib.vsc_uap_destroy.restype = None
-        lib.vsc_uap_rank_f64.argtypes = [P, P, P, I64, P, I64, I32, P, P, P, P]
-        lib.vsc_uap_curve_f64.argtypes = [P, P, P, I64, I64, P, P, P]
-        lib.uap_emu_scratch_allocs.restype = ctypes.c_size_t
         self.handle = P()
         assert lib.vsc_uap_create(None, ctypes.byref(self.handle)) == 0
 
@@ -73,19 +51,7 @@ class Emulated:
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu_uap")
-    src = open(KERNEL).read()
-    src, n = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)     # the build passes -ffp-contract=off
-    assert n == 1, "uap.hip no longer has the line the emulation replaces"
-    src, n = re.subn(r'^#include "common.h"\n', '#include "uap.h"\n', src, flags=re.M)
-    assert n == 1
-    (work / "uap.cpp").write_text(src)
-    lib = str(work / "libuap_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I", os.path.join(HERE, "hip_emu"),
-                           "-o", lib, str(work / "uap.cpp")])
-    emu = Emulated(ctypes.CDLL(lib))
+    emu = Emulated(hip_emu_build.build_shared(tmp_path_factory, "uap", hip_emu_build.source("uap")))
     yield emu
     emu.close()
 
@@ -178,7 +144,7 @@ def test_emulated_scratch_is_reused_across_sizes(emulated):
     call's leftovers in every buffer and must not read them; the slots grow only when a call needs more"""
     order = ["n257_ties", "n9_distinct", "n2049_ties", "n128_distinct", "n1000_ties", "n1_distinct", "n2500_distinct", "n7_ties"]
     check_case(emulated, cases.get("n2500_ties"))
-    before = emulated.lib.uap_emu_scratch_allocs()
+    before = emulated.lib.emu_scratch_allocs()
     for name in order:
         check_case(emulated, cases.get(name))
-    assert emulated.lib.uap_emu_scratch_allocs() == before, "a call no larger than an earlier one grew the scratch"
+    assert emulated.lib.emu_scratch_allocs() == before, "a call no larger than an earlier one grew the scratch"

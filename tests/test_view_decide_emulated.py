@@ -1,51 +1,31 @@
-"""csrc/view_decide.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h (unchanged: one OS
-thread per GPU thread, barriers for __syncthreads and the wave intrinsics) plus tests/hip_emu/view_decide.h (the dynamic LDS as a
-static buffer) with -ffp-contract=off, and must equal the executable contract (tests/view_decide_contract.py) exactly: boxes, counts,
-status and the bits of the trace -- every case up to 330 pixels on a side (and the two thin maps around the 8192-element boundary),
+"""csrc/view_decide.hip without a GPU: the kernel source is compiled as host C++ against tests/hip_emu/common.h by
+tests/hip_emu_build.py (one OS thread per GPU thread, barriers for __syncthreads and the wave intrinsics, LDS filled with a pattern
+before every launch) with -ffp-contract=off, and must equal the executable contract (tests/view_decide_contract.py) exactly: boxes,
+counts, status and the bits of the trace -- every case up to 330 pixels on a side (and the two thin maps around the 8192-element boundary),
 single and batched at odd offsets, more items than one launch holds, outputs between 0xFF guard bands with the -1 tails intact, a
 NULL trace, the refusals."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 sys.path.insert(0, HERE)
 
+import hip_emu_build  # noqa: E402
 import view_decide_cases as cases  # noqa: E402
 import view_decide_contract as C  # noqa: E402
+from hip_emu_build import guarded, guards_intact  # noqa: E402     (8 elements of 0xFF bytes on both sides)
 
-KERNEL = os.path.join(ROOT, "vsc22-submission_amd", "csrc", "view_decide.hip")
-P, I64, I32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32
-GUARD = 8
+P = ctypes.c_void_p
 SMALL = cases.names(large=False)
-
-
-def guarded(count, dtype):
-    """(buffer, view of `count` elements) with GUARD elements of 0xFF bytes on both sides"""
-    buf = np.full((count + 2 * GUARD) * np.dtype(dtype).itemsize, 0xFF, np.uint8).view(dtype)
-    return buf, buf[GUARD:GUARD + count]
-
-
-def guards_intact(buf):
-    raw = buf.view(np.uint8)
-    g = GUARD * buf.dtype.itemsize
-    return bool((raw[:g] == 0xFF).all() and (raw[len(raw) - g:] == 0xFF).all())
 
 
 class Emulated:
     def __init__(self, lib):
         self.lib = lib
-        lib.vsc_view_decide_create.argtypes = [P, ctypes.POINTER(P)]
-        lib.vsc_view_decide_destroy.argtypes = [P]
-        lib.vsc_view_decide_destroy.restype = None
-        lib.vsc_view_decide_f64.argtypes = [P, P, I64, P, I64, P, I64, I32, P, P, P, P]
         self.handle = P()
         assert lib.vsc_view_decide_create(None, ctypes.byref(self.handle)) == 0
 
@@ -70,21 +50,7 @@ class Emulated:
 
 @pytest.fixture(scope="module")
 def emulated(tmp_path_factory):
-    cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
-    assert shutil.which(cxx) or os.path.exists(cxx), "no host C++ compiler (g++ / clang++) for the emulated kernel"
-    work = tmp_path_factory.mktemp("hip_emu_view_decide")
-    src = open(KERNEL).read()
-    src, n = re.subn(r"^#pragma clang fp contract\(off\)\n", "", src, flags=re.M)     # the build passes -ffp-contract=off
-    assert n == 1, "view_decide.hip no longer has the line the emulation replaces"
-    src, n = re.subn(r'^#include "common.h"\n', '#include "view_decide.h"\n', src, flags=re.M)
-    assert n == 1
-    src, n = re.subn(r"^ *extern __shared__ __align__\(16\) unsigned char vd_smem\[\];\n", "", src, flags=re.M)   # view_decide.h's buffer
-    assert n == 1
-    (work / "view_decide.cpp").write_text(src)
-    lib = str(work / "libview_decide_emu.so")
-    subprocess.check_call([cxx, "-std=c++20", "-O2", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-I", os.path.join(HERE, "hip_emu"),
-                           "-o", lib, str(work / "view_decide.cpp")])
-    emu = Emulated(ctypes.CDLL(lib))
+    emu = Emulated(hip_emu_build.build_shared(tmp_path_factory, "view_decide", hip_emu_build.source("view_decide")))
     yield emu
     emu.close()
 

@@ -160,36 +160,6 @@ extern "C" int vsc_l2_normalize_f32(float *x, int64_t n, int32_t d, void *stream
     return launch_l2_normalize(x, n, d, (hipStream_t)stream);
 }
 
-// score normalisation (score_norm.hip): the handle is the stream every call of it enqueues on
-struct vsc_score_norm {
-    hipStream_t stream = nullptr;
-};
-
-extern "C" int vsc_score_norm_create(void *stream, vsc_score_norm **out) {
-    VSC_REQUIRE(out, "score_norm_create: null pointer");
-    *out = new vsc_score_norm{(hipStream_t)stream};
-    return VSC_OK;
-}
-
-extern "C" void vsc_score_norm_destroy(vsc_score_norm *h) { delete h; }
-
-extern "C" int vsc_column_var_f32(vsc_score_norm *h, const float *x_dev, int64_t n, int32_t d, int64_t ld, float *var_dev) {
-    VSC_REQUIRE(h, "column_var: null handle");
-    return launch_column_var(x_dev, n, d, ld, var_dev, h->stream);
-}
-
-extern "C" int vsc_score_norm_rows_f32(vsc_score_norm *h, const float *x_dev, int64_t n, int32_t d, int64_t ldx, int32_t drop, int32_t normalize,
-                                       int32_t append, const float *last_dev, float *out_dev, int64_t ldo) {
-    VSC_REQUIRE(h, "score_norm_rows: null handle");
-    return launch_score_norm_rows(x_dev, n, d, ldx, drop, normalize, append, last_dev, out_dev, ldo, h->stream);
-}
-
-extern "C" int vsc_score_norm_bias_f32(vsc_score_norm *h, const float *topk_dev, int64_t nq, int64_t ldk, int32_t nk, float neg_beta,
-                                       const uint8_t *gate_dev, float *bias_dev) {
-    VSC_REQUIRE(h, "score_norm_bias: null handle");
-    return launch_score_norm_bias(topk_dev, nq, ldk, nk, neg_beta, gate_dev, bias_dev, h->stream);
-}
-
 extern "C" int vsc_window_attention_bf16(const uint16_t *qkv, uint16_t *out, const float *bias, const float *scale,
                                          int32_t frames, int32_t res, int32_t window, int32_t shift,
                                          int32_t heads, void *stream) {
@@ -276,13 +246,6 @@ extern "C" int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const i
                                 int32_t *boxes_dev, int32_t *counts_dev, float *maxsim_dev, void *stream) {
     return launch_tn_align(sims_dev, sims_len, pairs_host, n_pairs, bias, max_step, top_k, max_path, min_sim, min_length, max_iou,
                            boxes_dev, counts_dev, maxsim_dev, (hipStream_t)stream);
-}
-
-extern "C" int vsc_match_segments_f32(const float *maps_dev, int64_t maps_len, const int64_t *items_host, int64_t n_items,
-                                      const float *thresholds, const double *std_ratios, int32_t n_thr, int32_t max_segments,
-                                      int32_t *out_segments_dev, double *out_scores_dev, int32_t *out_counts_dev, void *stream) {
-    return launch_match_segments(maps_dev, maps_len, items_host, n_items, thresholds, std_ratios, n_thr, max_segments, out_segments_dev,
-                                 out_scores_dev, out_counts_dev, (hipStream_t)stream);
 }
 
 extern "C" int vsc_frame_var_u8(const uint8_t *frames_dev, int64_t n, int32_t h, int32_t w, double *out_dev, void *stream) {

@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include "../../include/vsc_hip.h"
+#include "scratch_slots.h"
 
 typedef __attribute__((ext_vector_type(8))) short bf16x8_t;   // 8 bf16 = 4 VGPRs (MFMA A/B operand)
 typedef __attribute__((ext_vector_type(4))) short bf16x4_t;   // 8 bytes
@@ -310,37 +311,8 @@ int launch_patchify_u8(const uint8_t *frames, uint16_t *patches, int64_t n, int 
 int launch_f32_to_bf16(const float *src, uint16_t *dst, int64_t rows, int cols, int cols_pad,
                        hipStream_t stream);
 // grow-only device scratch of the search path (knn.hip), one set of slots per device; callers on one device are ordered
-// (one stream, or streams synchronised around the call)
+// (one stream, or streams synchronised around the call); the slots: scratch_slots.h
 int search_scratch_get(int slot, size_t bytes, void **out);
-// One owner per slot; two buffers that are live in one call never share one.  The numbers are part of nothing outside the library,
-// but tests/hip_emu/common.h mirrors SCRATCH_MS_TABLE.
-enum SearchScratchSlot {
-    // knn.hip, exact fp32 sweeps
-    SCRATCH_KNN_Q_F32 = 0, SCRATCH_KNN_R_F32 = 1,   // packed fp32 queries / references (every exact sweep, pair similarity)
-    SCRATCH_KNN_LISTS = 2,                          // exact top-k: candidate lists per workgroup
-    SCRATCH_KNN_PART = 3,                           // top-k, exact and pre-filter: sorted keys per (query, split)
-    SCRATCH_RANGE_COUNTS = 4,                       // range search, exact and pre-filter: hits per (query, split)
-    SCRATCH_PAIR_TILES = 5,                         // pair similarity: tile table
-    SCRATCH_PAIRMAX_TABLE = 6, SCRATCH_PAIRMAX_COUNTS = 7,   // video-pair maxima: [q videos][r videos] table, entries per row
-    // knn.hip, bf16 pre-filter (8-11: unused)
-    SCRATCH_PF_QB = 12, SCRATCH_PF_RB = 13,         // packed bf16 queries / references
-    SCRATCH_PF_QSTATS = 14, SCRATCH_PF_FLAGS = 15,  // per-query norms; max |r| bits + fallback flags + debug counters
-    SCRATCH_PF_LISTS = 16, SCRATCH_PF_CAND = 17, SCRATCH_PF_NCAND = 18,   // sweep lists per workgroup; survivors per (query, split), their number
-    SCRATCH_TN_TABLE = 19, SCRATCH_TN_NODES = 20,         // tn_align.hip
-    SCRATCH_VIEW_CANNY = 21, SCRATCH_VIEW_RESIZE = 22,    // view_prep.hip; the resize slot also serves frame_inputs.hip's two-pass path
-    SCRATCH_MS_TABLE = 23,                                // match_segments.hip
-    // global_topk.hip
-    SCRATCH_GTK_STATE = 24, SCRATCH_GTK_BLOCKS = 25,      // global top-k: select state; (above, equal) counts per tile
-    SCRATCH_GTK_KEYS = 26, SCRATCH_GTK_PAY = 27, SCRATCH_GTK_HIST = 28,   // survivors' keys / positions (two buffers each); [digit][tile] counters
-    SCRATCH_PFH_KEYS = 29, SCRATCH_PFH_POS = 30,          // pair first hits: table keys, least position per key
-    SCRATCH_PFH_FLAGS = 31, SCRATCH_PFH_BLOCKS = 32,      // first-hit flag per entry; flags per tile
-    // uap.hip; the two entries run one after the other and use the slots in turn
-    SCRATCH_UAP_STATE = 33,                               // rank: the four status counters
-    SCRATCH_UAP_KEYS = 34, SCRATCH_UAP_PAY = 35,          // rank: the sorts' two key buffers; two position buffers + the score keys.  curve: both term lists; (tps, last row) per tie group
-    SCRATCH_UAP_HIST = 36, SCRATCH_UAP_TREE = 37,         // rank: [digit][tile] counters.  curve: counts per tile; the pairwise trees' slots
-    SCRATCH_FRAME_FILTER_BITS = 38,                       // frame_filter.hip: adjacency bit matrices too large for LDS
-    SCRATCH_SLOTS
-};
 // temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h
 int launch_tn_align(const float *sims, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias, int max_step,
                     int top_k, int max_path, double min_sim, int min_length, double max_iou, int32_t *boxes, int32_t *counts,

@@ -508,3 +508,10 @@ int launch_match_segments(const float *maps_dev, int64_t maps_len, const int64_t
     VSC_CHECK_LAUNCH();
     return VSC_OK;
 }
+
+extern "C" int vsc_match_segments_f32(const float *maps_dev, int64_t maps_len, const int64_t *items_host, int64_t n_items,
+                                      const float *thresholds, const double *std_ratios, int32_t n_thr, int32_t max_segments,
+                                      int32_t *out_segments_dev, double *out_scores_dev, int32_t *out_counts_dev, void *stream) {
+    return launch_match_segments(maps_dev, maps_len, items_host, n_items, thresholds, std_ratios, n_thr, max_segments, out_segments_dev,
+                                 out_scores_dev, out_counts_dev, (hipStream_t)stream);
+}

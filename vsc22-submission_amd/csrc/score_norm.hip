@@ -229,3 +229,33 @@ int launch_score_norm_bias(const float *topk, int64_t nq, int64_t ldk, int nk, f
     VSC_CHECK_LAUNCH();
     return VSC_OK;
 }
+
+// the handle is the stream every call of it enqueues on
+struct vsc_score_norm {
+    hipStream_t stream = nullptr;
+};
+
+extern "C" int vsc_score_norm_create(void *stream, vsc_score_norm **out) {
+    VSC_REQUIRE(out, "score_norm_create: null pointer");
+    *out = new vsc_score_norm{(hipStream_t)stream};
+    return VSC_OK;
+}
+
+extern "C" void vsc_score_norm_destroy(vsc_score_norm *h) { delete h; }
+
+extern "C" int vsc_column_var_f32(vsc_score_norm *h, const float *x_dev, int64_t n, int32_t d, int64_t ld, float *var_dev) {
+    VSC_REQUIRE(h, "column_var: null handle");
+    return launch_column_var(x_dev, n, d, ld, var_dev, h->stream);
+}
+
+extern "C" int vsc_score_norm_rows_f32(vsc_score_norm *h, const float *x_dev, int64_t n, int32_t d, int64_t ldx, int32_t drop, int32_t normalize,
+                                       int32_t append, const float *last_dev, float *out_dev, int64_t ldo) {
+    VSC_REQUIRE(h, "score_norm_rows: null handle");
+    return launch_score_norm_rows(x_dev, n, d, ldx, drop, normalize, append, last_dev, out_dev, ldo, h->stream);
+}
+
+extern "C" int vsc_score_norm_bias_f32(vsc_score_norm *h, const float *topk_dev, int64_t nq, int64_t ldk, int32_t nk, float neg_beta,
+                                       const uint8_t *gate_dev, float *bias_dev) {
+    VSC_REQUIRE(h, "score_norm_bias: null handle");
+    return launch_score_norm_bias(topk_dev, nq, ldk, nk, neg_beta, gate_dev, bias_dev, h->stream);
+}
