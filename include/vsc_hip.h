@@ -822,6 +822,59 @@ int vsc_jpeg_decode_split_u8(vsc_jpeg_decode *h, const uint8_t *bytes_dev, int64
                              uint8_t *out_dev, int64_t out_len, int32_t *status_dev);
 int vsc_jpeg_decode_stats(vsc_jpeg_decode *h, int64_t *out);
 
+/* JPEG files of SEVERAL SCANS, and single-scan frames beside them, in one call (csrc/jpeg_scans.hip; executable contract:
+ * tests/jpeg_scans_contract.py): progressive files (SOF2), sequential files of more than one scan, Huffman table ids 0 .. 3.  The
+ * pixels are what Pillow gives for the file, bit for bit: the scans of a COMPLETE file accumulate the quantised coefficients its
+ * sequential twin holds, and from the coefficients on the decode path is vsc_jpeg_decode_u8's (libjpeg smooths blocks only while
+ * some coefficient's precision is unknown; files that end so are refused).  A frame whose scan list is one sequential scan of all
+ * its components gets vsc_jpeg_decode_u8's bytes and status.  Operands as in vsc_jpeg_decode_u8 except:
+ *   frames_host    int64 [n_frames][VSC_JPEG_FRAME_ROW], a row = {0, 0, height, width, sampling class, 0, the table set that holds
+ *                  the frame's quantisation tables, output byte offset, component word (byte c = quantisation table of component
+ *                  c), 0};
+ *   scans_host     int64 [scan_ptr_host[n_frames]][VSC_JPEG_SCAN_ROW] (HOST memory), a row = {segment offset in bytes_dev, segment
+ *                  length (from behind the SOS header to the next marker that is neither RSTn nor a stuffed zero), component mask
+ *                  (bit c = component c of the frame is in the scan; the scan header lists them in frame order), Ss, Se, Ah, Al,
+ *                  the restart interval in force at the scan (0: none), the table set in force at the scan, Huffman word (byte c =
+ *                  DC table | AC table << 2 of component c; 0 for a component outside the scan)};
+ *   scan_ptr_host  int64 [n_frames + 1] (HOST memory), CSR: frame i's scans are rows ptr[i] .. ptr[i + 1], in file order, at least one;
+ *   tables_host    uint8 [n_table_sets][VSC_JPEG_SCAN_TABLE_SET_BYTES], a set = uint16 quant[4][64] as above, uint8 bits[8][16] and
+ *                  uint8 vals[8][256] of the tables DC0 .. DC3, AC0 .. AC3, one byte of quantisation tables present, one whose bit
+ *                  (4 * class + id) says that Huffman table is, six zero bytes.  A DHT between two scans gives the later scan another
+ *                  set; quantisation tables are taken from the frame row's set alone (a DQT behind the first scan is refused by
+ *                  the parser).
+ * The points that are easy to get wrong, all part of the contract:
+ *   - a scan is sequential (Ss 0, Se 63, Ah = Al = 0), DC (Ss = Se = 0) or AC (Ss > 0, one component); DC first: predictor += difference,
+ *     coefficient = predictor << Al; DC refine: ONE BIT per block, no Huffman code, ORed in at 1 << Al;
+ *   - AC first: EOBn (run r < 15, size 0) sets EOBRUN = (1 << r) + r more bits and ends this block and EOBRUN - 1 more; values << Al;
+ *   - AC refine: size is 0 or 1; for size 1 the SIGN bit comes before the correction bits; the run r counts ZERO-history
+ *     coefficients only, every non-zero one that is passed takes one correction bit (1: add 1 << Al away from zero), and the
+ *     new +-(1 << Al) lands on the (r + 1)-th zero one; ZRL passes 16 zero ones; the blocks of an EOBRUN, the rest of the block
+ *     that starts it included, still take a correction bit per non-zero coefficient of the band;
+ *   - a scan of ONE component walks that component's own blocks, ceil(component width / 8) x ceil(component height / 8) row-major
+ *     (13 x 17 in 4:2:0: chroma 1 x 2 blocks, not the 2 x 2 of the MCU grid); a scan of several walks the frame's MCUs;
+ *   - the restart interval counts those units; a restart byte-aligns, wants RSTn in sequence, zeroes the DC predictors AND EOBRUN;
+ *   - coefficients wrap to 16 bits (libjpeg's JCOEF).
+ * The scan script of every frame is checked on the host as libjpeg checks it (jdphuff start_pass) before anything is launched:
+ * Ss <= Se <= 63, Al and Ah <= 13, a scan with Ss = 0 has Se = 0 or is sequential, an AC scan has one component and follows the
+ * component's DC first scan, Ah is 0 for coefficients not yet coded and otherwise their last Al with Al = Ah - 1, and the scans
+ * together bring every coefficient of every component to Al = 0 exactly once.  Anything else, and every fault vsc_jpeg_decode_u8
+ * refuses, is VSC_ERR_INVALID with nothing written.
+ * Three launches per chunk of frames: one wave per frame zeroes the frame's int16 coefficient planes (64 per block, MCU-padded,
+ * in the handle's scratch) and decodes its scans into them in file order; eight lanes per block dequantise and run jpeg_idct_islow
+ * over all blocks of the chunk; the colour launch is vsc_jpeg_decode_u8's.  Scratch per frame: 3 bytes per sample of its padded
+ * planes (1 for the pixel planes, 2 for the coefficients), chunked under the cap of vsc_jpeg_decode_scratch as there.
+ * Status: VSC_JPEG_STATUS_DATA / CODE (also a DC size above 16, an AC-refine size above 1) / RUN (also a run past the end of the
+ * band or past the last zero coefficient, and an EOBRUN longer than the blocks left in its restart interval or scan -- libjpeg
+ * drops the excess silently; here the file is damaged) / RESTART, and VSC_JPEG_STATUS_SCRIPT for a scan the host check should
+ * have excluded.  The frame stops at its first fault; no byte outside a scan's segment is read, nothing outside the frame's own
+ * planes and output is written, no other frame is disturbed.  No host synchronisation. */
+#define VSC_JPEG_SCAN_ROW 10
+#define VSC_JPEG_SCAN_TABLE_SET_BYTES 2696
+#define VSC_JPEG_STATUS_SCRIPT 5   /* a scan that fits no sequential or progressive script */
+int vsc_jpeg_decode_scans_u8(vsc_jpeg_decode *h, const uint8_t *bytes_dev, int64_t bytes_len, const int64_t *frames_host, int64_t n_frames,
+                             const int64_t *scans_host, const int64_t *scan_ptr_host, const uint8_t *tables_host, int32_t n_table_sets,
+                             uint8_t *out_dev, int64_t out_len, int32_t *status_dev);
+
 /* ------------------------------------------------------------------------ *
  * Building blocks, exported so the parity tests can check each kernel alone.
  * bf16 tensors are raw uint16 bit patterns.

@@ -35,7 +35,7 @@ from zipfile import ZipFile
 import numpy as np
 import torch
 
-from src.dataset import CLIP_MEAN, CLIP_STD, DECODE_SPLITS, DECODES, RESIZES, bytes_video, check_decode, check_decode_split, check_resize, clip_transform_u8, decode_rgb, vit_transform_u8
+from src.dataset import CLIP_MEAN, CLIP_STD, DECODE_SCANS, DECODE_SPLITS, DECODES, RESIZES, bytes_video, check_decode, check_decode_scans, check_decode_split, check_resize, clip_transform_u8, decode_rgb, vit_transform_u8
 from src.matching import calclualte_low_var_dim
 from src.model_zoo import DEFAULT_PRECISION, load_encoder, parse_model_spec
 from src.image_preprocess import HipViews, VIEW_DECISIONS
@@ -60,12 +60,16 @@ class QueryVideos(torch.utils.data.Dataset):
     ``resize="hip"``: the same raw frames and nothing else -- run_query_videos(resize="hip") makes every input, the CLIP frames
     included, on the GPU; a video whose frames differ in size is again resized here.
     ``decode="hip"`` (with ``resize="hip"``): the zip members are only read and their headers parsed -- the item carries a
-    src.dataset.BytesVideo under ``RAW_KEY``; a video with a frame the parser refuses is decoded here as a whole."""
+    src.dataset.BytesVideo under ``RAW_KEY``; a video with a frame the parser refuses is decoded here as a whole.
+    ``decode_scans="hip"`` (with ``decode="hip"``): the parser also takes files of several scans (vsc_hip.jpeg.parse_scans).
+    ``host_decoded`` counts the videos this object decoded with Pillow."""
 
-    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False, preprocess="none", resize="host", decode="host"):
+    def __init__(self, video_ids, zip_prefix, sizes, with_clip=False, preprocess="none", resize="host", decode="host", decode_scans="host"):
         assert preprocess in ("none", "hip"), preprocess
         self.zip_prefix, self.preprocess, self.resize = zip_prefix, preprocess, check_resize(resize)
         self.decode = check_decode(decode, self.resize)
+        self.decode_scans = check_decode_scans(decode_scans, self.decode)
+        self.host_decoded = 0
         self.video_ids = [v for v in video_ids if os.path.exists(self._path(v))]
         self.transforms = {s: vit_transform_u8(s, s) for s in sizes}
         if with_clip:
@@ -82,10 +86,11 @@ class QueryVideos(torch.utils.data.Dataset):
         vid = self.video_ids[i]
         with ZipFile(self._path(vid), "r") as z:
             files = [z.read(n) for n in sorted(z.namelist())]
-        video = bytes_video(files) if self.decode == "hip" else None
+        video = bytes_video(files, scans=self.decode_scans) if self.decode == "hip" else None
         if video is not None:
             n = video.shape[0]
             return vid, {RAW_KEY: video}, np.stack([np.arange(n, dtype=np.float32), np.arange(n, dtype=np.float32) + 1.0], axis=1)
+        self.host_decoded += 1
         images = [Image.open(io.BytesIO(f)).convert("RGB") for f in files]
         # [start, end] seconds per frame at 1 fps, the layout the reference's FFmpeg reader yields (infer/src/dataset.py:97-102):
         # a video rejected by the score gate gets a [1, 2] placeholder, so every video's timestamps must be 2-D for
@@ -100,8 +105,8 @@ class QueryVideos(torch.utils.data.Dataset):
         return vid, {s: torch.stack([t(im) for im in images]) for s, t in self.transforms.items()}, stamps
 
 
-def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0, preprocess="none", resize="host", decode="host"):
-    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip, preprocess, resize, decode)
+def zip_videos(video_ids, zip_prefix, sizes, with_clip=False, workers=0, preprocess="none", resize="host", decode="host", decode_scans="host"):
+    data = QueryVideos(video_ids, zip_prefix, sizes, with_clip, preprocess, resize, decode, decode_scans)
     kw = {"prefetch_factor": 4} if workers > 0 else {}
     return torch.utils.data.DataLoader(data, batch_size=1, shuffle=False, num_workers=workers, collate_fn=lambda b: b[0], **kw)
 
@@ -123,6 +128,7 @@ def main(args):
     resize = resize_of(args)
     decode = check_decode(getattr(args, "decode", "host"), resize)
     decode_split = check_decode_split(getattr(args, "decode_split", "none"), decode)
+    decode_scans = check_decode_scans(getattr(args, "decode_scans", "host"), decode)
     torch.cuda.set_device(0)
     device = torch.device("cuda", 0)
     specs = [parse_model_spec(s) for s in args.models]
@@ -139,11 +145,11 @@ def main(args):
         from src.model_zoo import _state_dict      # a plain / training checkpoint or the TorchScript archive the reference ships (vsm.torchscript.pt)
         scorer = VideoScorer(clip, VideoScoreHead("vsm_roberta_base", from_reference_state(_state_dict(args.vsm_checkpoint))), device)
     videos = zip_videos(vids, args.zip_prefix, sorted({size for _, size in encoders}), with_clip=scorer is not None,
-                        workers=args.workers, preprocess=args.preprocess, resize=resize, decode=decode)
+                        workers=args.workers, preprocess=args.preprocess, resize=resize, decode=decode, decode_scans=decode_scans)
     finals, per_model = run_query_videos(videos, encoders, pca.transform, scores, device, score_threshold=args.score_threshold,
                                          scorer=scorer, views=HipViews(device, getattr(args, "view_decisions", "host")) if args.preprocess == "hip" else None,
                                          frame_filter=getattr(args, "frame_filter", "host"),   # (a hand-built namespace from before the option)
-                                         resize=resize, decode=decode, decode_split=decode_split)
+                                         resize=resize, decode=decode, decode_split=decode_split, decode_scans=decode_scans)
     for i, (_, _, path) in enumerate(specs):
         key = os.path.split(path)[-1].split(".")[0]
         os.makedirs(os.path.join(args.output_dir, key), exist_ok=True)
@@ -198,6 +204,10 @@ def build_parser():
                     help="with --decode hip (needed, and refused without it): decode in parallel inside a frame -- at its restart markers "
                          "(markers), as self-synchronising sub-streams of a frame without them (substreams) or both (all); the same "
                          "files.  Measured faster than one wave per frame at every call size from 40 to 1 024 frames, most at the 40 frames of one video (DESIGN 4.19)")
+    ap.add_argument("--decode_scans", default="host", choices=DECODE_SCANS,
+                    help="with --decode hip (needed, and refused without it): jpgs of several scans -- progressive, one scan per component, "
+                         "Huffman table ids 2 and 3 -- are decoded on the device too (hip) instead of sending their whole video back to "
+                         "Pillow in a loader worker (host); the same files.  With --decode_split such frames are one wave each")
     return ap
 
 

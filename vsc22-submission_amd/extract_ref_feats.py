@@ -22,7 +22,7 @@ import os
 import numpy as np
 import torch
 
-from src.dataset import DECODE_SPLITS, DECODES, RESIZES, ZipFrames, check_decode, check_decode_split, check_resize, collate_fn, raw_collate, vit_transform_u8
+from src.dataset import DECODE_SCANS, DECODE_SPLITS, DECODES, RESIZES, ZipFrames, check_decode, check_decode_scans, check_decode_split, check_resize, collate_fn, raw_collate, vit_transform_u8
 from src.extractor import extract_vsc_feat, extract_vsc_feat_raw
 from vsc.storage import load_features, store_features
 from src.model_zoo import DEFAULT_PRECISION, WEIGHT_FORMATS, load_encoder
@@ -39,6 +39,7 @@ def main(args):
     resize = resize_of(args)
     decode = check_decode(getattr(args, "decode", "host"), resize)
     decode_split = check_decode_split(getattr(args, "decode_split", "none"), decode)
+    decode_scans = check_decode_scans(getattr(args, "decode_scans", "host"), decode)
     distributed = "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) > 1
     local_rank = int(os.environ.get("LOCAL_RANK", 0))
     torch.cuda.set_device(local_rank)
@@ -51,11 +52,11 @@ def main(args):
     with open(args.input_file, encoding="utf-8") as f:
         vids = [x.strip() for x in f if x.strip()]
     lo, hi = vdist.shard_bounds(len(vids), rank, world_size)
-    data = ZipFrames(vids[lo:hi], args.zip_prefix, vit_transform_u8(image_size, image_size), raw="bytes" if decode == "hip" else resize == "hip")   # uint8 to the GPU; normalised in patchify
+    data = ZipFrames(vids[lo:hi], args.zip_prefix, vit_transform_u8(image_size, image_size), raw="bytes" if decode == "hip" else resize == "hip", decode_scans=decode_scans)   # uint8 to the GPU; normalised in patchify
     loader = torch.utils.data.DataLoader(data, batch_size=args.batch_size, num_workers=getattr(args, "workers", 4), collate_fn=raw_collate if resize == "hip" else collate_fn)
     if resize == "hip":
         from src.image_preprocess import HipDecode, HipResize
-        ids, feats, stamps = extract_vsc_feat_raw(model, loader, device, image_size, HipResize(device), decoder=HipDecode(device, decode_split) if decode == "hip" else None)
+        ids, feats, stamps = extract_vsc_feat_raw(model, loader, device, image_size, HipResize(device), decoder=HipDecode(device, decode_split, decode_scans) if decode == "hip" else None)
     else:
         ids, feats, stamps = extract_vsc_feat(model, loader, device)
     np.savez(f"{args.save_file}_{rank}.npz", video_ids=ids, features=feats, timestamps=stamps)
@@ -98,6 +99,10 @@ def build_parser():
                     help="with --decode hip (needed, and refused without it): decode in parallel inside a frame -- at its restart markers "
                          "(markers), as self-synchronising sub-streams of a frame without them (substreams) or both (all); the same "
                          "file.  Measured faster than one wave per frame at every call size from 40 to 1 024 frames, most at the 40 frames of one video (DESIGN 4.19)")
+    ap.add_argument("--decode_scans", default="host", choices=DECODE_SCANS,
+                    help="with --decode hip (needed, and refused without it): jpgs of several scans -- progressive, one scan per component, "
+                         "Huffman table ids 2 and 3 -- are decoded on the device too (hip) instead of sending their whole video back to "
+                         "Pillow in a loader worker (host); the same file.  With --decode_split such frames are one wave each")
     return ap
 
 

@@ -23,5 +23,5 @@ for split in ${SPLITS:-train val test}; do
     --pca_model "$PCA_MODEL" --zip_prefix "$ZIPS" --input_file "$META/$split/${split}_query_ids.txt" --norm_refs "$NORM" \
     --clip_checkpoint "$CKPT/clip.torchscript.pt" --vsm_checkpoint "$CKPT/vsm.torchscript.pt" --output_dir "$OUT" \
     --preprocess "${PREPROCESS:-none}" --view_decisions "${VIEW_DECISIONS:-host}" --score_norm "${SCORE_NORM:-host}" \
-    --frame_filter "${FRAME_FILTER:-host}" --resize "${RESIZE:-host}" --decode "${DECODE:-host}" --decode_split "${DECODE_SPLIT:-none}"
+    --frame_filter "${FRAME_FILTER:-host}" --resize "${RESIZE:-host}" --decode "${DECODE:-host}" --decode_split "${DECODE_SPLIT:-none}" --decode_scans "${DECODE_SCANS:-host}"
 done

@@ -3,6 +3,7 @@
 # every backbone over the train and test reference videos, then concat + PCA + score normalisation.
 # RESIZE=hip resizes the decoded frames to the encoders' inputs on the GPU instead of with Pillow in the loader workers (the same files).
 # DECODE_SPLIT=markers|substreams|all (with DECODE=hip) decodes in parallel inside a frame.
+# DECODE_SCANS=hip (with DECODE=hip) decodes progressive and other multi-scan jpgs on the GPU too.
 # DECODE=hip (with RESIZE=hip) decodes the jpgs on the GPU too: the workers hand the compressed files on (the same files).
 #   CKPT=../checkpoints ZIPS=../data/jpg_zips META=../data/meta bash infer_ref.sh
 set -e
@@ -20,7 +21,7 @@ for m in "${MODELS[@]}"; do
     python -m torch.distributed.run --nnodes=1 --nproc-per-node "$GPUS" --master-addr 127.0.0.1 extract_ref_feats.py \
       --zip_prefix "$ZIPS" --input_file "$META/$split/${split}_ref_vids.txt" --save_file "$OUT/$name/${split}_refs" \
       --checkpoint_path "$CKPT/$name.torchscript.pt" --arch "$arch" --weights_format "$fmt" --batch_size 2 --precision "$PRECISION" \
-      --resize "${RESIZE:-host}" --decode "${DECODE:-host}" --decode_split "${DECODE_SPLIT:-none}"
+      --resize "${RESIZE:-host}" --decode "${DECODE:-host}" --decode_split "${DECODE_SPLIT:-none}" --decode_scans "${DECODE_SCANS:-host}"
   done
 done
 # PCA_FIT=hip fits the PCA on the train references on the GPU (implies --fit_pca; the model file is then an .npz, read by infer_query.sh

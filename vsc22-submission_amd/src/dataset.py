@@ -120,9 +120,22 @@ def check_decode_split(split: str, decode: str = "hip") -> str:
     return split
 
 
+DECODE_SCANS = ("host", "hip")   # --decode_scans: who decodes a jpg of several scans (progressive, one scan per component, Huffman table ids 2 and 3)
+
+
+def check_decode_scans(scans: str, decode: str = "hip") -> str:
+    """``scans`` if it is a known value; "hip" hands such files to the device decoder (vsc_jpeg_decode_scans_u8) and so needs ``decode="hip"``"""
+    if scans not in DECODE_SCANS:
+        raise ValueError(f"decode_scans must be one of {DECODE_SCANS}, not {scans!r}")
+    if scans == "hip" and decode != "hip":
+        raise ValueError("decode_scans='hip' needs decode='hip' (--decode hip): it is the device decoder that takes the files of several scans")
+    return scans
+
+
 class BytesVideo:
     """A video as its loader worker read it for ``--decode hip``: ``data`` uint8 [bytes], the jpg files one after the other,
-    ``offsets`` int64 [S + 1] where each starts and ``records`` the vsc_hip.jpeg.Frame of each.  Every file has been accepted by
+    ``offsets`` int64 [S + 1] where each starts and ``records`` the vsc_hip.jpeg.Frame (with ``--decode_scans hip`` also ScanFrame)
+    of each.  Every file has been accepted by
     the parser and all have one size (``shape`` = (S, H, W)).  ``restarts``: the CSR (int64 ptr [S + 1], int32 off) of the
     restart-marker offsets in every frame's segment (vsc_hip.jpeg.restart_rows), which ``--decode_split`` cuts frames at."""
 
@@ -139,13 +152,14 @@ class BytesVideo:
         return [raw[a:b].tobytes() for a, b in zip(self.offsets[:-1].tolist(), self.offsets[1:].tolist())]
 
 
-def bytes_video(files, warn=None):
+def bytes_video(files, warn=None, scans="host"):
     """The jpg files of one video -> a BytesVideo, or None where the video stays with Pillow as a whole: a file the parser
-    refuses (``warn(message)`` is told why), frames of different sizes, no frames."""
+    refuses (``warn(message)`` is told why), frames of different sizes, no frames.  ``scans="hip"``: the parser is
+    vsc_hip.jpeg.parse_scans, which also takes files of several scans."""
     from vsc_hip import jpeg
-    data, offsets, records = jpeg.pack(files)
+    data, offsets, records = jpeg.pack(files) if scans == "host" else jpeg.pack_scans(files)
     for i, r in enumerate(records):
-        if not isinstance(r, jpeg.Frame):
+        if isinstance(r, jpeg.Refusal):
             if warn is not None:
                 warn(f"frame {i} stays with the host decoder: {r.reason} ({r.message})")
             return None
@@ -162,12 +176,15 @@ def decode_rgb(img) -> np.ndarray:
 class ZipFrames(torch.utils.data.Dataset):
     """One item = all frames of one video, read from <prefix>/<vid[-2:]>/<vid>.zip of jpgs."""
 
-    def __init__(self, video_ids: Sequence[str], zip_prefix: str, transform, raw=False):
+    def __init__(self, video_ids: Sequence[str], zip_prefix: str, transform, raw=False, decode_scans="host"):
         """``raw`` (``--resize hip``): the workers only decode -- an item is (uint8 [S, H, W, 3] at the zip's own resolution, video_id)
         for ``raw_collate``; a video whose frames differ in size is resized by ``transform`` here, as without ``raw``.
         ``raw="bytes"`` (``--decode hip``): the workers only read the zip members and parse their headers -- an item is
-        (BytesVideo, video_id); a video with a frame the parser refuses is decoded here as a whole, as with ``raw=True``."""
+        (BytesVideo, video_id); a video with a frame the parser refuses is decoded here as a whole, as with ``raw=True``.
+        ``decode_scans="hip"`` (with ``raw="bytes"``): the parser also takes files of several scans (vsc_hip.jpeg.parse_scans)."""
         self.zip_prefix, self.transform, self.raw = zip_prefix, transform, raw
+        self.decode_scans = check_decode_scans(decode_scans, "hip" if raw == "bytes" else "host")
+        self.host_decoded = 0                                 # with raw="bytes": the videos this object (in its own process) decoded with Pillow
         self.video_ids = [v for v in video_ids if os.path.exists(self._path(v))]
 
     def _path(self, vid):
@@ -183,9 +200,10 @@ class ZipFrames(torch.utils.data.Dataset):
             if self.raw:
                 files = [z.read(n) for n in sorted(z.namelist())]
                 if self.raw == "bytes":
-                    video = bytes_video(files)
+                    video = bytes_video(files, scans=self.decode_scans)
                     if video is not None:
                         return video, vid
+                    self.host_decoded += 1
                 images = [Image.open(io.BytesIO(f)).convert("RGB") for f in files]
                 if len({im.size for im in images}) == 1:
                     return torch.from_numpy(np.stack([decode_rgb(im) for im in images])), vid

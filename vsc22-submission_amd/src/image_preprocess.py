@@ -306,12 +306,17 @@ class HipDecode:
     in the main process, as a whole (host frames; Pillow raises or decodes leniently as it does in the workers) and a warning
     names it.  The caller's stream is ordered behind the results.
     ``split`` (``--decode_split``: "none", "markers", "substreams" or "all"): frames are decoded in parallel inside, at their
-    restart markers and / or as self-synchronising sub-streams (vsc_jpeg_decode_split_u8: the same bytes and status)."""
+    restart markers and / or as self-synchronising sub-streams (vsc_jpeg_decode_split_u8: the same bytes and status).
+    ``scans`` (``--decode_scans``: "host" or "hip"): with "hip" the videos may hold frames of several scans (vsc_hip.jpeg.ScanFrame:
+    progressive, one scan per component, Huffman table ids 0 .. 3).  A batch that holds one goes through
+    vsc_jpeg_decode_scans_u8, single-scan frames included; with ``split`` the single-scan frames are cut as before in a call of
+    their own and the others follow in a second call, one wave each."""
 
-    def __init__(self, device, split="none"):
+    def __init__(self, device, split="none", scans="host"):
         import torch
-        from src.dataset import check_decode_split
+        from src.dataset import check_decode_scans, check_decode_split
         self.split = check_decode_split(split)
+        self.scans = check_decode_scans(scans)
         self.device = torch.device(device)
         self.stream = torch.cuda.Stream(device=self.device)
         self.pinned = None
@@ -329,10 +334,18 @@ class HipDecode:
         if not videos:
             return []
         sets = jpeg.TableSets()
+        several = any(isinstance(r, jpeg.ScanFrame) for v in videos for r in v.records)
+        assert not several or self.scans == "hip", "a video with frames of several scans reached a decoder made with scans='host'"
         rows, spans, at_bytes, at_out = [], [], 0, 0
+        records, file_at, out_at = [], [], []
         for v in videos:
             n, h, w = v.shape
-            rows.append(jpeg.frame_rows(v.records, (v.offsets[:-1] + at_bytes).tolist(), [at_out + i * h * w * 3 for i in range(n)], sets))
+            if several:
+                records += list(v.records)
+                file_at += (v.offsets[:-1] + at_bytes).tolist()
+                out_at += [at_out + i * h * w * 3 for i in range(n)]
+            else:
+                rows.append(jpeg.frame_rows(v.records, (v.offsets[:-1] + at_bytes).tolist(), [at_out + i * h * w * 3 for i in range(n)], sets))
             spans.append((at_out, n, h, w))
             at_bytes += int(v.data.numel())
             at_out += n * h * w * 3
@@ -351,8 +364,27 @@ class HipDecode:
             self.copied.record(torch.cuda.current_stream(self.device))
             self.used = True
             restarts = jpeg.concat_restart_rows([v.restarts for v in videos]) if self.split != "none" else None
-            out, status = ops.jpeg_decode(data, np.concatenate(rows), sets.array(), at_out, restarts=restarts, split=self.split)
-            status = status.cpu().numpy()          # waits for this stream only
+            if not several:
+                out, status = ops.jpeg_decode(data, np.concatenate(rows), sets.array(), at_out, restarts=restarts, split=self.split)
+                status = status.cpu().numpy()          # waits for this stream only
+            else:
+                # with a split the single-scan frames keep it, in a call of their own; every other frame, or without a split every frame, is one wave
+                one = [i for i, r in enumerate(records) if isinstance(r, jpeg.Frame)] if self.split != "none" else []
+                rest = sorted(set(range(len(records))) - set(one))
+                out = torch.empty(at_out, dtype=torch.uint8, device=self.device)
+                status = np.zeros(len(records), np.int32)
+                first_status = None
+                if one:
+                    rptr = np.concatenate([[0], np.cumsum(np.diff(restarts[0])[one])]).astype(np.int64)
+                    roff = np.concatenate([restarts[1][restarts[0][i]:restarts[0][i + 1]] for i in one]).astype(np.int32)
+                    r1 = jpeg.frame_rows([records[i] for i in one], [file_at[i] for i in one], [out_at[i] for i in one], sets)
+                    _, first_status = ops.jpeg_decode(data, r1, sets.array(), at_out, out=out, restarts=(rptr, roff), split=self.split)
+                wide = jpeg.ScanTableSets()
+                r2, srows, sptr = jpeg.scan_rows([records[i] for i in rest], [file_at[i] for i in rest], [out_at[i] for i in rest], wide)
+                _, st = ops.jpeg_decode(data, r2, wide.array(), at_out, out=out, scans=(srows, sptr))
+                status[rest] = st.cpu().numpy()        # waits for this stream only
+                if first_status is not None:
+                    status[one] = first_status.cpu().numpy()
         main.wait_stream(self.stream)
         out.record_stream(main)
         frames, first = [], 0

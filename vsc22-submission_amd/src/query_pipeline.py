@@ -11,7 +11,7 @@ from typing import Callable, Dict, Iterable, List, Sequence, Tuple
 import numpy as np
 import torch
 
-from src.dataset import BytesVideo, check_decode, check_decode_split, check_resize
+from src.dataset import BytesVideo, check_decode, check_decode_scans, check_decode_split, check_resize
 from src.query_postprocess import FRAME_FILTERS, HipOps, SCORE_THRESHOLD, process_query_group, process_query_video
 from vsc.index import VideoFeature
 
@@ -272,7 +272,7 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
                      pca_transform: Callable[[np.ndarray], np.ndarray], video_scores: Dict[str, float], device,
                      ops=HipOps, score_threshold: float = SCORE_THRESHOLD, chunk: int = None,
                      scorer: Callable[[torch.Tensor], float] = None,
-                     group_frames: int = 4096, views=None, frame_filter: str = "host", resize="host", decode="host", decode_split="none") -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
+                     group_frames: int = 4096, views=None, frame_filter: str = "host", resize="host", decode="host", decode_split="none", decode_scans="host") -> Tuple[List[VideoFeature], List[List[VideoFeature]]]:
     """videos yields (video_id, {image_size: frames [S,3,size,size]}, timestamps); encoders = [(model, image_size)].
     ``views`` (``--preprocess hip``, src.image_preprocess.HipViews): videos that carry full-resolution frames under ``RAW_KEY``
     are replaced by their views first (border removal and split views, ``_with_views``): k views of n frames encode as k * n rows.
@@ -289,7 +289,8 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
     ``decode``: "host" (the default), "hip" or a src.image_preprocess.HipDecode: videos that carry their jpg files under ``RAW_KEY``
     (src.dataset.BytesVideo) are decoded on the device (vsc_jpeg_decode_u8, Pillow's bytes) before ``resize`` takes them; needs
     ``resize`` on the device.  ``decode_split`` ("none", "markers", "substreams", "all"; needs ``decode="hip"``): the decoder it
-    makes cuts every frame into items (src.image_preprocess.HipDecode).
+    makes cuts every frame into items (src.image_preprocess.HipDecode).  ``decode_scans`` ("host", "hip"; needs ``decode="hip"``):
+    the decoder also takes videos whose BytesVideo holds frames of several scans (vsc_jpeg_decode_scans_u8).
     -> (final descriptors per video, per-model VideoFeatures per video), in input order."""
     if frame_filter not in FRAME_FILTERS:
         raise ValueError(f"frame_filter must be one of {FRAME_FILTERS}, not {frame_filter!r}")
@@ -304,11 +305,16 @@ def run_query_videos(videos: Iterable[Tuple[str, Dict[int, torch.Tensor], np.nda
     decoder = None if isinstance(decode, str) else decode
     if isinstance(decode, str) and check_decode(decode, "hip" if resizer is not None else "host") == "hip":
         from src.image_preprocess import HipDecode
-        decoder = HipDecode(device, check_decode_split(decode_split))
-    elif decode_split != "none":
-        check_decode_split(decode_split, decode if isinstance(decode, str) else "hip")
-        if decoder is not None:
-            decoder.split = check_decode_split(decode_split)
+        decoder = HipDecode(device, check_decode_split(decode_split), check_decode_scans(decode_scans))
+    else:
+        if decode_split != "none":
+            check_decode_split(decode_split, decode if isinstance(decode, str) else "hip")
+            if decoder is not None:
+                decoder.split = check_decode_split(decode_split)
+        if decode_scans != "host":
+            check_decode_scans(decode_scans, decode if isinstance(decode, str) else "hip")
+            if decoder is not None:
+                decoder.scans = check_decode_scans(decode_scans)
     if decoder is not None and resizer is None:
         raise ValueError("a decoder needs resize on the device")
     finals, per_model = [], []

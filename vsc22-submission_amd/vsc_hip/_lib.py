@@ -136,6 +136,7 @@ SIGNATURES = {
     "vsc_jpeg_decode_split": (c_int32, [c_void_p, c_int32, c_int32, c_int32, c_int32]),
     "vsc_jpeg_decode_split_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "vsc_jpeg_decode_stats": (c_int32, [c_void_p, c_void_p]),
+    "vsc_jpeg_decode_scans_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "vsc_frame_var_u8":(c_int32, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p]),
     "vsc_canny_count_u8": (c_int32, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, ctypes.c_double, ctypes.c_double,
                                      c_void_p, c_void_p]),

@@ -709,7 +709,7 @@ def jpeg_decode_stats():
     return tuple(int(v) for v in out)
 
 
-def jpeg_decode(data, rows, tables, out_len: int, out=None, restarts=None, split=None):
+def jpeg_decode(data, rows, tables, out_len: int, out=None, restarts=None, split=None, scans=None):
     """Baseline JPEG frames decoded on the device in one call (vsc_jpeg_decode_u8): ``data`` uint8 device tensor holding the files'
     bytes, ``rows`` int64 [n, 10] the frame table and ``tables`` uint8 [s, 1608] its table sets, both host arrays as
     vsc_hip.jpeg.frame_rows / TableSets.array build them -> (uint8 device tensor [out_len] with frame i packed at its row's output
@@ -717,17 +717,30 @@ def jpeg_decode(data, rows, tables, out_len: int, out=None, restarts=None, split
     Contract and refusals: vsc_jpeg_decode_u8 in include/vsc_hip.h.
     ``split`` (None or "none": one wave per frame, the default): frames are decoded in parallel inside (vsc_jpeg_decode_split_u8, the
     same bytes and status) -- "markers", "substreams", "all" or a dict (jpeg_decode_split_mode); ``restarts`` is then the CSR of
-    restart-marker offsets (int64 ptr [n + 1], int32 off) as vsc_hip.jpeg.restart_rows builds it, None: no frame has markers."""
+    restart-marker offsets (int64 ptr [n + 1], int32 off) as vsc_hip.jpeg.restart_rows builds it, None: no frame has markers.
+    ``scans`` (None: every frame is one sequential scan): (int64 [m, 10] scan table, int64 ptr [n + 1]) as vsc_hip.jpeg.scan_rows
+    builds them with ``rows``, and ``tables`` are then uint8 [s, 2696] (ScanTableSets): the frames -- progressive, several scans,
+    Huffman table ids 0 .. 3, single-scan ones beside them -- go through vsc_jpeg_decode_scans_u8, one wave per frame; not with ``split``."""
     import numpy as np
     lib = _rd()
     assert data.is_cuda and data.dtype == torch.uint8 and data.is_contiguous() and data.dim() == 1
     rows = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).reshape(-1, 10))
-    tables = np.ascontiguousarray(np.asarray(tables, dtype=np.uint8).reshape(-1, 1608))
+    tables = np.ascontiguousarray(np.asarray(tables, dtype=np.uint8).reshape(-1, 1608 if scans is None else 2696))
     n = rows.shape[0]
     if out is None:
         out = torch.empty(int(out_len), dtype=torch.uint8, device=data.device)
     assert out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() == int(out_len)
     status = torch.empty(n, dtype=torch.int32, device=data.device)
+    if scans is not None:
+        if split is not None and split != "none":
+            raise ValueError("jpeg_decode: frames of several scans are decoded one wave per frame; pass the single-scan frames to a call of their own to split them")
+        srows = np.ascontiguousarray(np.asarray(scans[0], dtype=np.int64).reshape(-1, 10))
+        sptr = np.ascontiguousarray(np.asarray(scans[1], dtype=np.int64))
+        assert sptr.shape == (n + 1,) and srows.shape[0] == int(sptr[-1]), "scans must be (int64 [m, 10], int64 ptr [n + 1]) with ptr[n] == m"
+        check(lib.vsc_jpeg_decode_scans_u8(jpeg_decode_handle(), ptr(data) if data.numel() else None, data.numel(), rows.ctypes.data if n else None, n,
+                                           srows.ctypes.data if len(srows) else None, sptr.ctypes.data, tables.ctypes.data if len(tables) else None, len(tables),
+                                           ptr(out) if out.numel() else None, out.numel(), ptr(status) if n else None))
+        return out, status
     if split is not None and split != "none":
         h = jpeg_decode_handle()
         check(lib.vsc_jpeg_decode_split(h, *jpeg_decode_split_mode(split)))
