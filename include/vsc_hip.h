@@ -262,6 +262,69 @@ int vsc_range_search_ip_f32(const float *q_dev, int64_t nq, const float *r_dev, 
  * vsc_knn_ip_f32's path; VSC_RANGE_PATH=exact|bf16 forces one. */
 int vsc_range_search_last_path(void);
 
+/* ------------------------------------------------------------------------ *
+ * Flat squared-L2 search: replaces faiss.IndexFlat(d, METRIC_L2).search / .range_search (infer/vsc/index.py:76-99; the
+ * reference's tests/test_index.py builds one).  Contract (executable form: tests/l2_search_contract.py):
+ *
+ *   Distance.  dist(q, r) = c_d with c_0 = +0.0f, t_j = q_j - r_j (one float32 rounding), c_{j+1} = fmaf(t_j, t_j, c_j), j
+ *   ascending; nothing is reassociated -- the L2 twin of the ascending-k float32 fmaf chain of vsc_knn_ip_f32.  A distance is a
+ *   function of its pair alone: it equals any slice of a larger call bit for bit, whichever path found the pair.
+ *   Top-k.  The k smallest distances over ALL nr rows, ascending, equal distances by ascending id; unused slots hold
+ *   (FLT_MAX, -1), as faiss pads.  A NaN or infinite distance is never reported (faiss's heap comparison rejects both).
+ *   ref_id_offset is added to every reported id.  The result equals brute force for every input, far clusters included:
+ *   the inner-product sweep on augmented operands only SELECTS candidates, and a row's list is taken from it only when
+ *   D_k < -s'_kk - slack(q), strictly (D_k: the k-th chain distance among the kk candidates, s'_kk: the kk-th expanded score,
+ *   slack(q): a bound on |expanded score + chain distance| over the bank) -- then no row outside the probe can beat
+ *   or tie the list -- or when the probe held the whole bank.  Every other row gets one wider probe under the same rule and is
+ *   then answered by a direct path that depends on no bound (chain distances against all rows, radix select on the bits, lower id first among equals).
+ *   Range.  Every pair with dist < radius, strict; CSR output query-major, ascending id inside a query; the count / capacity
+ *   protocol of vsc_range_search_ip_f32.
+ *
+ * The stream is the FIRST parameter of these entries.  Scratch: the search's grow-only per-device buffers (slots of their own,
+ * beside those of the inner-product sweep they call; vsc_search_release_scratch frees them).  One search call per device at a time.
+ * Alignment: every pointer at its element type, except r_aug_dev: 16 bytes when d + 2 is a multiple of 4 below 32 (it is the
+ * bank of a vsc_knn_ip_f32 sweep).  VSC_L2_PATH=probe|direct forces a path (probe: the sweep even for a bank one probe holds
+ * whole; rows it cannot certify still take the wider probe and the direct path).
+ * ------------------------------------------------------------------------ */
+
+/* Augmented rows for the sweep, from plain rows x_dev [n, d], 1 <= d <= 4094: aug_dev [n, d + 2] = [x, |x|^2, 1] (as_query == 0: bank
+ * rows) or [2x, -1, -|x|^2] (queries); norms_dev [n] = |x|^2; max_norm_dev [1] = the largest |x|^2 of the rows (non-finite if any row's
+ * is).  Each output may be NULL.  |x|^2 is a float32 sum of fmaf partial sums; a row whose |x|^2 is not finite is written as a zero
+ * row ([0, FLT_MAX, 1] / [0, -1, 0]).  These values only steer the selection: their bits are no part of the contract, their
+ * rounding is part of slack.  Done once per bank.  Only enqueues on `stream`; no host synchronisation. */
+int vsc_l2_augment_f32(void *stream, const float *x_dev, int64_t n, int32_t d, int32_t as_query, float *aug_dev, float *norms_dev,
+                       float *max_norm_dev);
+
+/* q_dev [nq, d], r_dev [nr, d] float32 row-major (the PLAIN rows), 1 <= k <= 1024; 1 <= d <= 4094 on the probe path, d <= 4096 on the
+ * direct path (d = 4095, 4096: always direct).  r_aug_dev [nr, d + 2] / r_max_norm_dev [1]: the bank's vsc_l2_augment_f32 outputs
+ * (aug_dev, max_norm_dev), or both NULL: the bank is augmented into scratch for this call.  out_dist_dev [nq, k] float32 ascending,
+ * out_ids_dev [nq, k] int64.  nq == 0: nothing is written; nr == 0: every slot (FLT_MAX, -1).  Anything else is refused by name with
+ * nothing written.
+ * Host synchronisation: a call that probes waits for `stream` once after the re-scoring, to read one certificate flag per query
+ * row (plus whatever the vsc_knn_ip_f32 sweep inside waits for), and, if some rows are not certified, once more to upload their
+ * list; the wider probe of those rows repeats the two; the direct path itself (banks of at most max(k + 8, 2k) rows,
+ * VSC_L2_PATH=direct) only enqueues. */
+int vsc_knn_l2_f32(void *stream, const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k,
+                   int64_t ref_id_offset, const float *r_aug_dev, const float *r_max_norm_dev, float *out_dist_dev,
+                   int64_t *out_ids_dev);
+
+/* Diagnostic: the query rows of the last vsc_knn_l2_f32 call of this process by path -- rows_out[0] certified at the first probe
+ * (kk = max(k + 8, 2k) ranks, at most 1024), rows_out[1] certified at the one wider probe (4 kk ranks, at least 256, at most 1024; there
+ * is none when that would hold the whole bank, or with VSC_L2_WIDE=0), rows_out[2] answered by the direct path. */
+int vsc_knn_l2_last_path(int64_t rows_out[3]);
+
+/* Range search, operands as vsc_knn_l2_f32, outputs as vsc_range_search_ip_f32: lims_dev [nq + 1] int64 CSR offsets, *total_out
+ * (host) the number of hits; hits are written only if total <= capacity, otherwise the caller calls again with capacity >=
+ * *total_out (capacity 0 = count only).  Sweep: the inner-product range sweep on the augmented operands at radius + slack (a
+ * superset by the bound), the chain on the survivors, dist < radius, a prefix sum; the direct form (VSC_L2_PATH=direct, d > 4094,
+ * no finite bound) materialises chain distances instead.  No hit goes to the host, only the totals.
+ * Host synchronisation: on the sweep path the call waits for `stream` once to read the two norm maxima, once per
+ * vsc_range_search_ip_f32 sweep inside (one, or two when the survivors outgrow the scratch) and once to read the total; on the
+ * direct path once, to read the total. */
+int vsc_range_search_l2_f32(void *stream, const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, float radius,
+                            int64_t ref_id_offset, const float *r_aug_dev, const float *r_max_norm_dev, int64_t *lims_dev,
+                            float *out_dist_dev, int64_t *out_ids_dev, int64_t capacity, int64_t *total_out);
+
 /* Per-candidate-pair frame similarity matrices -- the temporal alignment input of the matching track
  * (VSC22-Matching-Track-1st/infer/src/utils.py:29-51,66: np.matmul(qfeat, rfeat.T) per candidate).
  * q_dev [nq, d], r_dev [nr, d]: row banks (all query / reference videos' frames, concatenated).

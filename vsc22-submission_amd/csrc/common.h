@@ -57,7 +57,7 @@ void vsc_set_error(const char *fmt, ...);
 #define VSC_OPT_LIST(X)                                                                                                  \
     X(ATTN_SKEW) X(ATTN_ABL) X(ATTN_NI) X(ATTN_DMA) X(CONV_IMPLICIT) X(CONV_DIRECT) X(CONV_REMAP) X(CONV_PERSIST) X(CONV_STAGES) X(CONV_WAVES) X(CONV_NARROW_MAX) X(CONV_NARROW_NT) X(CONV_EXPAND) X(DWCONV_SMALL) X(CONV_STEM) X(CONV_STREAM_MIN_COUT) X(CONV_X3)      \
     X(GEMM_GROUP_N) X(GEMM_V4_SKEW) X(GEMM_TIMING_PRINT) X(GEMM_V4) X(GEMM_V4_GRID) X(GEMM_SKEW_NS_PER_K) X(GEMM_CFG)    \
-    X(GEMM_V3) X(GEMM_ABL) X(GEMM_V1) X(KNN_TRIG) X(KNN_ABL) X(KNN_PATH) X(KNN_XCD_MAP) X(KNN_DELTA) X(KNN_TAIL) X(RANGE_PATH) X(PAIRMAX_PATH) X(WATTN_ABL)      \
+    X(GEMM_V3) X(GEMM_ABL) X(GEMM_V1) X(KNN_TRIG) X(KNN_ABL) X(KNN_PATH) X(KNN_XCD_MAP) X(KNN_DELTA) X(KNN_TAIL) X(RANGE_PATH) X(PAIRMAX_PATH) X(L2_PATH) X(L2_WIDE) X(WATTN_ABL)      \
     X(SWIN_SPLIT_LN) X(SWIN_SPLIT_K) X(GEMM_LN_V4) X(SWIN_FUSED_MLP) X(SWIN_MLP512) X(SWIN_PROJ512) X(SWIN_QKV512) X(SWIN_MLP512_GRID) X(SWIN_FUSED_PROJ) X(SWIN_MLP_ABL) X(SWIN_MLP_SEQ) X(SWIN_MLP_NW4) X(SWIN_FUSED_MERGE) X(SWIN_ROW_MAX) X(LN_LIGHT) X(WATTN_STREAM) X(GEMM_LN_TAIL) X(JPEG_STAGES)
 enum VscOpt {
 #define X(n) OPT_##n,
@@ -313,6 +313,12 @@ int launch_f32_to_bf16(const float *src, uint16_t *dst, int64_t rows, int cols, 
 // grow-only device scratch of the search path (knn.hip), one set of slots per device; callers on one device are ordered
 // (one stream, or streams synchronised around the call); the slots: scratch_slots.h
 int search_scratch_get(int slot, size_t bytes, void **out);
+// vsc_knn_ip_f32 / vsc_range_search_ip_f32 (ref_id_offset 0) for callers inside the library (l2_search.hip): the same sweeps and bits,
+// and the diagnostics of the entries (vsc_knn_last_path, vsc_range_search_last_path, the profile) keep what the caller's own last call left
+int search_knn_ip(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k, float *out_scores_dev,
+                  int64_t *out_ids_dev, hipStream_t stream);
+int search_range_ip(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, float radius, int64_t *lims_dev,
+                    float *out_scores_dev, int64_t *out_ids_dev, int64_t capacity, int64_t *total_out, hipStream_t stream);
 // temporal-network alignment (tn_align.hip), contract at vsc_tn_align_f32 in include/vsc_hip.h
 int launch_tn_align(const float *sims, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias, int max_step,
                     int top_k, int max_path, double min_sim, int min_length, double max_iou, int32_t *boxes, int32_t *counts,

@@ -1998,6 +1998,25 @@ extern "C" int vsc_range_search_ip_f32(const float *q_dev, int64_t nq, const flo
     return VSC_OK;
 }
 
+int search_knn_ip(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, int32_t k, float *out_scores_dev,
+                  int64_t *out_ids_dev, hipStream_t stream) {
+    const int path = g_knn_last_path;
+    const bool profiling = g_knn_profiling;
+    g_knn_profiling = false;
+    const int rc = knn_ip_impl(q_dev, nq, r_dev, nr, d, k, 0, nullptr, out_scores_dev, out_ids_dev, stream);
+    g_knn_profiling = profiling;
+    g_knn_last_path = path;
+    return rc;
+}
+
+int search_range_ip(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d, float radius, int64_t *lims_dev,
+                    float *out_scores_dev, int64_t *out_ids_dev, int64_t capacity, int64_t *total_out, hipStream_t stream) {
+    const int path = g_range_last_path;
+    const int rc = vsc_range_search_ip_f32(q_dev, nq, r_dev, nr, d, radius, 0, lims_dev, out_scores_dev, out_ids_dev, capacity, total_out, stream);
+    g_range_last_path = path;
+    return rc;
+}
+
 extern "C" int vsc_pair_similarity_f32(const float *q_dev, int64_t nq, const float *r_dev, int64_t nr, int32_t d,
                                        const int64_t *pairs_host, int64_t n_pairs, int64_t *out_offsets_host,
                                        float *out_dev, int64_t capacity, void *stream_) {

@@ -28,5 +28,13 @@ enum SearchScratchSlot {
     SCRATCH_UAP_KEYS = 34, SCRATCH_UAP_PAY = 35,          // rank: the sorts' two key buffers; two position buffers + the score keys.  curve: both term lists; (tps, last row) per tie group
     SCRATCH_UAP_HIST = 36, SCRATCH_UAP_TREE = 37,         // rank: [digit][tile] counters.  curve: counts per tile; the pairwise trees' slots
     SCRATCH_FRAME_FILTER_BITS = 38,                       // frame_filter.hip: adjacency bit matrices too large for LDS
+    // l2_search.hip; live only inside its own entries, beside the slots of the inner-product sweep they call
+    SCRATCH_L2_QAUG = 39, SCRATCH_L2_QNORM = 40,          // augmented queries; their |q|^2 (top-k) / the largest of them (range)
+    SCRATCH_L2_RAUG = 41, SCRATCH_L2_RMAX = 42,           // a bank augmented for one call (no caller's copy); its largest |r|^2
+    SCRATCH_L2_PROBE_S = 43, SCRATCH_L2_PROBE_I = 44,     // the probe's [nq, kk] scores / ids; range: the sweep's survivors
+    SCRATCH_L2_FLAGS = 45, SCRATCH_L2_ROWS = 46,          // certificate per query row; the rows sent to the direct path
+    SCRATCH_L2_DIST = 47,                                 // direct path: one materialised [rows, nr] chunk of distance bits
+    SCRATCH_L2_COUNTS = 48, SCRATCH_L2_SLIMS = 49,        // range: hits per query row; the sweep's CSR offsets
+    SCRATCH_L2_QAUG2 = 50,                                // the augmented queries of the wider probe
     SCRATCH_SLOTS
 };

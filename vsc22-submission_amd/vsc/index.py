@@ -66,6 +66,9 @@ class PairMatches:
                    "ref_start": m.ref_timestamps[0], "ref_end": m.ref_timestamps[1], "score": m.score}
 
 
+L2_FORMS = ("host", "hip")
+
+
 class FlatIPBank:
     """What `faiss.index_factory(dim, "Flat", metric)` is to the reference: add() appends rows, search() is the exact
     top-k.  Rows live in HBM as one float32 matrix (bigger, fewer allocations: sized for 288 GB).
@@ -74,11 +77,22 @@ class FlatIPBank:
     rows are stored as r' = [r, |r|^2, 1] and a query is presented as q' = [2q, -1, -|q|^2], so <q', r'> = -|q - r|^2
     and "largest inner product" is "smallest distance".  The sweep SELECTS; the squared distances handed back are
     recomputed on the host from the selected rows as sum((q - r)^2) in float32 (what faiss's flat L2 scan returns), so
-    no cancellation error of the expanded form reaches the caller."""
+    no cancellation error of the expanded form reaches the caller.  That `l2="host"` form's probe of max(k + 8, 2k) ranks is a
+    heuristic: on a cluster far from the origin (300 rows in d = 16 at norm 200, spread 1e-2) the expanded form's rounding exceeds the
+    neighbour distances and true neighbours fall outside the probe.
 
-    def __init__(self, dim: int, metric: int = METRIC_INNER_PRODUCT):
+    l2="hip" (METRIC_L2 only; opt-in): the bank is uploaded as plain rows and augmented on the device once, and search /
+    range_search / range_count run vsc_knn_l2_f32 / vsc_range_search_l2_f32 -- distances are the device's fmaf chain, the selection
+    is certified per query row or redone exactly (include/vsc_hip.h), nothing is recomputed on the host; search_device,
+    range_search_device and adopt_device_rows work for L2 too."""
+
+    def __init__(self, dim: int, metric: int = METRIC_INNER_PRODUCT, l2: str = "host"):
         if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
             raise NotImplementedError(f"metric {metric}: the reference only builds inner-product and L2 flat indexes")
+        if l2 not in L2_FORMS:
+            raise ValueError(f"l2 {l2!r}: one of {L2_FORMS}")
+        self.l2 = l2
+        self._l2_aug = None             # l2="hip": (augmented rows, largest norm) of the device bank, made once per bank
         self.d = dim
         self.metric_type = metric
         self._chunks: list = []
@@ -91,29 +105,35 @@ class FlatIPBank:
     def is_similarity(self) -> bool:
         return self.metric_type == METRIC_INNER_PRODUCT
 
+    @property
+    def l2_native(self) -> bool:
+        return self.metric_type == METRIC_L2 and self.l2 == "hip"
+
     def add(self, x: np.ndarray) -> None:
         x = np.ascontiguousarray(x, dtype=np.float32)
         assert x.ndim == 2 and x.shape[1] == self.d, f"expected [n,{self.d}], got {x.shape}"
         self._chunks.append(x)
-        self._bank = self._bank_max_norm = None
+        self._bank = self._bank_max_norm = self._l2_aug = None
         self.adopted = False
         self.ntotal += x.shape[0]
 
     def reset(self) -> None:
         self._chunks, self._bank, self._bank_max_norm, self.ntotal, self.adopted = [], None, None, 0, False
+        self._l2_aug = None
 
     def adopt_device_rows(self, rows_dev) -> None:
         """The rows added so far already stand on the device as `rows_dev` ([ntotal, d] float32, contiguous: the finished array of a
         device score normalisation): it becomes the device bank and nothing is uploaded.  The caller vouches that it holds the bytes
-        of the added rows.  Valid until the next add(); inner-product banks only (an L2 bank stores augmented rows)."""
+        of the added rows.  Valid until the next add(); inner-product banks and l2="hip" banks (an l2="host" bank stores augmented
+        rows)."""
         import torch
-        if not self.is_similarity:
-            raise ValueError("adopt_device_rows: inner-product indexes only")
+        if not self.is_similarity and not self.l2_native:
+            raise ValueError("adopt_device_rows: inner-product indexes only (or METRIC_L2 with l2='hip')")
         if not (rows_dev.is_cuda and rows_dev.dtype == torch.float32 and rows_dev.is_contiguous()
                 and tuple(rows_dev.shape) == (self.ntotal, self.d)):
             raise ValueError(f"adopt_device_rows: expected a contiguous float32 [{self.ntotal}, {self.d}] device tensor, got "
                              f"{rows_dev.dtype} {tuple(rows_dev.shape)}")
-        self._bank, self.adopted = rows_dev, True
+        self._bank, self.adopted, self._l2_aug = rows_dev, True, None
 
     def _host_rows(self) -> np.ndarray:
         if len(self._chunks) > 1:
@@ -131,11 +151,20 @@ class FlatIPBank:
     def device_bank(self):
         if self._bank is None:
             host = self._host_rows()
-            if not self.is_similarity:
+            if not self.is_similarity and not self.l2_native:
                 sq = np.einsum("ij,ij->i", host, host, dtype=np.float32)[:, None]
                 host = np.concatenate([host, sq, np.ones_like(sq)], axis=1)
             self._bank = self._to_device(host)
         return self._bank
+
+    def _l2_operands(self, x: np.ndarray):
+        """l2="hip": (plain queries, plain bank, (augmented bank, largest norm)) on the device; the bank's share is made once."""
+        from vsc_hip import ops
+        bank = self.device_bank()
+        if self._l2_aug is None:
+            aug, _, max_norm = ops.l2_augment(bank)
+            self._l2_aug = (aug, max_norm)
+        return self._to_device(np.ascontiguousarray(x, dtype=np.float32).reshape(-1, self.d)), bank, self._l2_aug
 
     def _device_queries(self, x: np.ndarray):
         x = np.ascontiguousarray(x, dtype=np.float32)
@@ -163,6 +192,9 @@ class FlatIPBank:
         METRIC_L2 this is the count of the expanded-form sweep, which may differ from the exact-distance count by the
         pairs within its rounding of the radius (range_search re-filters them)."""
         from vsc_hip import ops
+        if self.l2_native:      # the exact count: the device's own distances, nothing to re-filter
+            q, bank, aug = self._l2_operands(x)
+            return ops.range_count_l2(q, bank, float(radius), bank=aug)
         radius = float(radius) if self.is_similarity else -float(radius)
         return ops.range_count_ip(self._device_queries(x) if q_dev is None else q_dev, self.device_bank(), radius)
 
@@ -179,6 +211,9 @@ class FlatIPBank:
         """All (query row, ref row, score) with score > radius (inner product) / distance < radius (L2) -> three flat
         arrays, query-major, ascending ref row inside a query (faiss.Index.range_search, flattened)."""
         from vsc_hip import ops
+        if self.l2_native:
+            rows, ids, dist = self.range_search_device(x, radius)
+            return rows.cpu().numpy(), ids.cpu().numpy(), dist.cpu().numpy()
         bank = self.device_bank()
         q = self._device_queries(x)
         if self.is_similarity:
@@ -202,10 +237,13 @@ class FlatIPBank:
         """search() whose result stays on the device: (D [nq,k] float32, I [nq,k] int64) tensors.  Inner product only: the L2
         form orders by distances recomputed on the host."""
         from vsc_hip import ops
-        if not self.is_similarity:
-            raise ValueError("search_device: inner-product indexes only (METRIC_L2 needs the host's exact distances)")
+        if not self.is_similarity and not self.l2_native:
+            raise ValueError("search_device: inner-product indexes only (METRIC_L2 needs the host's exact distances, or l2='hip')")
         if k > MAX_K:
             raise NotImplementedError(f"k={k} > {MAX_K} is not supported by vsc_knn_ip_f32")
+        if self.l2_native:
+            q, bank, aug = self._l2_operands(x)
+            return ops.knn_l2(q, bank, k, bank=aug)
         return ops.knn_ip(self._device_queries(x), self.device_bank(), k)
 
     def range_search_device(self, x: np.ndarray, radius: float):
@@ -213,9 +251,13 @@ class FlatIPBank:
         row inside a query.  Inner product only."""
         import torch
         from vsc_hip import ops
-        if not self.is_similarity:
-            raise ValueError("range_search_device: inner-product indexes only (METRIC_L2 needs the host's exact distances)")
-        lims, D, I = ops.range_search_ip(self._device_queries(x), self.device_bank(), float(radius))
+        if not self.is_similarity and not self.l2_native:
+            raise ValueError("range_search_device: inner-product indexes only (METRIC_L2 needs the host's exact distances, or l2='hip')")
+        if self.l2_native:
+            q, bank, aug = self._l2_operands(x)
+            lims, D, I = ops.range_search_l2(q, bank, float(radius), bank=aug)
+        else:
+            lims, D, I = ops.range_search_ip(self._device_queries(x), self.device_bank(), float(radius))
         rows = torch.repeat_interleave(torch.arange(lims.numel() - 1, dtype=torch.int64, device=lims.device), lims[1:] - lims[:-1])
         return rows, I, D
 
@@ -223,6 +265,9 @@ class FlatIPBank:
         """-> (D [nq,k] float32, I [nq,k] int64), faiss.Index.search semantics: inner products descending, or squared
         L2 distances ascending."""
         from vsc_hip import ops
+        if self.l2_native:
+            D, I = self.search_device(x, k)
+            return D.cpu().numpy(), I.cpu().numpy()
         bank = self.device_bank()
         q = self._device_queries(x)
         if k > MAX_K:
@@ -268,10 +313,11 @@ SELECTIONS = ("host", "hip")
 
 
 class VideoIndex:
-    def __init__(self, dim: int, codec_str: str = "Flat", metric: int = METRIC_INNER_PRODUCT, selection: str = "host"):
+    def __init__(self, dim: int, codec_str: str = "Flat", metric: int = METRIC_INNER_PRODUCT, selection: str = "host", l2: str = "host"):
         """selection: where the global top-k is cut and grouped -- "host": the probe is copied back, ordered by _best_first and
         grouped with numpy; "hip": the probe stays on the device (vsc_global_topk_f32, vsc_pair_first_hits) and only the
-        selected hits / the candidate pairs come back.  Same lists either way."""
+        selected hits / the candidate pairs come back.  Same lists either way.
+        l2: the METRIC_L2 form of the flat index (FlatIPBank): "host" or "hip"."""
         if codec_str != "Flat":
             raise NotImplementedError(f"codec {codec_str!r}: the descriptor track only uses 'Flat'")
         if selection not in SELECTIONS:
@@ -281,7 +327,7 @@ class VideoIndex:
         self.selection = selection
         self._ref_video_table = None    # (names, int32 video of every bank row on the device), built once per bank
         self.dim = dim
-        self.index = FlatIPBank(dim, metric)
+        self.index = FlatIPBank(dim, metric, l2=l2)
         self.video_clip_idx: list = []
         self.video_clip_to_video_ids: list = []
         self.video_metadata: dict = {}

@@ -173,7 +173,13 @@ SIGNATURES = {
     "vsc_knn_last_profile": (c_int32, [c_void_p]),
     "vsc_range_search_ip_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_float, c_int64,
                                           c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64), c_void_p]),
-    "vsc_l2_normalize_f32": (c_int32, [c_void_p, c_int64, c_int32, c_void_p]),
+    "vsc_l2_augment_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "vsc_knn_l2_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int64, c_void_p, c_void_p, c_void_p,
+                                 c_void_p]),
+    "vsc_knn_l2_last_path": (c_int32, [POINTER(c_int64)]),
+    "vsc_range_search_l2_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_float, c_int64, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+    "vsc_l2_normalize_f32":(c_int32, [c_void_p, c_int64, c_int32, c_void_p]),
     "vsc_score_norm_create": (c_int32, [c_void_p, POINTER(c_void_p)]),
     "vsc_score_norm_destroy": (None, [c_void_p]),
     "vsc_column_var_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int64, c_void_p]),

@@ -309,6 +309,86 @@ def range_count_ip(q, r, radius: float) -> int:
     return int(total.value)
 
 
+def l2_augment(x, as_query: bool = False):
+    """Augmented rows of the L2 search's sweep (vsc_l2_augment_f32): x [n, d] float32 on the GPU -> (aug [n, d + 2], norms [n] = |x|^2,
+    max_norm [1] = the largest of them).  Bank rows [x, |x|^2, 1], or with as_query [2x, -1, -|x|^2].  Once per bank: the pair
+    (aug, max_norm) is the `bank=` of knn_l2 / range_search_l2."""
+    lib = _rd()
+    x = _dev(x, torch.float32)
+    n, d = x.shape
+    aug = torch.empty((n, d + 2), dtype=torch.float32, device=x.device)
+    norms = torch.empty(n, dtype=torch.float32, device=x.device)
+    max_norm = torch.zeros(1, dtype=torch.float32, device=x.device)
+    check(lib.vsc_l2_augment_f32(current_stream(), ptr(x) if n else None, n, d, int(bool(as_query)), ptr(aug) if n else None,
+                                 ptr(norms) if n else None, ptr(max_norm)))
+    return aug, norms, max_norm
+
+
+def _l2_bank(bank, nr, d):
+    if bank is None:
+        return None, None
+    aug, max_norm = bank
+    assert aug.is_cuda and aug.dtype == torch.float32 and tuple(aug.shape) == (nr, d + 2), "bank: l2_augment's rows of these references"
+    assert max_norm.is_cuda and max_norm.dtype == torch.float32 and max_norm.numel() == 1
+    return ptr(aug) if nr else None, ptr(max_norm) if nr else None
+
+
+def knn_l2(q, r, k: int, ref_id_offset: int = 0, bank=None):
+    """Exact squared-L2 top-k (vsc_knn_l2_f32).  q [nq, d], r [nr, d] float32 on the GPU (plain rows) -> (distances [nq, k] float32
+    ascending, ids [nq, k] int64; equal distances by ascending id, unused slots (FLT_MAX, -1)).  bank: (aug, max_norm) of
+    l2_augment(r), or None: the bank is augmented for this call."""
+    lib = _rd()
+    q, r = _dev(q, torch.float32), _dev(r, torch.float32)
+    nq, d = q.shape
+    nr = r.shape[0]
+    assert r.shape[1] == d, "query / reference dimension mismatch"
+    dist = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    aug, max_norm = _l2_bank(bank, nr, d)
+    check(lib.vsc_knn_l2_f32(current_stream(), ptr(q) if nq else None, nq, ptr(r) if nr else None, nr, d, k, ref_id_offset, aug, max_norm,
+                             ptr(dist) if nq else None, ptr(ids) if nq else None))
+    return dist, ids
+
+
+def knn_l2_last_path():
+    """Query rows of the last knn_l2 call by path: (certified at the first probe, at a wider probe, direct) -- vsc_knn_l2_last_path."""
+    import ctypes
+    out = (ctypes.c_int64 * 3)()
+    check(_rd().vsc_knn_l2_last_path(out))
+    return tuple(int(v) for v in out)
+
+
+def range_search_l2(q, r, radius: float, ref_id_offset: int = 0, capacity: int = 1 << 20, bank=None):
+    """All pairs with squared L2 distance < radius (vsc_range_search_l2_f32).  -> (lims [nq+1] int64, distances, ids), hits of query i
+    in lims[i]:lims[i+1], ascending reference id.  capacity 0: count only -> (lims, empty, empty) with lims[-1] the total."""
+    import ctypes
+    lib = _rd()
+    q, r = _dev(q, torch.float32), _dev(r, torch.float32)
+    nq, d = q.shape
+    nr = r.shape[0]
+    assert r.shape[1] == d, "query / reference dimension mismatch"
+    lims = torch.zeros(nq + 1, dtype=torch.int64, device=q.device)
+    aug, max_norm = _l2_bank(bank, nr, d)
+    total = ctypes.c_int64(0)
+    count_only = capacity == 0
+    while True:
+        dist = torch.empty(capacity, dtype=torch.float32, device=q.device)
+        ids = torch.empty(capacity, dtype=torch.int64, device=q.device)
+        check(lib.vsc_range_search_l2_f32(current_stream(), ptr(q) if nq else None, nq, ptr(r) if nr else None, nr, d, float(radius),
+                                          ref_id_offset, aug, max_norm, ptr(lims), ptr(dist) if capacity else None,
+                                          ptr(ids) if capacity else None, capacity, ctypes.byref(total)))
+        if total.value <= capacity or count_only:
+            n = 0 if count_only else total.value
+            return lims, dist[:n], ids[:n]
+        capacity = int(total.value)
+
+
+def range_count_l2(q, r, radius: float, bank=None) -> int:
+    """Number of pairs with squared L2 distance < radius: vsc_range_search_l2_f32 with capacity 0."""
+    lims, _, _ = range_search_l2(q, r, radius, capacity=0, bank=bank)
+    return int(lims[-1].item())
+
+
 GLOBAL_TOPK_TILE = 2048     # VSC_GLOBAL_TOPK_TILE (include/vsc_hip.h): entries per workgroup of the compaction passes
 
 
