@@ -31,7 +31,7 @@ typedef void* hipStream_t;
 struct dim3 { unsigned x; dim3(unsigned a):x(a){} };
 struct Idx { int x; };
 static thread_local Idx threadIdx, blockIdx;
-constexpr int EMU_BLOCK = 512;
+constexpr int EMU_BLOCK = 1024;     // the device's own limit
 static std::barrier<> *g_block_bar;
 static std::barrier<> *g_wave_bar[EMU_BLOCK/64];
 static uint64_t g_xch[EMU_BLOCK/64][64];
@@ -51,6 +51,13 @@ static inline unsigned long long __ballot(bool p) {
 static inline int __popcll(unsigned long long v) { return __builtin_popcountll(v); }
 static inline int __ffsll(long long v) { return __builtin_ffsll(v); }
 static inline uint32_t atomicAdd(uint32_t *p, uint32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
+static inline unsigned atomicMin(unsigned *p, unsigned v) {     // (g++ has no __atomic_fetch_min)
+    unsigned old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (v < old && !__atomic_compare_exchange_n(p, &old, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old; }
+static inline unsigned long long atomicCAS(unsigned long long *p, unsigned long long expect, unsigned long long v) {
+    __atomic_compare_exchange_n(p, &expect, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED); return expect; }     // -> what *p held
+static inline unsigned __float_as_uint(float x) { unsigned u; memcpy(&u, &x, sizeof u); return u; }
 static char g_err[512];
 #define VSC_REQUIRE(cond, ...) do { if (!(cond)) { snprintf(g_err, sizeof g_err, __VA_ARGS__); fprintf(stderr, "%s\n", g_err); return VSC_ERR_INVALID; } } while (0)
 #define VSC_TRY(expr) do { if (int _rc = (expr)) return _rc; } while (0)

@@ -30,6 +30,7 @@ KERNELS = {
     "segment_metric": (("segment_metric.hip",), "common.h", None),
     "score_norm": (("score_norm.hip",), "common.h", None),
     "uap": (("uap.hip",), "common.h", None),
+    "global_topk": (("global_topk.hip",), "common.h", None),
     "frame_filter": (("frame_filter.hip",), "frame_filter.h", "ff_smem"),
     "view_decide": (("view_decide.hip",), "view_decide.h", "vd_smem"),
     "frame_inputs": (("frame_inputs.hip",), "frame_inputs.h", "fi_smem"),

@@ -148,3 +148,16 @@ def test_emulated_scratch_is_reused_across_sizes(emulated):
     for name in order:
         check_case(emulated, cases.get(name))
     assert emulated.lib.emu_scratch_allocs() == before, "a call no larger than an earlier one grew the scratch"
+
+
+def test_emulated_grown_sort_tile(emulated, tmp_path_factory):
+    """built with VSC_SORT_MAX_TILES = 1: the 2 500 predictions take one tile of 2 560, ten rounds of one workgroup, where the plain
+    build takes two tiles of 2 048 in each of its 8 + 3 digit passes over them"""
+    grown = Emulated(hip_emu_build.build_shared(tmp_path_factory, "uap_grown", hip_emu_build.source("uap"), ["-DVSC_SORT_MAX_TILES=1"]))
+    blocks = []
+    for emu in (emulated, grown):
+        before = emu.lib.emu_blocks()
+        check_case(emu, cases.get("n2500_ties"))
+        blocks.append(emu.lib.emu_blocks() - before)
+    grown.close()
+    assert blocks[0] - blocks[1] == (8 + 3) * 2 * (2 - 1), blocks      # (histogram, scatter) x one tile fewer

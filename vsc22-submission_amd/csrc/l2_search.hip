@@ -22,6 +22,7 @@
 
 #define VSC_TU_BF16 1   // no 16-bit operands here: one object for both builds of the library
 #include "common.h"
+#include "scan_sort.h"
 
 namespace {
 
@@ -391,14 +392,6 @@ __global__ __launch_bounds__(256) void l2_range_fill_kernel(const unsigned *__re
     }
 }
 
-template <class T>
-int slot(int s, size_t bytes, T **out) {
-    void *p = nullptr;
-    VSC_TRY(search_scratch_get(s, bytes, &p));
-    *out = (T *)p;
-    return VSC_OK;
-}
-
 inline unsigned blocks_of(int64_t items, int per) {
     const int64_t b = (items + per - 1) / per;
     return (unsigned)(b < 1 ? 1 : b);
@@ -434,7 +427,7 @@ int knn_direct(const float *q, const float *r, int64_t nr, int d, int k, int64_t
                int64_t *out_i, hipStream_t stream) {
     const int64_t step = chunk_rows(nr);
     unsigned *dist;
-    VSC_TRY(slot(SCRATCH_L2_DIST, (size_t)(n < step ? n : step) * nr * 4, &dist));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_DIST, (size_t)(n < step ? n : step) * nr * 4, &dist));
     for (int64_t lo = 0; lo < n; lo += step) {
         const int64_t rows = n - lo < step ? n - lo : step;
         VSC_TRY(launch_dist(q, r, nr, d, rows_list ? rows_list + lo : nullptr, lo, rows, dist, stream));
@@ -480,8 +473,8 @@ static int bank_operands(const float *r_dev, int64_t nr, int d, const float *r_a
     }
     float *a;
     unsigned *m;
-    VSC_TRY(slot(SCRATCH_L2_RAUG, (size_t)nr * (d + 2) * 4, &a));
-    VSC_TRY(slot(SCRATCH_L2_RMAX, 16, &m));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_RAUG, (size_t)nr * (d + 2) * 4, &a));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_RMAX, 16, &m));
     VSC_TRY(augment(r_dev, nr, d, 0, a, nullptr, m, stream));
     *aug = a;
     *max_bits = m;
@@ -523,10 +516,10 @@ extern "C" int vsc_knn_l2_f32(void *stream_, const float *q_dev, int64_t nq, con
     int *flags;
     const float *r_aug;
     const unsigned *r_max;
-    VSC_TRY(slot(SCRATCH_L2_QAUG, (size_t)nq * (d + 2) * 4, &q_aug));
-    VSC_TRY(slot(SCRATCH_L2_QNORM, (size_t)nq * 4, &q_norm));
-    VSC_TRY(slot(SCRATCH_L2_FLAGS, (size_t)nq * 4, &flags));
-    VSC_TRY(slot(SCRATCH_L2_ROWS, (size_t)nq * 8, &rows_dev));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_QAUG, (size_t)nq * (d + 2) * 4, &q_aug));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_QNORM, (size_t)nq * 4, &q_norm));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_FLAGS, (size_t)nq * 4, &flags));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_ROWS, (size_t)nq * 8, &rows_dev));
     VSC_TRY(bank_operands(r_dev, nr, d, r_aug_dev, r_max_norm_dev, &r_aug, &r_max, stream));
     VSC_TRY(augment(q_dev, nq, d, 1, q_aug, q_norm, nullptr, stream));
     // the rows a probe of `ranks` ranks cannot certify: sweep, re-score (their lists are written either way), read the flags
@@ -534,8 +527,8 @@ extern "C" int vsc_knn_l2_f32(void *stream_, const float *q_dev, int64_t nq, con
     auto probe_pass = [&](const float *qa, int64_t n, int64_t ranks, const int64_t *rows_list) -> int {
         float *probe_s;
         int64_t *probe_i;
-        VSC_TRY(slot(SCRATCH_L2_PROBE_S, (size_t)n * ranks * 4, &probe_s));
-        VSC_TRY(slot(SCRATCH_L2_PROBE_I, (size_t)n * ranks * 8, &probe_i));
+        VSC_TRY(search_scratch_get(SCRATCH_L2_PROBE_S, (size_t)n * ranks * 4, &probe_s));
+        VSC_TRY(search_scratch_get(SCRATCH_L2_PROBE_I, (size_t)n * ranks * 8, &probe_i));
         VSC_TRY(search_knn_ip(qa, n, r_aug, nr, d + 2, (int)ranks, probe_s, probe_i, stream));
         hipLaunchKernelGGL(l2_rescore_kernel, dim3((unsigned)n), dim3(256), (size_t)d * 4, stream, q_dev, r_dev, nr, d, k, (int)ranks,
                            (const float *)probe_s, (const int64_t *)probe_i, (const float *)q_norm, r_max, ref_id_offset, rows_list, out_dist_dev,
@@ -563,7 +556,7 @@ extern "C" int vsc_knn_l2_f32(void *stream_, const float *q_dev, int64_t nq, con
     if (!todo.empty() && wide > kk && wide < nr && !vsc_opt_is(OPT_L2_WIDE, '0')) {
         const int64_t n = (int64_t)todo.size();
         float *q_aug2;
-        VSC_TRY(slot(SCRATCH_L2_QAUG2, (size_t)n * (d + 2) * 4, &q_aug2));
+        VSC_TRY(search_scratch_get(SCRATCH_L2_QAUG2, (size_t)n * (d + 2) * 4, &q_aug2));
         hipLaunchKernelGGL(l2_gather_rows_kernel, dim3((unsigned)n), dim3(256), 0, stream, (const float *)q_aug, (const int64_t *)rows_dev, d + 2,
                            q_aug2);
         VSC_CHECK_LAUNCH();
@@ -610,7 +603,7 @@ extern "C" int vsc_range_search_l2_f32(void *stream_, const float *q_dev, int64_
     }
     VSC_REQUIRE(q_dev && r_dev, "range_search_l2: null pointer");
     long long *counts;
-    VSC_TRY(slot(SCRATCH_L2_COUNTS, (size_t)nq * 8, &counts));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_COUNTS, (size_t)nq * 8, &counts));
     bool fill = false;
     if (forced != L2_DIRECT && d <= 4094) {
         // the sweep's radius: widened by the largest slack of the call (one read of the two norm maxima)
@@ -618,8 +611,8 @@ extern "C" int vsc_range_search_l2_f32(void *stream_, const float *q_dev, int64_
         unsigned *q_max;
         const float *r_aug;
         const unsigned *r_max;
-        VSC_TRY(slot(SCRATCH_L2_QAUG, (size_t)nq * (d + 2) * 4, &q_aug));
-        VSC_TRY(slot(SCRATCH_L2_QNORM, 16, &q_max));
+        VSC_TRY(search_scratch_get(SCRATCH_L2_QAUG, (size_t)nq * (d + 2) * 4, &q_aug));
+        VSC_TRY(search_scratch_get(SCRATCH_L2_QNORM, 16, &q_max));
         VSC_TRY(bank_operands(r_dev, nr, d, r_aug_dev, r_max_norm_dev, &r_aug, &r_max, stream));
         VSC_TRY(augment(q_dev, nq, d, 1, q_aug, nullptr, q_max, stream));
         unsigned maxima[2] = {0, 0};
@@ -635,10 +628,10 @@ extern "C" int vsc_range_search_l2_f32(void *stream_, const float *q_dev, int64_
             int64_t *s_lims, *s_ids;
             float *s_scores;
             int64_t cap = 1 << 20, total_s = 0;
-            VSC_TRY(slot(SCRATCH_L2_SLIMS, (size_t)(nq + 1) * 8, &s_lims));
+            VSC_TRY(search_scratch_get(SCRATCH_L2_SLIMS, (size_t)(nq + 1) * 8, &s_lims));
             for (int attempt = 0; attempt < 2; ++attempt) {
-                VSC_TRY(slot(SCRATCH_L2_PROBE_S, (size_t)cap * 4, &s_scores));
-                VSC_TRY(slot(SCRATCH_L2_PROBE_I, (size_t)cap * 8, &s_ids));
+                VSC_TRY(search_scratch_get(SCRATCH_L2_PROBE_S, (size_t)cap * 4, &s_scores));
+                VSC_TRY(search_scratch_get(SCRATCH_L2_PROBE_I, (size_t)cap * 8, &s_ids));
                 VSC_TRY(search_range_ip(q_aug, nq, r_aug, nr, d + 2, sweep_radius, s_lims, s_scores, s_ids, cap, &total_s, stream));
                 if (total_s <= cap) break;
                 VSC_REQUIRE(attempt == 0, "range_search_l2: the sweep's count changed between two calls");
@@ -667,7 +660,7 @@ extern "C" int vsc_range_search_l2_f32(void *stream_, const float *q_dev, int64_
     // direct: materialised chunks, counted, then -- if the hits fit -- materialised again and filled
     const int64_t step = chunk_rows(nr);
     unsigned *dist;
-    VSC_TRY(slot(SCRATCH_L2_DIST, (size_t)(nq < step ? nq : step) * nr * 4, &dist));
+    VSC_TRY(search_scratch_get(SCRATCH_L2_DIST, (size_t)(nq < step ? nq : step) * nr * 4, &dist));
     for (int pass = 0; pass < 2; ++pass) {
         for (int64_t lo = 0; lo < nq; lo += step) {
             const int64_t rows = nq - lo < step ? nq - lo : step;

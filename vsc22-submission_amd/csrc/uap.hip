@@ -4,9 +4,7 @@
 // interned; everything else the reference does with sorted(), sets, a merge and cumsum is here:
 //  vsc_uap_rank_f64
 //   (a) stable ascending LSD radix sort (8-bit digits) of the order-preserving 64-bit image of -score with the input position as
-//       payload: the order of sorted(reverse=True) and argsort(-s, kind="mergesort").  The scheme of global_topk.hip part (C) --
-//       per-tile digit histograms, one exclusive scan over [digit][tile], stable in-tile ranking by wave ballots -- on 64-bit
-//       keys.  (global_topk.hip keeps its own 32-bit copy: its objects and results do not change.)
+//       payload: the order of sorted(reverse=True) and argsort(-s, kind="mergesort").  The sort is scan_sort.h's, on 64-bit keys.
 //   (b) the same sort, keys only and only the passes below key_bits, of the prediction keys and of the ground-truth keys, each
 //       followed by a count of adjacent equal keys: the duplicates the reference detects with sets.
 //   (c) one binary search per ranked prediction in the sorted ground truth: `correct`.
@@ -29,6 +27,7 @@
 // on the caller's stream (as the segment-metric and score-normalisation entries do) and only enqueue on it.  Divisions are IEEE fp64
 // divisions of exactly representable integers; nothing is contracted.  No 16-bit operands: one object for both builds of the library.
 #include "common.h"
+#include "scan_sort.h"
 
 // contract arithmetic: every product, difference and sum rounded on its own
 #pragma clang fp contract(off)
@@ -40,7 +39,6 @@ constexpr int UAP_ITEMS = 8;                      // consecutive rows of one thr
 constexpr int UAP_TILE = VSC_UAP_TILE;
 static_assert(UAP_TILE == UAP_THREADS * UAP_ITEMS, "tile = threads x items");
 constexpr int UAP_SCAN_THREADS = 512;
-constexpr int UAP_MAX_SORT_TILES = 4096;          // the sort's tile grows beyond this many tiles: the [256][tiles] scan stays <= 1M counters
 constexpr int UAP_PW_LEAF = 128;                  // numpy's PW_BLOCKSIZE
 constexpr int UAP_PW_CHUNK = 8192;                // numpy's reduction hands its inner loop at most this many elements (its buffer size)
 constexpr int UAP_PW_LOCAL = 8;                   // a chunk's tree has at most this many levels below the root (2^8 = UAP_THREADS slots)
@@ -49,58 +47,6 @@ constexpr int UAP_NO_LEAF = 255;
 struct UapCounters {
     unsigned nonfinite, dup_pred, dup_gt, n_pos;
 };
-
-__device__ inline unsigned wave_scan_incl(unsigned v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned t = __shfl_up(v, o, 64);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-// exclusive prefix of v over the workgroup's threads, *total = the sum; wsum: NT / 64 words of LDS (reusable across calls: the
-// leading barrier orders a call behind the reads of the one before)
-template <int NT>
-__device__ inline unsigned block_scan_excl(unsigned v, unsigned *wsum, unsigned *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned inc = wave_scan_incl(v);
-    __syncthreads();
-    if (lane == 63) wsum[wave] = inc;
-    __syncthreads();
-    unsigned base = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) {
-        const unsigned s = wsum[w];
-        if (w < wave) base += s;
-        tot += s;
-    }
-    *total = tot;
-    return base + inc - v;
-}
-
-// exclusive scan in place of `segments` runs of `len` counters each, one workgroup per run; totals (or null): [segments]
-struct UapScanArgs {
-    unsigned *data;
-    int64_t len;
-    unsigned *totals;
-};
-
-__global__ __launch_bounds__(UAP_SCAN_THREADS) void uap_scan_kernel(UapScanArgs a) {
-    __shared__ unsigned wsum[UAP_SCAN_THREADS / 64];
-    unsigned *d = a.data + (int64_t)blockIdx.x * a.len;
-    unsigned carry = 0;
-    for (int64_t base = 0; base < a.len; base += UAP_SCAN_THREADS) {
-        const int64_t i = base + threadIdx.x;
-        const unsigned v = i < a.len ? d[i] : 0u;
-        unsigned tot;
-        const unsigned ex = block_scan_excl<UAP_SCAN_THREADS>(v, wsum, &tot);
-        if (i < a.len) d[i] = carry + ex;
-        carry += tot;
-    }
-    if (a.totals && threadIdx.x == 0) a.totals[blockIdx.x] = carry;
-}
 
 __device__ inline uint64_t f64_bits(double x) {
     uint64_t u;
@@ -124,76 +70,6 @@ __global__ __launch_bounds__(UAP_THREADS) void uap_build_kernel(UapBuildArgs a) 
         u ^= 0x8000000000000000ull;                                  // -score
         if (u == 0x8000000000000000ull) u = 0ull;
         a.keys[i] = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-    }
-}
-
-// ---- stable LSD radix sort, one 8-bit digit per pass ------------------------------------------------------------------------------
-struct UapSortArgs {
-    const uint64_t *keys_in;
-    const int64_t *pay_in;     // null: the payload of entry i is i (the first pass of a sort that carries positions)
-    uint64_t *keys_out;
-    int64_t *pay_out;          // null: keys only
-    int64_t m, tile, nbs;
-    unsigned *hist;            // [256][nbs]
-    int shift;
-};
-
-__global__ __launch_bounds__(UAP_THREADS) void uap_sort_hist_kernel(UapSortArgs a) {
-    __shared__ unsigned h[256];
-    const int tid = threadIdx.x;
-    h[tid] = 0u;
-    __syncthreads();
-    const int64_t lo = (int64_t)blockIdx.x * a.tile;
-    const int64_t hi = lo + a.tile < a.m ? lo + a.tile : a.m;
-    for (int64_t i = lo + tid; i < hi; i += UAP_THREADS) atomicAdd(&h[(unsigned)(a.keys_in[i] >> a.shift) & 255u], 1u);
-    __syncthreads();
-    a.hist[(int64_t)tid * a.nbs + blockIdx.x] = h[tid];
-}
-
-// hist: after the scan, the first output slot of (digit, tile).  Inside a tile an element's slot is that base + the elements of
-// its digit in earlier rounds of 256 (running) + those in lower waves of its round (wcount) + those in lower lanes of its wave.
-__global__ __launch_bounds__(UAP_THREADS) void uap_sort_scatter_kernel(UapSortArgs a) {
-    constexpr int WAVES = UAP_THREADS / 64;
-    __shared__ unsigned running[256];
-    __shared__ unsigned wcount[WAVES][256];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    running[tid] = a.hist[(int64_t)tid * a.nbs + blockIdx.x];
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) wcount[w][tid] = 0u;
-    __syncthreads();
-    const int64_t lo = (int64_t)blockIdx.x * a.tile;
-    const int64_t hi = lo + a.tile < a.m ? lo + a.tile : a.m;
-    for (int64_t r = lo; r < hi; r += UAP_THREADS) {
-        const int64_t i = r + tid;
-        const bool active = i < hi;
-        const uint64_t k = active ? a.keys_in[i] : 0ull;
-        const int64_t v = active ? (a.pay_in ? a.pay_in[i] : i) : 0;
-        const unsigned d = (unsigned)(k >> a.shift) & 255u;
-        unsigned long long peers = __ballot(active);      // lanes of this wave that hold the same digit
-#pragma unroll
-        for (int bit = 0; bit < 8; ++bit) {
-            const bool set = (d >> bit) & 1u;
-            const unsigned long long bal = __ballot(set);
-            peers &= set ? bal : ~bal;
-        }
-        const unsigned below = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
-        if (active && below == 0u) wcount[wave][d] = (unsigned)__popcll(peers);
-        __syncthreads();
-        if (active) {
-            unsigned o = running[d] + below;
-            for (int w = 0; w < wave; ++w) o += wcount[w][d];
-            a.keys_out[o] = k;
-            if (a.pay_out) a.pay_out[o] = v;
-        }
-        __syncthreads();
-        unsigned add = 0;
-#pragma unroll
-        for (int w = 0; w < WAVES; ++w) {
-            add += wcount[w][tid];
-            wcount[w][tid] = 0u;
-        }
-        running[tid] += add;
-        __syncthreads();
     }
 }
 
@@ -457,61 +333,6 @@ __global__ void uap_pw_total_kernel(UapPwArgs a) {
     *a.out = res;
 }
 
-inline int grid_for(int64_t items, int per_block, int cap) {
-    const int64_t b = (items + per_block - 1) / per_block;
-    return (int)(b < 1 ? 1 : (b > cap ? cap : b));
-}
-
-template <class T>
-int uap_scratch(int slot, size_t bytes, T **out) {
-    void *p = nullptr;
-    VSC_TRY(search_scratch_get(slot, bytes, &p));
-    *out = (T *)p;
-    return VSC_OK;
-}
-
-// Sorts m keys by their low `bits` bits; src is only read.  keys: two buffers of `stride` keys; pay (or null: keys only): two
-// buffers of `stride` positions, which start as 0 .. m - 1; hist: uap_sort_tiles(m) x 256 counters.  Returns where the last pass
-// left its output.
-int64_t uap_sort_tile(int64_t m) {
-    int64_t tile = UAP_TILE;
-    if ((m + tile - 1) / tile > UAP_MAX_SORT_TILES)
-        tile = ((m + UAP_MAX_SORT_TILES - 1) / UAP_MAX_SORT_TILES + UAP_THREADS - 1) / UAP_THREADS * UAP_THREADS;
-    return tile;
-}
-int64_t uap_sort_tiles(int64_t m) { return (m + uap_sort_tile(m) - 1) / uap_sort_tile(m); }
-
-int uap_sort(const uint64_t *src, int64_t m, int bits, uint64_t *keys, int64_t *pay, int64_t stride, unsigned *hist, hipStream_t stream,
-             const uint64_t **keys_sorted, const int64_t **pay_sorted) {
-    const int64_t tile = uap_sort_tile(m), nbs = uap_sort_tiles(m);
-    UapSortArgs a;
-    a.keys_in = src;
-    a.pay_in = nullptr;
-    a.keys_out = keys;
-    a.pay_out = pay;
-    a.m = m;
-    a.tile = tile;
-    a.nbs = nbs;
-    a.hist = hist;
-    for (int shift = 0; shift < bits; shift += 8) {
-        a.shift = shift;
-        hipLaunchKernelGGL(uap_sort_hist_kernel, dim3((unsigned)nbs), dim3(UAP_THREADS), 0, stream, a);
-        VSC_CHECK_LAUNCH();
-        UapScanArgs sc = {hist, nbs * 256, nullptr};
-        hipLaunchKernelGGL(uap_scan_kernel, dim3(1), dim3(UAP_SCAN_THREADS), 0, stream, sc);
-        VSC_CHECK_LAUNCH();
-        hipLaunchKernelGGL(uap_sort_scatter_kernel, dim3((unsigned)nbs), dim3(UAP_THREADS), 0, stream, a);
-        VSC_CHECK_LAUNCH();
-        a.keys_in = a.keys_out;
-        a.pay_in = a.pay_out;
-        a.keys_out = a.keys_in == keys ? keys + stride : keys;
-        if (pay) a.pay_out = a.pay_in == pay ? pay + stride : pay;
-    }
-    *keys_sorted = a.keys_in;
-    if (pay_sorted) *pay_sorted = a.pay_in;
-    return VSC_OK;
-}
-
 int uap_pairwise(const double *terms, const unsigned *len_dev, int64_t len_bound, double *chunks, double *out, hipStream_t stream) {
     UapPwArgs a = {terms, len_dev, len_bound, chunks, out};
     hipLaunchKernelGGL(uap_pw_chunk_kernel, dim3((unsigned)uap_pw_chunks(len_bound)), dim3(UAP_THREADS), 0, stream, a);
@@ -520,6 +341,9 @@ int uap_pairwise(const double *terms, const unsigned *len_dev, int64_t len_bound
     VSC_CHECK_LAUNCH();
     return VSC_OK;
 }
+
+// the shared sort as this file uses it: the length on the host, positions (or nothing) as the payload
+constexpr auto uap_sort = radix_sort<UAP_SCAN_THREADS, uint64_t, int64_t>;
 
 }  // namespace
 
@@ -551,12 +375,12 @@ extern "C" int vsc_uap_rank_f64(vsc_uap *h, const double *scores_dev, const uint
     UapCounters *cnt;
     uint64_t *keys;
     int64_t *pay;
-    VSC_TRY(uap_scratch(SCRATCH_UAP_STATE, sizeof(UapCounters), &cnt));
-    VSC_TRY(uap_scratch(SCRATCH_UAP_KEYS, (size_t)stride * 2 * 8, &keys));
-    VSC_TRY(uap_scratch(SCRATCH_UAP_PAY, (size_t)n * 3 * 8, &pay));
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_STATE, sizeof(UapCounters), &cnt));
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_KEYS, (size_t)stride * 2 * 8, &keys));
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_PAY, (size_t)n * 3 * 8, &pay));
     unsigned *hist;
-    const int64_t tiles = uap_sort_tiles(n) > uap_sort_tiles(g) ? uap_sort_tiles(n) : uap_sort_tiles(g);
-    VSC_TRY(uap_scratch(SCRATCH_UAP_HIST, (size_t)tiles * 256 * 4, &hist));
+    const int64_t tiles = sort_tiles(n) > sort_tiles(g) ? sort_tiles(n) : sort_tiles(g);
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_HIST, (size_t)tiles * 256 * 4, &hist));
     uint64_t *score_keys = (uint64_t *)(pay + 2 * n);               // the sort's input; its two key buffers are `keys`
     VSC_CHECK_HIP(hipMemsetAsync(cnt, 0, sizeof(UapCounters), stream));
     const int sweep = grid_for(n, UAP_THREADS, 2048);
@@ -565,14 +389,14 @@ extern "C" int vsc_uap_rank_f64(vsc_uap *h, const double *scores_dev, const uint
     VSC_CHECK_LAUNCH();
     const uint64_t *sorted;
     const int64_t *perm_sorted;
-    VSC_TRY(uap_sort(score_keys, n, 64, keys, pay, n, hist, stream, &sorted, &perm_sorted));
-    VSC_TRY(uap_sort(pred_keys_dev, n, key_bits, keys, nullptr, stride, hist, stream, &sorted, nullptr));
+    VSC_TRY(uap_sort(score_keys, nullptr, nullptr, n, 64, keys, pay, n, hist, stream, &sorted, &perm_sorted));
+    VSC_TRY(uap_sort(pred_keys_dev, nullptr, nullptr, n, key_bits, keys, nullptr, stride, hist, stream, &sorted, nullptr));
     UapDupArgs dp = {sorted, n, &cnt->dup_pred, sweep};
     hipLaunchKernelGGL(uap_dup_kernel, dim3(sweep), dim3(UAP_THREADS), 0, stream, dp);
     VSC_CHECK_LAUNCH();
     sorted = nullptr;
     if (g) {
-        VSC_TRY(uap_sort(gt_keys_dev, g, key_bits, keys, nullptr, stride, hist, stream, &sorted, nullptr));
+        VSC_TRY(uap_sort(gt_keys_dev, nullptr, nullptr, g, key_bits, keys, nullptr, stride, hist, stream, &sorted, nullptr));
         const int gsweep = grid_for(g, UAP_THREADS, 2048);
         UapDupArgs dg = {sorted, g, &cnt->dup_gt, gsweep};
         hipLaunchKernelGGL(uap_dup_kernel, dim3(gsweep), dim3(UAP_THREADS), 0, stream, dg);
@@ -599,16 +423,14 @@ extern "C" int vsc_uap_curve_f64(vsc_uap *h, const double *scores_ranked_dev, co
     const int64_t chunks_n = uap_pw_chunks(n);
     unsigned *blk, *groups;
     double *terms, *slots;
-    VSC_TRY(uap_scratch(SCRATCH_UAP_HIST, (size_t)(2 * nb + 2) * 4, &blk));
-    VSC_TRY(uap_scratch(SCRATCH_UAP_PAY, (size_t)n * 2 * 4, &groups));
-    VSC_TRY(uap_scratch(SCRATCH_UAP_KEYS, (size_t)n * 2 * 8, &terms));
-    VSC_TRY(uap_scratch(SCRATCH_UAP_TREE, (size_t)chunks_n * 8, &slots));
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_HIST, (size_t)(2 * nb + 2) * 4, &blk));
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_PAY, (size_t)n * 2 * 4, &groups));
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_KEYS, (size_t)n * 2 * 8, &terms));
+    VSC_TRY(search_scratch_get(SCRATCH_UAP_TREE, (size_t)chunks_n * 8, &slots));
     UapCurveArgs c = {scores_ranked_dev, correct_dev, n, n_gt, nb, blk, curve_dev, terms + n, groups, groups + n};
     hipLaunchKernelGGL(uap_curve_count_kernel, dim3((unsigned)nb), dim3(UAP_THREADS), 0, stream, c);
     VSC_CHECK_LAUNCH();
-    UapScanArgs sc = {blk, nb, blk + 2 * nb};
-    hipLaunchKernelGGL(uap_scan_kernel, dim3(2), dim3(UAP_SCAN_THREADS), 0, stream, sc);
-    VSC_CHECK_LAUNCH();
+    VSC_TRY(scan_runs<UAP_SCAN_THREADS>(blk, nb, 2, blk + 2 * nb, stream));
     hipLaunchKernelGGL(uap_curve_rows_kernel, dim3((unsigned)nb), dim3(UAP_THREADS), 0, stream, c);
     VSC_CHECK_LAUNCH();
     const int sweep = grid_for(n, UAP_THREADS, 2048);
