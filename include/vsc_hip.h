@@ -188,6 +188,66 @@ int vsc_swin_set_profiling(vsc_swin *enc, int32_t on);
 int vsc_swin_get_profile(vsc_swin *enc, double ms_out[VSC_SWIN_PROF_CLASSES], int64_t launches_out[VSC_SWIN_PROF_CLASSES]);
 
 /* ------------------------------------------------------------------------ *
+ * CNN frame encoder: the VSC22 baseline's descriptor model, the SSCD ResNet-50 (infer/vsc/baseline: a TorchScript model adapted
+ * from sscd_disc_mixup.torchvision.pt) -- torchvision's ResNet-50 v1.5 without fc, GeM(p) over the last map, Linear, optional L2.
+ * Convolutions run on the 16-bit matrix pipe in the library's operand type with fp32 accumulation (csrc/conv16.hip); BatchNorm is
+ * folded into weight + bias by the caller.  Tensor names: conv1.{weight,bias}, layerL.B.conv{1,2,3}.{weight,bias} (L = 1..4),
+ * layerL.0.downsample.{weight,bias}, head.{weight,bias}; convolution weights as [cout, cin, kh, kw] fp32.
+ * Frames of ANY H, W >= 1 are taken, (n, H, W) per call; a frame's descriptor does not depend on what else is in the call.
+ * ------------------------------------------------------------------------ */
+typedef struct vsc_cnn_encoder vsc_cnn_encoder;
+
+typedef struct vsc_cnn_encoder_config {
+    int32_t stem_width;      /* 64 */
+    int32_t widths[4];       /* stage output widths (256, 512, 1024, 2048): multiples of 256, the bottleneck width is a quarter */
+    int32_t depths[4];       /* (3, 4, 6, 3) */
+    int32_t head_in, head_out; /* head_in = widths[3] <= 2048; head_out <= 2048 */
+    float gem_p;
+    int32_t l2;              /* 0: the adapted model's un-normalised projection; 1: the original model's L2-normalised descriptor */
+    int64_t max_pixels;      /* largest n * H * W of one call: sizes the workspace (for even H, W; odd extents grow it once) */
+} vsc_cnn_encoder_config;
+
+int vsc_cnn_encoder_create(const vsc_cnn_encoder_config *cfg, vsc_cnn_encoder **out);
+void vsc_cnn_encoder_destroy(vsc_cnn_encoder *enc);
+int vsc_cnn_encoder_set_weight(vsc_cnn_encoder *enc, const char *name, const float *host, size_t count);
+int vsc_cnn_encoder_finalize(vsc_cnn_encoder *enc);
+/* The stream comes first, as in the entries of the exact L2 search.
+ * frames_dev f32 [n, 3, h, w], already normalised -> desc_dev f32 [n, head_out]; asynchronous on `stream` (a call whose odd extents
+ * need a larger workspace than any call before waits for the device once).  Refused before anything is launched, with nothing
+ * written: a null handle or pointer, n < 0, h or w < 1, n * h * w above max_pixels (VSC_ERR_INVALID); a handle that is not
+ * finalized (VSC_ERR_STATE). */
+int vsc_cnn_encoder_forward(void *stream, vsc_cnn_encoder *enc, const float *frames_dev, int64_t n, int32_t h, int32_t w, float *desc_dev);
+/* uint8 [n, h, w, 3] input; mean / std: host arrays of 3; (v / 255 - mean) / std in fp32, the order of ToTensor + Normalize */
+int vsc_cnn_encoder_forward_u8(void *stream, vsc_cnn_encoder *enc, const uint8_t *frames_u8_dev, int64_t n, int32_t h, int32_t w,
+                               const float *mean, const float *std, float *desc_dev);
+int64_t vsc_cnn_encoder_workspace_bytes(const vsc_cnn_encoder *enc);
+/* Per-class timing as vsc_swin_set_profiling: stem rows, stem convolution, max-pool, the four stages, GeM + head. */
+enum {
+    VSC_CNN_PROF_STEM_ROWS = 0, VSC_CNN_PROF_STEM_CONV = 1, VSC_CNN_PROF_MAXPOOL = 2, VSC_CNN_PROF_STAGE0 = 3, VSC_CNN_PROF_POOL_HEAD = 7,
+    VSC_CNN_PROF_CLASSES = 8
+};
+int vsc_cnn_encoder_set_profiling(vsc_cnn_encoder *enc, int32_t on);
+int vsc_cnn_encoder_get_profile(vsc_cnn_encoder *enc, double ms_out[VSC_CNN_PROF_CLASSES], int64_t launches_out[VSC_CNN_PROF_CLASSES]);
+
+/* Building blocks of the CNN encoder (csrc/conv16.hip), in the library's 16-bit operand type whatever the name's suffix says (as
+ * vsc_gemm_bf16).  All NHWC, asynchronous on `stream` (their first argument), every refusal (VSC_ERR_INVALID) named before anything is launched.
+ *
+ * vsc_conv2d_nhwc_bf16: out[n, ho, wo, cout] = act(bias + conv(in[n, h, w, cin], w[cout, ksize, ksize, cin]) + residual), fp32
+ * accumulation, one rounding to the operand type at the store.  ksize 1 or 3, stride 1 or 2, padding (ksize - 1) / 2 with zeros,
+ * ho = (h + 2 pad - ksize) / stride + 1.  cin a multiple of 64, cout a multiple of 4.  bias_dev [cout] fp32 and residual_dev
+ * [n, ho, wo, cout] may be NULL; relu != 0 clamps at zero last.  Alignment: in_dev, w_dev 16 bytes; residual_dev, out_dev 8 bytes.
+ * vsc_maxpool3x3s2_nhwc_bf16: 3 x 3, stride 2, pad 1, the maximum over the taps inside the image; c a multiple of 8; 16-byte aligned.
+ * vsc_stem_rows_u8: im2col rows of the 7 x 7 stride-2 pad-3 stem: rows_dev [n ho wo, 192], k = (r * 7 + s) * 3 + c, zeros for
+ * k >= 147 and for taps outside the image.  Exactly one of frames_u8_dev [n, h, w, 3] (normalised with the host arrays mean / std as
+ * above) and frames_f32_dev [n, 3, h, w] (already normalised).  rows_dev 16-byte aligned. */
+int vsc_conv2d_nhwc_bf16(void *stream, const uint16_t *in_dev, const uint16_t *w_dev, const float *bias_dev, const uint16_t *residual_dev,
+                         uint16_t *out_dev, int64_t n, int32_t h, int32_t w, int32_t cin, int32_t cout, int32_t ksize, int32_t stride,
+                         int32_t relu);
+int vsc_maxpool3x3s2_nhwc_bf16(void *stream, const uint16_t *in_dev, uint16_t *out_dev, int64_t n, int32_t h, int32_t w, int32_t c);
+int vsc_stem_rows_u8(void *stream, const uint8_t *frames_u8_dev, const float *frames_f32_dev, int64_t n, int32_t h, int32_t w,
+                     const float *mean, const float *std, uint16_t *rows_dev);
+
+/* ------------------------------------------------------------------------ *
  * Flat inner-product search: replaces faiss.IndexFlat(d, METRIC_INNER_PRODUCT)
  *   .search(x, k)        infer/vsc/index.py:167-175, infer/vsc/baseline/score_normalization.py:95,141,
  *                        infer/vsc/exhaustive_search.py:66 (the k = 1024 probe of range_search_gpu)

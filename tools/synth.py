@@ -269,3 +269,53 @@ def vsm_weights(seed: int, cfg) -> dict:
     w["output_proj.weight"] = normalish(nxt(), (1, 2 * h), 1.0 / np.sqrt(2 * h))
     w["output_proj.bias"] = normalish(nxt(), (1,), 0.05)
     return w
+
+
+def frames_u8(seed: int, n: int, h: int, w: int) -> np.ndarray:
+    """[n, H, W, 3] uint8 decoded frames: a smooth per-frame gradient plus noise (so that the pooling windows see structure)"""
+    noise = uniform(seed, (n, h, w, 3), 0.0, 96.0)
+    yy = np.arange(h, dtype=np.float32)[None, :, None, None] / max(h - 1, 1)
+    xx = np.arange(w, dtype=np.float32)[None, None, :, None] / max(w - 1, 1)
+    tilt = uniform(seed + 1, (n, 1, 1, 3), 0.0, 1.0)
+    base = 159.0 * (tilt * yy + (1.0 - tilt) * xx)
+    return np.clip(np.floor(base + noise), 0, 255).astype(np.uint8)
+
+
+def resnet_weights(seed: int, cfg) -> dict:
+    """Random-init weights of the CNN descriptor backbone (vsc_hip/cnn_config.py) under torchvision's state-dict names, as the SSCD
+    checkpoint carries them: ``backbone.conv1`` / ``bn1``, ``backbone.layerL.B.convK`` / ``bnK`` / ``downsample.{0,1}``,
+    ``embeddings.1`` (the head's Linear).
+
+    Recipe: He-scaled convolutions (std sqrt(2 / fan_in)), BatchNorm gamma 1 with std 0.1 except the LAST BatchNorm of a block (0.25 with std 0.025:
+    the residual branch adds a fraction of the identity's energy per block, as a trained network's does), beta +- 0.1, running means
+    with spread (std 0.3) and running variances in [1.5, 2.5] -- a He-scaled convolution of a unit-RMS rectified input has variance
+    ~2, so the folded scale is ~1 / sqrt(2).  This keeps the activation RMS of every stage within [0.1, 10]
+    (tests/golden/gen_sscd_resnet_golden.py and tests/test_sscd_resnet_cpu.py assert it)."""
+    s = seed * 1000
+    w = {}
+
+    def nxt():
+        nonlocal s
+        s += 1
+        return s
+
+    def conv_bn(conv, bn, cout, cin, k, gamma):
+        w[conv + ".weight"] = normalish(nxt(), (cout, cin, k, k), float(np.sqrt(2.0 / (cin * k * k))))
+        w[bn + ".weight"] = gamma + normalish(nxt(), (cout,), 0.2 * gamma * 0.5)
+        w[bn + ".bias"] = normalish(nxt(), (cout,), 0.1)
+        w[bn + ".running_mean"] = normalish(nxt(), (cout,), 0.3)
+        w[bn + ".running_var"] = uniform(nxt(), (cout,), 1.5, 2.5)
+
+    conv_bn("backbone.conv1", "backbone.bn1", cfg.stem_width, 3, 7, 1.0)
+    for st in range(4):
+        for b in range(cfg.depths[st]):
+            cin, mid, cout, _ = cfg.block_io(st, b)
+            p = f"backbone.layer{st + 1}.{b}."
+            conv_bn(p + "conv1", p + "bn1", mid, cin, 1, 1.0)
+            conv_bn(p + "conv2", p + "bn2", mid, mid, 3, 1.0)
+            conv_bn(p + "conv3", p + "bn3", cout, mid, 1, 0.25)
+            if b == 0:
+                conv_bn(p + "downsample.0", p + "downsample.1", cout, cin, 1, 1.0)
+    w["embeddings.1.weight"] = normalish(nxt(), (cfg.out_dim, cfg.widths[3]), 1.0 / np.sqrt(cfg.widths[3]))
+    w["embeddings.1.bias"] = normalish(nxt(), (cfg.out_dim,), 0.05)
+    return w

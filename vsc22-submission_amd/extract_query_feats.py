@@ -124,6 +124,16 @@ def resize_of(args) -> str:
     return check_resize(getattr(args, "resize", "host"))
 
 
+def check_models(models):
+    """the parsed --models specs; a CNN arch is refused by name: the ensemble path is square-input only"""
+    from vsc_hip.cnn_config import CNN_PRESETS
+    specs = [parse_model_spec(s) for s in models]
+    for arch, _, _ in specs:
+        if arch in CNN_PRESETS:
+            raise ValueError(f"--models: {arch} is a CNN arch; the query ensemble is square-input only (use extract_ref_feats.py --arch {arch})")
+    return specs
+
+
 def main(args):
     resize = resize_of(args)
     decode = check_decode(getattr(args, "decode", "host"), resize)
@@ -131,7 +141,7 @@ def main(args):
     decode_scans = check_decode_scans(getattr(args, "decode_scans", "host"), decode)
     torch.cuda.set_device(0)
     device = torch.device("cuda", 0)
-    specs = [parse_model_spec(s) for s in args.models]
+    specs = check_models(args.models)
     encoders = [load_encoder(arch, fmt, path, args.max_batch, precision=args.precision) for arch, fmt, path in specs]
     pca = HipPCA(load_pca_model(args.pca_model))
     with open(args.input_file, encoding="utf-8") as f:

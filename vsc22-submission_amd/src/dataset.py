@@ -73,6 +73,34 @@ def clip_transform_u8(size: int = 224):
     return apply
 
 
+def sscd_transform_u8(mode: str):
+    """The VSC22 baseline's two inference transforms up to ToTensor (infer/vsc/baseline/inference_impl.py:33-54) as uint8 Pillow
+    transforms: uint8 [H', W', 3]; ToTensor + Normalize(ImageNet mean / std) then run on the device inside the CNN encoder's stem
+    (vsc_hip.cnn_config.IMAGENET_MEAN / IMAGENET_STD).
+    ``resize_288``: torchvision's Resize(288) -- short side to 288, long side int(288 * long / short), bilinear; a frame whose short
+    side is 288 already is returned as it is.  ``resize_320_center``: Resize(320), then CenterCrop(320) with torchvision's offsets
+    int(round((extent - 320) / 2.0))."""
+    from PIL import Image
+    if mode not in SSCD_TRANSFORMS:
+        raise ValueError(f"transforms must be one of {SSCD_TRANSFORMS}, not {mode!r}")
+    size = 288 if mode == "resize_288" else 320
+
+    def apply(img) -> torch.Tensor:
+        img = img.convert("RGB")
+        w, h = img.size
+        nw, nh = (size, int(size * h / w)) if w <= h else (int(size * w / h), size)
+        if (nw, nh) != (w, h):
+            img = img.resize((nw, nh), Image.BILINEAR)
+        if mode == "resize_320_center":
+            left, top = int(round((nw - size) / 2.0)), int(round((nh - size) / 2.0))
+            img = img.crop((left, top, left + size, top + size))
+        return torch.from_numpy(np.asarray(img, dtype=np.uint8).copy())
+    return apply
+
+
+SSCD_TRANSFORMS = ("resize_288", "resize_320_center")   # --transforms of a CNN arch (InferenceTransforms of the baseline)
+
+
 RESIZES = ("host", "hip")   # where decoded frames become model inputs: Pillow in the loader workers, or vsc_frame_inputs_u8
 
 
@@ -210,6 +238,18 @@ class ZipFrames(torch.utils.data.Dataset):
                 return torch.stack([self.transform(im) for im in images]), vid
             frames = [self.transform(Image.open(io.BytesIO(z.read(n)))) for n in sorted(z.namelist())]
         return torch.stack(frames), vid
+
+
+class RaggedZipFrames(ZipFrames):
+    """``ZipFrames`` for transforms that keep the aspect ratio (``sscd_transform_u8``): one item = (the video's transformed frames as
+    a LIST of uint8 [H_i, W_i, 3], video_id) for ``raw_collate`` -- nothing is stacked here, so the frames of a video may differ in
+    size (``src.extractor.extract_cnn_feat`` groups them by size)."""
+
+    def __getitem__(self, i):
+        from PIL import Image
+        vid = self.video_ids[i]
+        with ZipFile(self._path(vid), "r") as z:
+            return [self.transform(Image.open(io.BytesIO(z.read(n)))) for n in sorted(z.namelist())], vid
 
 
 class TensorFrames(torch.utils.data.Dataset):

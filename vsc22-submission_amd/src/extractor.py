@@ -59,6 +59,35 @@ def extract_vsc_feat_raw(model, batches: Iterable, device, image_size: int, resi
     return _extract(model, videos(), device, group_frames)
 
 
+def extract_cnn_feat(model, batches: Iterable, device) -> Tuple[List[str], np.ndarray, np.ndarray]:
+    """``extract_vsc_feat`` for a CNN encoder (vsc_hip.cnn_encoder.CnnHipEncoder), whose frames keep their own H x W: a loader
+    batch is a list of (frames, video_id) (``src.dataset.raw_collate``), frames a uint8 tensor [S, H, W, 3] or -- the transforms keep
+    the aspect ratio, so the frames of one video may differ in size -- a list of S tensors [H_i, W_i, 3].  All frames of a batch are
+    encoded per (H, W), one call per distinct size, and come back in the loader's order.  Same outputs as ``extract_vsc_feat``."""
+    feats, vids, stamps = [], [], []
+    for batch in batches:
+        sizes = {}
+        for i, (frames, _) in enumerate(batch):
+            for j, f in enumerate(frames):
+                sizes.setdefault(tuple(f.shape[:2]), []).append((i, j))
+        outs = [[None] * len(frames) for frames, _ in batch]
+        for where in sizes.values():
+            desc = model(torch.stack([batch[i][0][j] for i, j in where]).to(device, non_blocking=True)).cpu().numpy()
+            for row, (i, j) in zip(desc, where):
+                outs[i][j] = row
+        for i, (frames, v) in enumerate(batch):
+            c = len(frames)
+            vids.extend([v] * c)
+            stamps.append(np.arange(c))
+            if c:
+                feats.append(np.stack(outs[i]))
+    if not stamps:
+        return [], np.zeros((0, 0), np.float32), np.zeros((0,), np.int64)
+    if not feats:
+        return vids, np.zeros((0, 0), np.float32), np.concatenate(stamps)
+    return vids, np.concatenate(feats), np.concatenate(stamps)
+
+
 def _extract(model, batches: Iterable, device, group_frames: int) -> Tuple[List[str], np.ndarray, np.ndarray]:
     """batches yields one list of (video_id, valid frames) per loader batch"""
     from src.query_pipeline import encode_group

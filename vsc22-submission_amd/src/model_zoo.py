@@ -1,7 +1,7 @@
 """Checkpoint -> HIP encoder, shared by the extract_* entry points.
 
 A model is named ``arch:weights_format:checkpoint_path``: arch is a preset of vsc_hip.config (ViT family) or
-vsc_hip.swin_config (Swin-V2); weights_format says how the checkpoint's parameters are named."""
+vsc_hip.swin_config (Swin-V2) or vsc_hip.cnn_config (the SSCD ResNet-50); weights_format says how the checkpoint's parameters are named."""
 from __future__ import annotations
 
 from typing import Tuple
@@ -9,13 +9,16 @@ from typing import Tuple
 import torch
 
 from vsc_hip import weights as W
+from vsc_hip.cnn_config import CNN_PRESETS, get_cnn_config
+from vsc_hip.cnn_encoder import CnnHipEncoder
 from vsc_hip.config import PRESETS as VIT_PRESETS, aligned_batch, get_config
 from vsc_hip.encoder import HipEncoder
 from vsc_hip.swin_config import SWIN_PRESETS, get_swin_config
 from vsc_hip.swin_encoder import SwinHipEncoder, from_reference_state
 
 VIT_LOADERS = {"hf_vit": W.from_hf_vit, "timm_vit": W.from_timm_vit, "clip": W.from_clip_visual}
-WEIGHT_FORMATS = sorted(VIT_LOADERS) + ["swin_ref"]
+CNN_FORMAT = "sscd_torchvision"
+WEIGHT_FORMATS = sorted(VIT_LOADERS) + ["swin_ref", CNN_FORMAT]
 
 
 def _state_dict(path: str) -> dict:
@@ -39,8 +42,9 @@ DEFAULT_PRECISION = "fp16"   # of the infer/ entry points: the operand type whos
 
 
 def load_encoder(arch: str, weights_format: str, checkpoint_path: str, max_batch: int = None, u8_norm=None,
-                 precision: str = DEFAULT_PRECISION):
-    """-> (encoder, image_size).  ``u8_norm`` = (mean, std) applied to uint8 frames on the GPU (default 0.5 / 0.5, the
+                 precision: str = DEFAULT_PRECISION, l2_normalize: bool = True):
+    """-> (encoder, image_size); image_size is None for a CNN preset, whose frames keep their own H x W (``l2_normalize`` is
+    theirs alone: the original SSCD model's L2, or the adapted model's raw projection; u8_norm defaults to ImageNet's).  ``u8_norm`` = (mean, std) applied to uint8 frames on the GPU (default 0.5 / 0.5, the
     reference's vit_transform; pass dataset.CLIP_MEAN / CLIP_STD for the CLIP tower).  ``max_batch`` = None sizes the
     workspace for the architecture's tile-aligned batch (vsc_hip.config.aligned_batch).  ``precision``: "fp16" | "bf16" operands
     (vsc_hip.encoder.HipEncoder).
@@ -54,7 +58,16 @@ def load_encoder(arch: str, weights_format: str, checkpoint_path: str, max_batch
         deepest = max(range(cfg.stages), key=lambda st: cfg.depths[st])
         batch = max_batch or aligned_batch(cfg.resolution(deepest) ** 2)
         return SwinHipEncoder(cfg, from_reference_state(_state_dict(checkpoint_path)), max_batch=batch, **kw), cfg.image_size
+    if arch in CNN_PRESETS:
+        if weights_format != CNN_FORMAT:
+            raise ValueError(f"{arch} is a CNN preset: weights_format must be {CNN_FORMAT}, not {weights_format}")
+        cfg = get_cnn_config(arch)
+        if max_batch is not None:
+            kw["max_pixels"] = max_batch * 320 * 320
+        return CnnHipEncoder(cfg, W.from_sscd_torchvision(_state_dict(checkpoint_path), cfg), l2_normalize=l2_normalize, **kw), None
     if arch in VIT_PRESETS:
+        if weights_format == CNN_FORMAT:
+            raise ValueError(f"weights_format {CNN_FORMAT} belongs to the CNN presets {sorted(CNN_PRESETS)}, not to the ViT preset {arch}")
         if weights_format not in VIT_LOADERS:
             raise ValueError(f"{arch} is a ViT preset: weights_format must be one of {sorted(VIT_LOADERS)}")
         cfg = get_config(arch)

@@ -53,6 +53,16 @@ class SwinConfigC(ctypes.Structure):
     ]
 
 
+class CnnEncoderConfigC(ctypes.Structure):
+    _fields_ = [
+        ("stem_width", c_int32), ("widths", c_int32 * 4), ("depths", c_int32 * 4), ("head_in", c_int32), ("head_out", c_int32),
+        ("gem_p", c_float), ("l2", c_int32), ("max_pixels", c_int64),
+    ]
+
+
+CNN_PROF_CLASSES = ("stem_rows", "stem_conv", "maxpool", "stage0", "stage1", "stage2", "stage3", "pool_head")
+
+
 # name -> (restype, argtypes); also the list the symbol test checks against the header
 SIGNATURES = {
     "vsc_last_error": (c_char_p, []),
@@ -79,6 +89,19 @@ SIGNATURES = {
     "vsc_swin_workspace_bytes": (c_int64, [c_void_p]),
     "vsc_swin_set_profiling": (c_int32, [c_void_p, c_int32]),
     "vsc_swin_get_profile": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "vsc_cnn_encoder_create": (c_int32, [POINTER(CnnEncoderConfigC), POINTER(c_void_p)]),
+    "vsc_cnn_encoder_destroy": (None, [c_void_p]),
+    "vsc_cnn_encoder_set_weight": (c_int32, [c_void_p, c_char_p, c_void_p, c_size_t]),
+    "vsc_cnn_encoder_finalize": (c_int32, [c_void_p]),
+    "vsc_cnn_encoder_forward": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),       # (stream first)
+    "vsc_cnn_encoder_forward_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "vsc_cnn_encoder_workspace_bytes": (c_int64, [c_void_p]),
+    "vsc_cnn_encoder_set_profiling": (c_int32, [c_void_p, c_int32]),
+    "vsc_cnn_encoder_get_profile": (c_int32, [c_void_p, c_void_p, c_void_p]),
+    "vsc_conv2d_nhwc_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                       c_int32, c_int32, c_int32, c_int32]),
+    "vsc_maxpool3x3s2_nhwc_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32]),
+    "vsc_stem_rows_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "vsc_window_attention_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
                                             c_int32, c_int32, c_void_p]),
     "vsc_ln_residual_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,

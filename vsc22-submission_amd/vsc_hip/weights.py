@@ -18,6 +18,8 @@ Sources understood (model loading is host-side Python, as in the reference):
   * timm ``VisionTransformer`` (``blocks.N.attn.qkv`` ...), the ``vit_v68`` backbone.
   * the reference's CLIP tower (video/clip.py:98-110: ``conv1``,
     ``class_embedding``, ``transformer.resblocks.N.attn.in_proj_weight`` ...).
+  * the SSCD ResNet-50 in its torchvision form (``from_sscd_torchvision``): BatchNorm folded, names of
+    vsc_hip/cnn_config.py: ``cnn_weight_names``.
 """
 from __future__ import annotations
 
@@ -157,4 +159,50 @@ def from_clip_visual(state: dict, cfg) -> dict:
             }
             if rest in table:
                 out[f"blocks.{i}.{table[rest]}"] = v
+    return out
+
+
+def from_sscd_torchvision(state: dict, cfg) -> dict:
+    """The SSCD ResNet-50 checkpoint in its torchvision form (sscd_disc_mixup.torchvision.pt; infer/vsc/baseline/adapt_sscd_model.py)
+    -> the folded tensors of the CNN encoder: every BatchNorm goes into the convolution before it (float64 arithmetic, as
+    vsc_hip/cnn.py::_fold).  Names accepted: ``backbone.conv1`` / ``backbone.bn1``, ``backbone.layerL.B.convK`` / ``bnK`` /
+    ``downsample.{0,1}``; the head as ``embeddings.1.{weight,bias}`` (the original model) or ``project.{weight,bias}`` (an adapted
+    file).  A leading ``module.`` and / or ``model.`` (DataParallel, a wrapper module) is stripped.  BatchNorm's ``num_batches_tracked``
+    counters are the only names ignored; any other unmatched name, and any missing one,
+    is a ValueError that lists them."""
+    state = {re.sub(r"^(module\.)?(model\.)?", "", k): v for k, v in state.items() if not k.endswith("num_batches_tracked")}
+    used, missing, out = set(), [], {}
+
+    def take(name):
+        if name not in state:
+            missing.append(name)
+            return None
+        used.add(name)
+        return _np(state[name]).astype(np.float64)
+
+    def fold(conv, bn, dst):
+        w = take(conv + ".weight")
+        g, beta, mu, var = (take(f"{bn}.{k}") for k in ("weight", "bias", "running_mean", "running_var"))
+        if any(v is None for v in (w, g, beta, mu, var)):
+            return
+        s = g / np.sqrt(var + cfg.bn_eps)
+        out[dst + ".weight"] = (w * s[:, None, None, None]).astype(np.float32)
+        out[dst + ".bias"] = (beta - mu * s).astype(np.float32)
+
+    fold("backbone.conv1", "backbone.bn1", "conv1")
+    for s in range(4):
+        for b in range(cfg.depths[s]):
+            src, dst = f"backbone.layer{s + 1}.{b}.", f"layer{s + 1}.{b}."
+            for k in (1, 2, 3):
+                fold(f"{src}conv{k}", f"{src}bn{k}", f"{dst}conv{k}")
+            if b == 0:
+                fold(src + "downsample.0", src + "downsample.1", dst + "downsample")
+    head = "project" if "project.weight" in state else "embeddings.1"
+    for kind in ("weight", "bias"):
+        v = take(f"{head}.{kind}")
+        if v is not None:
+            out["head." + kind] = v.astype(np.float32)
+    stray = sorted(set(state) - used)
+    if missing or stray:
+        raise ValueError(f"sscd_torchvision state dict does not fit {cfg.name}: missing {sorted(missing)}, unmatched {stray}")
     return out
