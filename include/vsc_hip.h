@@ -1018,6 +1018,11 @@ typedef enum vsc_epilogue {
 int vsc_gemm_bf16(const uint16_t *a_dev, const uint16_t *w_dev, const float *bias_dev,
                   const float *aux_dev, void *out_dev, int64_t m, int32_t n, int32_t k,
                   int32_t epilogue, int32_t tokens, void *stream);
+/* The plan vsc_gemm_bf16 would execute for this shape and epilogue now -- on the current device, with the switches as they stand
+ * (csrc/gemm_plan.h); launches nothing and refuses what vsc_gemm_bf16 refuses of a shape.  out = { kernel, tiles_m, tiles_n,
+ * N-tiles per group, grid, block, dynamic LDS bytes, 0 }; kernel: 0 the 128 x 128 kernel, 1..4 the 256-row configurations A..D,
+ * 5 v3 (256 x 256, one tile per workgroup), 6 v4 (v3 persistent). */
+int vsc_gemm_plan(int64_t m, int32_t n, int32_t k, int32_t epilogue, int32_t out[8]);
 
 /* x_inout[M,N] += A[M,K] . W[N,K]^T + bias[N] (float32), y_out[M,N] = LayerNorm_row(x_inout) * gamma + beta in the operand type:
  * the residual GEMM of a transformer block and the LayerNorm behind it.  Where the persistent 256 x 256 kernel has that form

@@ -26,12 +26,29 @@ def _rand(seed, shape, std=1.0):
     return torch.from_numpy(synth.normalish(seed, shape, std))
 
 
+# the kernel each shape below relies on reaching, on 256 CUs (csrc/gemm_plan.h); every shape not named here makes fewer than 65 tiles
+# of 256 x 256 and runs the 128 x 128 kernel
+GEMM_KERNEL = {(5043, 2304, 768): "V3", (8448, 512, 256): "V2_C", (8448, 384, 256): "V2_D", (16640, 128, 512): "V2_B",
+               (8193, 1024, 768): "V3", (8449, 512, 192): "V2_C", (8448, 1024, 768): "V3", (43 * 196, 1024, 768): "V3"}
+
+
+def _on_its_kernel(m, n, k, epilogue):
+    """asked of the library before the case runs, so that a rule that moves cannot leave the test on another kernel unnoticed"""
+    from vsc_hip import ops
+    plan = ops.gemm_plan(m, n, k, epilogue)
+    assert plan["kernel"] == GEMM_KERNEL.get((m, n, k), "V1"), (m, n, k, plan)
+
+
 @pytest.mark.parametrize("m,n,k", [(128, 128, 64), (200, 132, 128), (1000, 768, 768),
                                    (5043, 2304, 768), (37, 512, 3072), (1, 4, 64),
-                                   # the short-K tile choices of launch_v2_pick: D (N % 256 = 128), C, B (N <= 128), ragged M
-                                   (1500, 384, 128), (2049, 512, 256), (1300, 128, 512), (1025, 1032, 192)])
+                                   # fewer than 65 tiles of 256 x 256: the 128 x 128 kernel, ragged in M and in N
+                                   (1500, 384, 128), (2049, 512, 256), (1300, 128, 512), (1025, 1032, 192),
+                                   # the smallest shapes that reach the 256-row configurations: 66 tiles C, 66 tiles D (N % 256 = 128),
+                                   # 65 tiles B (N <= 128), 132 tiles v3 (ragged M), C with ragged M and K % 128 != 0
+                                   (8448, 512, 256), (8448, 384, 256), (16640, 128, 512), (8193, 1024, 768), (8449, 512, 192)])
 def test_gemm_bf16_store(dev, m, n, k):
     from vsc_hip import ops, _lib
+    _on_its_kernel(m, n, k, _lib.EPI_BF16)
     a = _rand(1, (m, k)).to(torch.bfloat16)
     w = _rand(2, (n, k), 0.05).to(torch.bfloat16)
     b = _rand(3, (n,))
@@ -55,9 +72,10 @@ def test_gemm_is_not_transposed(dev):
 
 
 @pytest.mark.parametrize("epi", ["gelu", "qgelu"])
-@pytest.mark.parametrize("m,n,k", [(300, 512, 128), (1333, 512, 128), (1100, 3072, 768)])
+@pytest.mark.parametrize("m,n,k", [(300, 512, 128), (1333, 512, 128), (1100, 3072, 768), (8448, 1024, 768), (8448, 512, 256)])
 def test_gemm_activation_epilogues(dev, epi, m, n, k):
     from vsc_hip import ops, _lib
+    _on_its_kernel(m, n, k, _lib.EPI_GELU_BF16 if epi == "gelu" else _lib.EPI_QGELU_BF16)
     a = _rand(4, (m, k)).to(torch.bfloat16)
     w = _rand(5, (n, k), 0.1).to(torch.bfloat16)
     b = _rand(6, (n,), 0.1)
@@ -70,9 +88,10 @@ def test_gemm_activation_epilogues(dev, epi, m, n, k):
     torch.testing.assert_close(out, ref, rtol=2 ** -7, atol=2e-3)
 
 
-@pytest.mark.parametrize("m,n,k", [(517, 768, 3072), (1300, 768, 768), (1100, 512, 256)])
+@pytest.mark.parametrize("m,n,k", [(517, 768, 3072), (1300, 768, 768), (1100, 512, 256), (8448, 1024, 768), (8448, 512, 256)])
 def test_gemm_residual_epilogue_in_place(dev, m, n, k):
     from vsc_hip import ops, _lib
+    _on_its_kernel(m, n, k, _lib.EPI_RESADD_F32)
     a = _rand(7, (m, k)).to(torch.bfloat16)
     w = _rand(8, (n, k), 0.02).to(torch.bfloat16)
     b = _rand(9, (n,), 0.1)
@@ -93,7 +112,9 @@ def test_gemm_residual_epilogue_in_place(dev, m, n, k):
                                    (70000, 512, 128)])           # K = 128: two K-tiles per output tile, every one of them stages the next tile (Swin stage-1 shapes)
 def test_gemm_persistent_kernel_equals_one_tile_per_workgroup(dev, epi, m, n, k):
     """v4 (persistent: the operand ring streams across output tiles, write-out through 4 KiB per wave) runs the same
-    MFMA chain and the same epilogue arithmetic as v3 -> identical bits; v3 itself is checked against fp32 above."""
+    MFMA chain and the same epilogue arithmetic as v3 -> identical bits; v3 itself is checked against fp32 above, for every
+    epilogue (the cases of test_gemm_bf16_store, test_gemm_activation_epilogues and test_gemm_residual_epilogue_in_place that
+    name V3)."""
     import os
     from vsc_hip import ops, _lib
     kind = {"bf16": _lib.EPI_BF16, "gelu": _lib.EPI_GELU_BF16, "qgelu": _lib.EPI_QGELU_BF16, "resadd": _lib.EPI_RESADD_F32,
@@ -142,9 +163,12 @@ def test_gemm_persistent_kernel_without_bias(dev):
     torch.testing.assert_close(y[rows], x[rows] + a[rows].float() @ w.float().t(), rtol=1e-4, atol=2e-3)
 
 
-def test_gemm_patch_epilogue(dev):
+# 3 x 16 patches on the 128 x 128 kernel; 43 frames of 196: 132 tiles, the patch epilogue -- which the persistent kernel does not
+# serve -- on v3
+@pytest.mark.parametrize("frames,tokens,n,k", [(3, 17, 128, 768), (43, 197, 1024, 768)])
+def test_gemm_patch_epilogue(dev, frames, tokens, n, k):
     from vsc_hip import ops, _lib
-    frames, tokens, n, k = 3, 17, 128, 768
+    _on_its_kernel(frames * (tokens - 1), n, k, _lib.EPI_PATCH_F32)
     a = _rand(11, (frames * (tokens - 1), k)).to(torch.bfloat16)
     w = _rand(12, (n, k), 0.03).to(torch.bfloat16)
     b = _rand(13, (n,), 0.1)

@@ -66,6 +66,10 @@ int vsc_opt_int(VscOpt o, int dflt) {
     const char *e = vsc_opt(o);
     return e ? atoi(e) : dflt;
 }
+void vsc_opt_read(const VscOpt *which, int n, const char **values) {
+    std::call_once(g_opt_once, opt_load_env);
+    for (int i = 0; i < n; ++i) values[i] = g_opt_values[which[i]].load(std::memory_order_acquire);
+}
 // value == NULL (or "") clears the switch.  Superseded strings are not freed: a reader may still hold them, and switches
 // change a handful of times per process (tests, A/B tools).
 extern "C" int vsc_set_option(const char *name, const char *value) {

@@ -68,6 +68,8 @@ enum VscOpt {
 const char *vsc_opt(VscOpt o);   // value of VSC_<name> (environment at first use, or the last vsc_set_option), nullptr when unset
 bool vsc_opt_is(VscOpt o, char c);     // set, and its first character is c ('0' = off, '1' = on for most switches)
 int vsc_opt_int(VscOpt o, int dflt);   // atoi of the value, dflt when unset
+// the values of n switches in one call (a launch path that reads many: one pass over the table instead of n look-ups)
+void vsc_opt_read(const VscOpt *which, int n, const char **values);
 
 // ---- per-device launch plumbing (capi.hip) ---------------------------------------------------------
 // One copy for the whole library, callable from several threads, valid for any device ordinal.  Both return VSC_OK or

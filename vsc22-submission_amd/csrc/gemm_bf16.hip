@@ -31,6 +31,7 @@
 
 #include "common.h"
 #include "gelu_poly.h"
+#include "gemm_plan.h"
 #include "ln_row.h"
 #include "mainloop64.h"
 
@@ -59,11 +60,18 @@ struct GemmArgs {
     GemmExtra ex;  // LayerNorm-folding operands (common.h)
 };
 
-constexpr bool epi_bf16_out(int e) {
-    return e == VSC_EPI_BF16 || e == VSC_EPI_GELU_BF16 || e == VSC_EPI_QGELU_BF16 || e == VSC_EPI_LNF_BF16 ||
-           e == VSC_EPI_LNF_GELU_BF16 || e == VSC_EPI_LNF_QGELU_BF16;
-}
-constexpr bool epi_lnf(int e) { return e >= VSC_EPI_LNF_BF16 && e <= VSC_EPI_LNF_QGELU_BF16; }
+// the epilogue classes the choice of kernel depends on live with it (gemm_plan.h), by number
+using gemmplan::epi_bf16_out;
+using gemmplan::epi_lnf;
+using gemmplan::epi_v4;
+using gemmplan::GemmPlan;
+using gemmplan::GemmSwitches;
+static_assert(gemmplan::EPI_BF16 == VSC_EPI_BF16 && gemmplan::EPI_GELU_BF16 == VSC_EPI_GELU_BF16 && gemmplan::EPI_QGELU_BF16 == VSC_EPI_QGELU_BF16 &&
+              gemmplan::EPI_RESADD_F32 == VSC_EPI_RESADD_F32 && gemmplan::EPI_PATCH_F32 == VSC_EPI_PATCH_F32 && gemmplan::EPI_F32 == VSC_EPI_F32 &&
+              gemmplan::EPI_LNF_BF16 == VSC_EPI_LNF_BF16 && gemmplan::EPI_LNF_GELU_BF16 == VSC_EPI_LNF_GELU_BF16 &&
+              gemmplan::EPI_LNF_QGELU_BF16 == VSC_EPI_LNF_QGELU_BF16 && gemmplan::EPI_RESADD_STATS_F32 == VSC_EPI_RESADD_STATS_F32 &&
+              gemmplan::EPI_LN_RES_F32 == VSC_EPI_LN_RES_F32 && gemmplan::EPI_RESADD_LN_F32 == VSC_EPI_RESADD_LN_F32 &&
+              gemmplan::RING_BYTES == ml64::RING_BYTES, "gemm_plan.h and the library disagree");
 constexpr bool epi_gelu(int e) { return e == VSC_EPI_GELU_BF16 || e == VSC_EPI_LNF_GELU_BF16; }
 constexpr bool epi_qgelu(int e) { return e == VSC_EPI_QGELU_BF16 || e == VSC_EPI_LNF_QGELU_BF16; }
 
@@ -736,23 +744,40 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_v3_kernel(GemmArgs p) {
     epilogue_via_lds<EPI, TM, TN>(p, acc, lds2, wave, lane, wm, wn, m0, n0, rs, bzp, csp);
 }
 
+// ---- launchers: one per kernel generation, each executes a GemmPlan (gemm_plan.h) and recomputes none of its numbers ------------
+// (p: the caller's own arguments, completed in place from the plan -- nothing is copied on the way to the launch)
+inline void apply_plan(GemmArgs &p, const GemmPlan &pl) {
+    p.tiles_m = pl.tiles_m;
+    p.tiles_n = pl.tiles_n;
+    p.group_n = pl.group_n;
+    p.skew = pl.skew;
+}
+
+#ifdef VSC_GEMM_TIMING
+// host half of the instrumented build: a zeroed counter block for the launch, and its values once the launch is done
+inline int gemm_timing_begin(GemmArgs &p, hipStream_t stream) {
+    static unsigned long long *dbg = nullptr;
+    if (!dbg) VSC_CHECK_HIP(hipMalloc(&dbg, 64 * 8));
+    VSC_CHECK_HIP(hipMemsetAsync(dbg, 0, 64 * 8, stream));
+    p.dbg = dbg;
+    return VSC_OK;
+}
+// -> *print: VSC_GEMM_TIMING_PRINT is set and h holds the `count` counters at `dev`
+inline int gemm_timing_read(unsigned long long *h, int count, const void *dev, hipStream_t stream, bool *print) {
+    *print = vsc_opt(OPT_GEMM_TIMING_PRINT) != nullptr;
+    if (!*print) return VSC_OK;
+    VSC_CHECK_HIP(hipStreamSynchronize(stream));
+    VSC_CHECK_HIP(hipMemcpy(h, dev, (size_t)count * 8, hipMemcpyDeviceToHost));
+    return VSC_OK;
+}
+#endif
+
 template <int EPI>
-int launch_v3(GemmArgs p, hipStream_t stream) {
-    constexpr int smem = ml64::RING_BYTES + 4096;   // ring (== 8 waves x 16 KiB of write-out staging) + the epilogue constants
+int launch_v3(GemmArgs &p, const GemmPlan &pl, hipStream_t stream) {
     auto kern = gemm_bf16_v3_kernel<EPI>;
-    VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
-    p.tiles_m = (int)((p.m + 255) / 256);
-    p.tiles_n = (p.n + 255) / 256;
-    // N-group width (tile order): groups of 4 N-tiles whatever K is.  Swept on the ViT shapes with this loop (G = 1..12,
-    // gpurun_out/gemm_ab_groups.txt -> profiles/r02_gemm_ab_groups.txt): 4 is fastest for qkv / fc1, equal for the
-    // N = 768 GEMMs (3 N-tiles: one group), and the L2-capacity rule of v2 picked 1 at K = 8192 (1186 vs 1561 TF/s).
-    // groups of 4 N-tiles; of 3 where that divides the row of tiles and 4 does not (qkv: 9 = 3 + 3 + 3 instead of 4 + 4 + 1:
-    // 204 -> 199.5 us on the persistent kernel, tools/micro/gemm_v4_groups.py)
-    int g = (p.tiles_n % 4 != 0 && p.tiles_n % 3 == 0) ? 3 : 4;
-    g = vsc_opt_int(OPT_GEMM_GROUP_N, g);
-    p.group_n = g < 1 ? 1 : (g > p.tiles_n ? p.tiles_n : g);
-    p.skew = 0;
-    hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(512), smem, stream, p);
+    VSC_TRY(vsc_allow_dynamic_lds(kern, gemmplan::V3_LDS_BYTES));
+    apply_plan(p, pl);
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.grid), dim3(pl.block), pl.lds_bytes, stream, p);
     VSC_CHECK_LAUNCH();
     return VSC_OK;
 }
@@ -765,10 +790,7 @@ int launch_v3(GemmArgs p, hipStream_t stream) {
 // (slots 6, 7: 4 KiB per wave) in passes of 32 (bf16) / 16 (fp32) rows, with the next tile's first six units in flight;
 // the per-tile bias sits in a double-buffered 1-KiB row behind the ring, fetched during the previous write-out.
 // Serves the plain, GELU and residual epilogues; K % 128 == 0 (an even number of K-tiles), K >= 256.
-constexpr bool epi_v4(int e) {
-    return e == VSC_EPI_BF16 || e == VSC_EPI_GELU_BF16 || e == VSC_EPI_QGELU_BF16 || e == VSC_EPI_RESADD_F32 || e == VSC_EPI_F32 ||
-           e == VSC_EPI_LN_RES_F32 || epi_lnf(e) || e == VSC_EPI_RESADD_STATS_F32 || e == VSC_EPI_RESADD_LN_F32;
-}
+// (which epilogues: epi_v4, gemm_plan.h)
 
 #ifdef VSC_GEMM_TIMING
 static __device__ unsigned long long g_v4_t_mid[16];   // (per-wave scratch of the instrumented build; racy by design, read by the same wave)
@@ -1357,25 +1379,15 @@ __global__ __launch_bounds__(512, 2) void gemm_bf16_v4_kernel(GemmArgs p) {
 }
 
 template <int EPI>
-int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
-    constexpr int smem_tail = EPI == VSC_EPI_RESADD_LN_F32 ? 64 + 2 * 768 * 4 : 0;   // the claim word and gamma | beta behind the bias rows
-    constexpr int smem_max = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + 12 * 2048 : 2048 + smem_tail);
-    const int smem = ml64::RING_BYTES + (epi_lnf(EPI) ? 2 * 2048 + 2048 + p.ex.nslices * 2048 : 2048 + smem_tail);
+int launch_v4(GemmArgs &p, const GemmPlan &pl, hipStream_t stream) {
+    const int cus = (int)pl.grid;
     auto kern = gemm_bf16_v4_kernel<EPI>;
-    VSC_TRY(vsc_allow_dynamic_lds(kern, smem_max));
-    // groups of 4 N-tiles; of 3 where that divides the row of tiles and 4 does not (qkv: 9 = 3 + 3 + 3 instead of 4 + 4 + 1:
-    // 204 -> 199.5 us on the persistent kernel, tools/micro/gemm_v4_groups.py)
-    int g = (p.tiles_n % 4 != 0 && p.tiles_n % 3 == 0) ? 3 : 4;
-    g = vsc_opt_int(OPT_GEMM_GROUP_N, g);
-    p.group_n = g < 1 ? 1 : (g > p.tiles_n ? p.tiles_n : g);
-    p.skew = 0;
+    VSC_TRY(vsc_allow_dynamic_lds(kern, gemmplan::v4_lds_bytes(EPI, gemmplan::V4_MAX_SLICES)));
+    apply_plan(p, pl);
     p.skew_groups = 1;
-    if (EPI == VSC_EPI_RESADD_LN_F32) p.group_n = p.tiles_n;   // a row block's tiles are consecutive tile indices (no diagnostic regrouping)
     constexpr bool pair_exchange = EPI == VSC_EPI_LN_RES_F32;
     if (pair_exchange) {
-        // the row's two tiles (t, t ^ 1) must land on workgroups (b, b ^ 8) of the same round: N-groups spanning the whole row
-        // of tiles, no diagnostic regrouping, one workgroup on every CU, whole pairs per round
-        p.group_n = p.tiles_n;
+        // (the plan's N-group spans the whole row of tiles) ... one workgroup on every CU, whole pairs per round
         int dev_cus = 0;
         VSC_TRY(vsc_device_cus(&dev_cus));
         // (grid < CUs -- the VSC_GEMM_V4_GRID diagnostic -- keeps every workgroup resident as well; the exchange slots are sized for 256)
@@ -1391,18 +1403,15 @@ int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
         }
     }
 #ifdef VSC_GEMM_TIMING
-    static unsigned long long *dbg = nullptr;
-    if (!dbg) VSC_CHECK_HIP(hipMalloc(&dbg, 64 * 8));
-    VSC_CHECK_HIP(hipMemsetAsync(dbg, 0, 64 * 8, stream));
-    p.dbg = dbg;
+    VSC_TRY(gemm_timing_begin(p, stream));
 #endif
-    hipLaunchKernelGGL(kern, dim3(cus), dim3(512), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3(cus), dim3(pl.block), pl.lds_bytes, stream, p);
     VSC_CHECK_LAUNCH();
 #ifdef VSC_GEMM_TIMING
-    if (vsc_opt(OPT_GEMM_TIMING_PRINT)) {
-        unsigned long long h[64];
-        VSC_CHECK_HIP(hipStreamSynchronize(stream));
-        VSC_CHECK_HIP(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+    unsigned long long h[64];
+    bool print = false;
+    VSC_TRY(gemm_timing_read(h, 64, p.dbg, stream, &print));
+    if (print) {
         for (int g = 0; g < 2; ++g) {
             const unsigned long long *t = h + g * 32;
             fprintf(stderr, "v4 timing m=%lld n=%d k=%d epi=%d wave %d (10 ns ticks from kernel start):", (long long)p.m, p.n, p.k, EPI, g * 4);
@@ -1416,94 +1425,23 @@ int launch_v4(GemmArgs p, int cus, hipStream_t stream) {
     return VSC_OK;
 }
 
-// the shapes the persistent kernel takes (p.tiles_m / p.tiles_n: 256 x 256 tiles)
-inline bool v4_shape_ok(const GemmArgs &p, int cus, bool bf16_out) {
-    const int64_t a_span = (int64_t)p.tiles_m * 256 * p.k * 2, w_span = (int64_t)p.tiles_n * 256 * p.k * 2;
-    // (K > 3072: the per-tile costs v4 removes are < 1 % of a tile and its lockstep costs ~3 % -- 8192^3 680 vs 701 us)
-    // fp32 write-outs address [m, n] by 32-bit byte offsets from the matrix origin, rows of the last (ragged) tile included
-    const bool out_span_ok = (int64_t)p.tiles_m * 256 * p.n * (bf16_out ? 2 : 4) < (1ll << 32);
-    return p.k % 128 == 0 && p.k >= 128 && p.k <= 3072 && cus % 8 == 0 && (int64_t)p.tiles_m * p.tiles_n > cus && a_span < (1ll << 32) &&
-           w_span < (1ll << 32) && out_span_ok;
-}
-
-// v3 or its persistent form: v4 wherever a workgroup gets more than one tile and the 32-bit source offsets hold
-template <int EPI>
-int launch_v34(GemmArgs p, hipStream_t stream) {
-    p.tiles_m = (int)((p.m + 255) / 256);
-    p.tiles_n = (p.n + 255) / 256;
-    if constexpr (epi_v4(EPI)) {
-        const bool off = vsc_opt_is(OPT_GEMM_V4, '0');   // diagnostic A/B switch, read per launch
-        int cus = 0;
-        VSC_TRY(vsc_device_cus(&cus));
-        if (!off && v4_shape_ok(p, cus, epi_bf16_out(EPI)) && (EPI != VSC_EPI_RESADD_F32 || p.aux) &&
-            (!epi_lnf(EPI) || p.m * 8 < (1ll << 32)))
-        {
-            int grid = cus;
-            // diagnostic: persistent workgroups per launch (a multiple of 8).  Measured with two lanes, so that the two chunks' GEMMs run
-            // side by side on half the chip each instead of one after the other: 128 -> 23.4 k, 192 -> 23.4 k, 256 -> 23.9 k frames/s
-            const int g = vsc_opt_int(OPT_GEMM_V4_GRID, 0);
-            if (g >= 8 && g <= cus && g % 8 == 0) grid = g;
-            if constexpr (epi_lnf(EPI)) {
-                // statistics given as slice partials: merged per tile inside the kernel when they fit behind the ring (<= 12 slices)
-                if (p.ex.slices && p.ex.nslices > 12) {
-                    int rc = launch_ln_stats_merge(p.ex.slices, const_cast<float *>(p.ex.rowstats), p.m, p.ex.nslices, p.k, p.ex.eps, stream);
-                    if (rc) return rc;
-                    p.ex.nslices = 0;
-                } else if (!p.ex.slices) {
-                    p.ex.nslices = 0;
-                }
-            }
-            return launch_v4<EPI>(p, grid, stream);
-        }
-    }
-    if constexpr (epi_lnf(EPI)) {
-        if (p.ex.slices) {
-            int rc = launch_ln_stats_merge(p.ex.slices, const_cast<float *>(p.ex.rowstats), p.m, p.ex.nslices, p.k, p.ex.eps, stream);
-            if (rc) return rc;
-        }
-        p.ex.nslices = 0;
-    }
-    return launch_v3<EPI>(p, stream);
-}
-
-// first-round start skew (diagnostic, off by default): VSC_GEMM_SKEW_NS_PER_K * K / 10 shader cycles spread over the
-// first 256 workgroups.  Re-measured in the ViT step with skews from 0.6 us to a whole tile time: 0 is as fast as any
-// (19.7 k frames/s), a tile time costs 6 % -- the start-up delay is never recovered.
-inline int skew_cycles(int k) {
-    return (int)((int64_t)vsc_opt_int(OPT_GEMM_SKEW_NS_PER_K, 0) * k / 10);
-}
-
-template <int EPI, int WAVES_M, int WAVES_N, int TM, int TN, int STAGES>
-int launch_v2(GemmArgs p, hipStream_t stream) {
-    constexpr int BM2 = WAVES_M * TM * 16, BN2 = WAVES_N * TN * 16;
-    constexpr int NW = WAVES_M * WAVES_N;
-    constexpr int ring = STAGES * (BM2 + BN2) * 64;
-    constexpr int smem = ring > NW * 16384 ? ring : NW * 16384;
-    auto kern = gemm_bf16_v2_kernel<EPI, WAVES_M, WAVES_N, TM, TN, STAGES>;
-    VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
-    p.tiles_m = (int)((p.m + BM2 - 1) / BM2);
-    p.tiles_n = (p.n + BN2 - 1) / BN2;
-    // W panel of one N-group (G tiles x K) should sit in a 4 MiB XCD L2 next to the A panels: every N-group is one
-    // more pass over A.  With few N tiles the whole width is one group whatever K is -- fc2 (N = 768, K = 3072) ran
-    // 3 passes over its 402 MB A (larger than the Infinity Cache) under the L2 rule: 395 -> 330 us with one.
-    int g = (int)((int64_t)(3 << 19) / ((int64_t)BN2 * p.k * 2));
-    if (p.tiles_n <= 4) g = p.tiles_n;
-    g = vsc_opt_int(OPT_GEMM_GROUP_N, g);
-    p.group_n = g < 1 ? 1 : (g > p.tiles_n ? p.tiles_n : g);
-    p.skew = skew_cycles(p.k);
+template <int EPI, int KERNEL>
+int launch_v2(GemmArgs &p, const GemmPlan &pl, hipStream_t stream) {
+    constexpr gemmplan::V2Config c = gemmplan::v2_config(KERNEL);
+    [[maybe_unused]] constexpr int NW = c.waves();   // (the instrumented build prints per wave)
+    auto kern = gemm_bf16_v2_kernel<EPI, c.waves_m, c.waves_n, c.tm, c.tn, c.stages>;
+    VSC_TRY(vsc_allow_dynamic_lds(kern, c.lds_bytes()));
+    apply_plan(p, pl);
 #ifdef VSC_GEMM_TIMING
-    static unsigned long long *dbg = nullptr;
-    if (!dbg) VSC_CHECK_HIP(hipMalloc(&dbg, 64 * 8));
-    VSC_CHECK_HIP(hipMemsetAsync(dbg, 0, 64 * 8, stream));
-    p.dbg = dbg;
+    VSC_TRY(gemm_timing_begin(p, stream));
 #endif
-    hipLaunchKernelGGL(kern, dim3(p.tiles_m * p.tiles_n), dim3(NW * 64), smem, stream, p);
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.grid), dim3(pl.block), pl.lds_bytes, stream, p);
     VSC_CHECK_LAUNCH();
 #ifdef VSC_GEMM_TIMING
-    if (vsc_opt(OPT_GEMM_TIMING_PRINT)) {
-        unsigned long long h[64];
-        VSC_CHECK_HIP(hipStreamSynchronize(stream));
-        VSC_CHECK_HIP(hipMemcpy(h, dbg, sizeof(h), hipMemcpyDeviceToHost));
+    unsigned long long h[64];
+    bool print = false;
+    VSC_TRY(gemm_timing_read(h, 64, p.dbg, stream, &print));
+    if (print) {
         const double nk = p.k / 32.0;
         for (int w = 0; w < NW; ++w)
             fprintf(stderr, "timing m=%lld n=%d k=%d wave %d: per K-step cycles  dma-issue %.0f  reads+landing %.0f  barrier-L %.0f  mfma-issue %.0f  barrier-C %.0f\n",
@@ -1514,52 +1452,56 @@ int launch_v2(GemmArgs p, hipStream_t stream) {
     return VSC_OK;
 }
 
-
-
+// The (kernel, epilogue) pairs that exist: V1 and the configurations B, C, D for the public kinds, A and v3 for every kind of
+// launch_gemm_bf16_ex, v4 for every kind but PATCH.
 template <int EPI>
-int launch_v2_pick(const GemmArgs &p, hipStream_t stream) {
-    // wide N: 256x256 tile; N <= 1024 (proj / fc2 / patch): 256x128 so the grid still fills 256 CUs
-    // A: 8 waves 256x256 (1 block/CU)   B: 8 waves 256x128
-    // C: 4 waves 128x256 (2 blocks/CU)  D: 4 waves 256x128 (2 blocks/CU)
-    // Tried and dropped: 64-k stages with full 128-B line fetches (+0.6 %),
-    // a 5-deep ring (+0.4 %), register staging instead of LDS-DMA (0.47x, spills), issuing the
-    // LDS-DMA between the MFMA rows of the C phase (-1 %), hybrid staging with A by LDS-DMA and W
-    // through registers (-3 %), an intra-wave software pipeline (A fragments refilled from the next stage right
-    // after their MFMA group, W fragments double-buffered, one barrier per K-step: equal with DMA, 0.79x with DMA
-    // off -- anything issued between back-to-back MFMAs costs more than the phase barriers it removes), a
-    // persistent workgroup per CU with a 3-stage ring and the write-out staged behind it so the next tile's first
-    // stages fly during the write-out (+-1 %: launch, fill and drain were already hidden; 3 stages are as fast
-    // as 4).  tools/micro/fill_bench.hip: LDS-DMA alone delivers 21.6 B/clk/CU with 64-B row pieces (34-40 with
-    // full 128-B lines), VGPR staging no more; the K loop is issue/phase-bound, not delivery-bound.
-    const char *force = vsc_opt(OPT_GEMM_CFG);   // diagnostic, read per launch
-    // measured: A wins on every ViT shape (K >= 768).  With K <= 512 (Swin) the K loop is only 4-16 stages long and
-    // the epilogue is a large share of a tile: the 4-wave tiles run two workgroups per CU, so one's write-out
-    // overlaps the other's K loop (stage-3 qkv 765 -> 875 TF/s); D when N is a multiple of 128 but not of 256.
-    char cfg = p.n > 128 ? 'A' : 'B';
-    if (p.k <= 512 && p.n > 128) {
-        cfg = (p.n % 256 != 0 && p.n % 128 == 0) ? 'D' : 'C';
-        // ... unless the persistent kernel takes it (v4: K = 256 / 384 / 512, more 256 x 256 tiles than CUs): without the per-tile
-        // launch / prologue / drain the big tile wins here too (Swin-V2-B batch 256: 12.15 k -> 12.95 k frames/s)
-        if (epi_v4(EPI) && p.k % 128 == 0 && p.k >= 128 && p.n % 256 == 0 && ((p.m + 255) / 256) * (p.n / 256) > 256) cfg = 'A';
+int launch_v1(GemmArgs &p, const GemmPlan &pl, hipStream_t stream) {
+    if constexpr (EPI <= VSC_EPI_F32) {
+        apply_plan(p, pl);
+        hipLaunchKernelGGL(gemm_bf16_kernel<EPI>, dim3((unsigned)pl.grid), dim3(pl.block), 0, stream, p);
+        VSC_CHECK_LAUNCH();
+        return VSC_OK;
     }
-    if (force) cfg = force[0];
-    const bool no_v3 = vsc_opt_is(OPT_GEMM_V3, '0');   // diagnostic A/B switch, read per launch
-    if (cfg == 'A' && p.k % 64 == 0 && !no_v3) return launch_v34<EPI>(p, stream);
-    switch (cfg) {
-        case 'A': return launch_v2<EPI, 2, 4, 8, 4, 4>(p, stream);
-        case 'B': return launch_v2<EPI, 4, 2, 4, 4, 4>(p, stream);
-        case 'C': return launch_v2<EPI, 1, 4, 8, 4, 3>(p, stream);
-        default: return launch_v2<EPI, 2, 2, 8, 4, 3>(p, stream);
-    }
+    VSC_REQUIRE(false, "gemm: no kernel %d for epilogue %d", pl.kernel, EPI);
 }
 
+// a plan of the 256-row family on its kernel (the kernels stand in the code object in the order of these cases)
 template <int EPI>
-int launch_t(const GemmArgs &p, int tiles_m, hipStream_t stream) {
-    hipLaunchKernelGGL(gemm_bf16_kernel<EPI>, dim3(tiles_m * p.tiles_n), dim3(256), 0, stream, p);
-    VSC_CHECK_LAUNCH();
-    return VSC_OK;
+int launch_256(GemmArgs &p, const GemmPlan &pl, hipStream_t stream) {
+    constexpr bool is_public = EPI <= VSC_EPI_F32;
+    if constexpr (epi_lnf(EPI)) {
+        if (pl.merge_first) VSC_TRY(launch_ln_stats_merge(p.ex.slices, const_cast<float *>(p.ex.rowstats), p.m, p.ex.nslices, p.k, p.ex.eps, stream));
+        p.ex.nslices = pl.kernel_slices;
+    }
+    switch (pl.kernel) {
+        case gemmplan::V4: if constexpr (epi_v4(EPI)) return launch_v4<EPI>(p, pl, stream); break;
+        case gemmplan::V3: return launch_v3<EPI>(p, pl, stream);
+        case gemmplan::V2_A: return launch_v2<EPI, gemmplan::V2_A>(p, pl, stream);
+        case gemmplan::V2_B: if constexpr (is_public) return launch_v2<EPI, gemmplan::V2_B>(p, pl, stream); break;
+        case gemmplan::V2_C: if constexpr (is_public) return launch_v2<EPI, gemmplan::V2_C>(p, pl, stream); break;
+        case gemmplan::V2_D: if constexpr (is_public) return launch_v2<EPI, gemmplan::V2_D>(p, pl, stream); break;
+        default: break;
+    }
+    VSC_REQUIRE(false, "gemm: no kernel %d for epilogue %d", pl.kernel, EPI);
 }
 
+// the one switch over the epilogue: f(std::integral_constant<int, EPI>) for the kind's number
+template <class F>
+int with_epilogue(int epilogue, F &&f) {
+    switch (epilogue) {
+        case VSC_EPI_BF16: return f(std::integral_constant<int, VSC_EPI_BF16>{});
+        case VSC_EPI_GELU_BF16: return f(std::integral_constant<int, VSC_EPI_GELU_BF16>{});
+        case VSC_EPI_QGELU_BF16: return f(std::integral_constant<int, VSC_EPI_QGELU_BF16>{});
+        case VSC_EPI_RESADD_F32: return f(std::integral_constant<int, VSC_EPI_RESADD_F32>{});
+        case VSC_EPI_PATCH_F32: return f(std::integral_constant<int, VSC_EPI_PATCH_F32>{});
+        case VSC_EPI_F32: return f(std::integral_constant<int, VSC_EPI_F32>{});
+        case VSC_EPI_LNF_BF16: return f(std::integral_constant<int, VSC_EPI_LNF_BF16>{});
+        case VSC_EPI_LNF_GELU_BF16: return f(std::integral_constant<int, VSC_EPI_LNF_GELU_BF16>{});
+        case VSC_EPI_LNF_QGELU_BF16: return f(std::integral_constant<int, VSC_EPI_LNF_QGELU_BF16>{});
+        case VSC_EPI_RESADD_STATS_F32: return f(std::integral_constant<int, VSC_EPI_RESADD_STATS_F32>{});
+        default: VSC_REQUIRE(false, "gemm: unknown epilogue %d", epilogue);
+    }
+}
 
 // ---------------------------------------------------------------------------------------------
 // gemm_ln: out rows are OWNED by one workgroup (BN == N), so the res-post-norm update of Swin-V2
@@ -1800,22 +1742,21 @@ __global__ __launch_bounds__(512, 2) void gemm_ln_kernel(GemmLnArgs p) {
 #endif
 }
 
-template <int WAVES_M, int WAVES_N, int STAGES>
-int launch_ln_t(const GemmLnArgs &p, hipStream_t stream) {
-    // the write-out regions + row-statistic partials alias the ring once the K loop is done
-    constexpr int ring = STAGES * (WAVES_M * 64 + WAVES_N * 128) * 64;
-    constexpr int smem = ring > 8 * 16384 + 8192 ? ring : 8 * 16384 + 8192;
-    auto kern = gemm_ln_kernel<WAVES_M, WAVES_N, STAGES>;
-    VSC_TRY(vsc_allow_dynamic_lds(kern, smem));
-    const int64_t blocks = (p.m + WAVES_M * 64 - 1) / (WAVES_M * 64);
-    VSC_REQUIRE(blocks < (1ll << 31), "gemm_ln: grid too large");
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(512), smem, stream, p);
+template <int KERNEL>
+int launch_ln_row(const GemmLnArgs &p, const GemmPlan &pl, hipStream_t stream) {
+    constexpr gemmplan::LnRowConfig c = gemmplan::ln_row_config(KERNEL);
+    auto kern = gemm_ln_kernel<c.waves_m, c.waves_n, c.stages>;
+    VSC_TRY(vsc_allow_dynamic_lds(kern, c.lds_bytes()));
+    VSC_REQUIRE(pl.grid < (1ll << 31), "gemm_ln: grid too large");
+    hipLaunchKernelGGL(kern, dim3((unsigned)pl.grid), dim3(pl.block), pl.lds_bytes, stream, p);
     VSC_CHECK_LAUNCH();
 #ifdef VSC_GEMM_TIMING
-    if (vsc_opt(OPT_GEMM_TIMING_PRINT)) {
-        unsigned long long h[8];
-        VSC_CHECK_HIP(hipStreamSynchronize(stream));
-        VSC_CHECK_HIP(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_ln_dbg), sizeof(h)));
+    unsigned long long h[8];
+    bool print = false;
+    void *dbg = nullptr;
+    VSC_CHECK_HIP(hipGetSymbolAddress(&dbg, HIP_SYMBOL(g_ln_dbg)));
+    VSC_TRY(gemm_timing_read(h, 8, dbg, stream, &print));
+    if (print) {
         fprintf(stderr, "timing gemm_ln m=%lld n=%d k=%d (%d K-steps): prologue %llu  K loop %llu (%.0f per step)  LN + write-out %llu ticks (statistics + normalise %llu)\n",
                 (long long)p.m, p.n, p.k, p.k / 32, h[0], h[1], (double)h[1] / (p.k / 32), h[2], h[3]);
     }
@@ -1832,25 +1773,68 @@ int launch_gemm_bf16(const uint16_t *a, const uint16_t *w, const float *bias, co
     return launch_gemm_bf16_ex(a, w, bias, aux, out, m, n, k, epilogue, tokens, GemmExtra{}, stream);
 }
 
-int launch_gemm_bf16_ex(const uint16_t *a, const uint16_t *w, const float *bias, const float *aux, void *out, int64_t m,
-                        int n, int k, int epilogue, int tokens, const GemmExtra &ex, hipStream_t stream) {
-    VSC_REQUIRE(a && w && out, "gemm: null operand");
+// the switches that steer the choice of kernel (gemm_plan.h), as they stand now: diagnostic, read per launch -- in one pass over the
+// option table, which costs a small launch less than the three look-ups its path used to make.  abl: VSC_GEMM_ABL, for the kernels
+static GemmSwitches gemm_switches(int *abl = nullptr) {
+    static const VscOpt which[] = {OPT_GEMM_V1, OPT_GEMM_CFG, OPT_GEMM_V3, OPT_GEMM_V4, OPT_GEMM_V4_GRID, OPT_GEMM_GROUP_N,
+                                   OPT_GEMM_SKEW_NS_PER_K, OPT_GEMM_LN_TAIL, OPT_GEMM_LN_V4, OPT_GEMM_ABL};
+    const char *v[10];
+    vsc_opt_read(which, 10, v);
+    GemmSwitches sw;
+    sw.v1 = v[0] != nullptr;
+    sw.cfg_set = v[1] != nullptr;
+    sw.cfg = v[1] ? v[1][0] : 0;
+    sw.v3_off = v[2] && v[2][0] == '0';
+    sw.v4_off = v[3] && v[3][0] == '0';
+    sw.v4_grid_set = v[4] != nullptr;
+    sw.v4_grid = v[4] ? atoi(v[4]) : 0;
+    sw.group_n_set = v[5] != nullptr;
+    sw.group_n = v[5] ? atoi(v[5]) : 0;
+    sw.skew_ns_per_k = v[6] ? atoi(v[6]) : 0;
+    sw.ln_tail = v[7] && v[7][0] == '1';
+    sw.ln_v4 = v[8] ? v[8][0] : 0;
+    if (abl) *abl = v[9] ? atoi(v[9]) : 0;
+    return sw;
+}
+
+// the refusals of a shape, shared by the launch and by the query of its plan
+static int gemm_check_shape(int64_t m, int n, int k) {
     VSC_REQUIRE(m > 0 && n > 0 && k > 0, "gemm: empty problem m=%lld n=%d k=%d", (long long)m, n, k);
     VSC_REQUIRE(k % BK == 0, "gemm: K=%d must be a multiple of %d", k, BK);
     VSC_REQUIRE(n % 4 == 0, "gemm: N=%d must be a multiple of 4", n);
     const int64_t tiles_m = (m + BM - 1) / BM;
     const int tiles_n = (n + BN - 1) / BN;
     VSC_REQUIRE(tiles_m * tiles_n < (1ll << 31), "gemm: grid too large");
-    GemmArgs p{a, w, bias, aux, out, m, n, k, tokens, tiles_n, (int)tiles_m, 1, 0};
-    p.abl = vsc_opt_int(OPT_GEMM_ABL, 0);
+    return VSC_OK;
+}
+
+// the plan of launch_gemm_bf16_ex on the current device, with the switches as they stand
+static int gemm_plan_now(int64_t m, int n, int k, int epilogue, const GemmExtra &ex, GemmPlan *pl, int *abl = nullptr) {
+    const GemmSwitches sw = gemm_switches(abl);
+    int cus = 0;   // (not asked for where the plan does not depend on it: gemm_plan.h)
+    if (gemmplan::gemm_256_row_family(m, n, k, epilogue, sw)) VSC_TRY(vsc_device_cus(&cus));
+    *pl = gemmplan::gemm_plan(m, n, k, epilogue, ex.slices != nullptr, ex.nslices, cus, sw);
+    return VSC_OK;
+}
+
+// debug entry (include/vsc_hip.h): the plan vsc_gemm_bf16 would execute now; launches nothing
+extern "C" int vsc_gemm_plan(int64_t m, int32_t n, int32_t k, int32_t epilogue, int32_t out[8]) {
+    VSC_REQUIRE(out, "gemm_plan: null output");
+    VSC_REQUIRE(epilogue >= VSC_EPI_BF16 && epilogue <= VSC_EPI_F32, "gemm: unknown epilogue %d", epilogue);
+    VSC_TRY(gemm_check_shape(m, n, k));
+    GemmPlan pl;
+    VSC_TRY(gemm_plan_now(m, n, k, epilogue, GemmExtra{}, &pl));
+    const int32_t v[8] = {pl.kernel, pl.tiles_m, pl.tiles_n, pl.group_n, (int32_t)pl.grid, pl.block, pl.lds_bytes, 0};
+    for (int i = 0; i < 8; ++i) out[i] = v[i];
+    return VSC_OK;
+}
+
+int launch_gemm_bf16_ex(const uint16_t *a, const uint16_t *w, const float *bias, const float *aux, void *out, int64_t m,
+                        int n, int k, int epilogue, int tokens, const GemmExtra &ex, hipStream_t stream) {
+    VSC_REQUIRE(a && w && out, "gemm: null operand");
+    VSC_TRY(gemm_check_shape(m, n, k));
+    GemmArgs p{a, w, bias, aux, out, m, n, k, tokens, 0, 0, 1, 0};
     p.ex = ex;
-    const bool force_v1 = vsc_opt(OPT_GEMM_V1) != nullptr;
-    const bool force_v2 = vsc_opt(OPT_GEMM_CFG) != nullptr;
-    // A launch that cannot put a 256-row tile on at least half the CUs runs the 128 x 128 kernel instead (four times
-    // the workgroups, two per CU): at 8 frames (M = 1576) fc2 takes 44 instead of 74 us and proj 16 instead of 27,
-    // at 32 frames the N = 768 GEMMs 26 / 57 instead of 35 / 77 us; from ~130 tiles up the big tile wins.
-    const int64_t big_tiles = ((m + 255) / 256) * ((n + 255) / 256);
-    const bool fills = big_tiles > (k <= 512 ? 64 : 128);
     const bool fused = epilogue >= VSC_EPI_LNF_BF16;  // LayerNorm-folding kinds exist in the 256-row kernels only
     if (fused) {
         VSC_REQUIRE(n % 64 == 0 && k % 32 == 0, "gemm: LayerNorm-folding epilogue needs N %% 64 == 0 (N=%d)", n);
@@ -1860,7 +1844,6 @@ int launch_gemm_bf16_ex(const uint16_t *a, const uint16_t *w, const float *bias,
             VSC_REQUIRE(ex.rowstats && ex.colsum && bias && (!ex.slices || (ex.nslices * 64 == k && ex.eps > 0.f)),
                         "gemm: LNF needs rowstats, colsum and the folded bias (and K / 64 slices + eps when given partials)");
     }
-    const bool v2 = fused || (!force_v1 && m >= 1024 && k % 32 == 0 && n % 8 == 0 && (fills || force_v2));
     if (epilogue == VSC_EPI_RESADD_F32) VSC_REQUIRE(aux, "gemm: RESADD needs the residual pointer");
     if (epilogue == VSC_EPI_PATCH_F32) {
         VSC_REQUIRE(aux && tokens > 1, "gemm: PATCH needs pos and tokens");
@@ -1868,55 +1851,24 @@ int launch_gemm_bf16_ex(const uint16_t *a, const uint16_t *w, const float *bias,
                     (long long)m, tokens - 1);
         VSC_REQUIRE(m / (tokens - 1) * tokens < (1ll << 31), "gemm: PATCH output rows exceed 2^31");
     }
-    if (v2) {
-        switch (epilogue) {
-            case VSC_EPI_BF16: return launch_v2_pick<VSC_EPI_BF16>(p, stream);
-            case VSC_EPI_GELU_BF16: return launch_v2_pick<VSC_EPI_GELU_BF16>(p, stream);
-            case VSC_EPI_QGELU_BF16: return launch_v2_pick<VSC_EPI_QGELU_BF16>(p, stream);
-            case VSC_EPI_RESADD_F32: return launch_v2_pick<VSC_EPI_RESADD_F32>(p, stream);
-            case VSC_EPI_PATCH_F32: return launch_v2_pick<VSC_EPI_PATCH_F32>(p, stream);
-            case VSC_EPI_F32: return launch_v2_pick<VSC_EPI_F32>(p, stream);
-            case VSC_EPI_LNF_BF16: return p.k % 64 == 0 ? launch_v34<VSC_EPI_LNF_BF16>(p, stream) : launch_v2<VSC_EPI_LNF_BF16, 2, 4, 8, 4, 4>(p, stream);
-            case VSC_EPI_LNF_GELU_BF16: return p.k % 64 == 0 ? launch_v34<VSC_EPI_LNF_GELU_BF16>(p, stream) : launch_v2<VSC_EPI_LNF_GELU_BF16, 2, 4, 8, 4, 4>(p, stream);
-            case VSC_EPI_LNF_QGELU_BF16: return p.k % 64 == 0 ? launch_v34<VSC_EPI_LNF_QGELU_BF16>(p, stream) : launch_v2<VSC_EPI_LNF_QGELU_BF16, 2, 4, 8, 4, 4>(p, stream);
-            case VSC_EPI_RESADD_STATS_F32: return p.k % 64 == 0 ? launch_v34<VSC_EPI_RESADD_STATS_F32>(p, stream) : launch_v2<VSC_EPI_RESADD_STATS_F32, 2, 4, 8, 4, 4>(p, stream);
-            default: VSC_REQUIRE(false, "gemm: unknown epilogue %d", epilogue);
-        }
-    }
-    switch (epilogue) {
-        case VSC_EPI_BF16: return launch_t<VSC_EPI_BF16>(p, (int)tiles_m, stream);
-        case VSC_EPI_GELU_BF16: return launch_t<VSC_EPI_GELU_BF16>(p, (int)tiles_m, stream);
-        case VSC_EPI_QGELU_BF16: return launch_t<VSC_EPI_QGELU_BF16>(p, (int)tiles_m, stream);
-        case VSC_EPI_RESADD_F32: return launch_t<VSC_EPI_RESADD_F32>(p, (int)tiles_m, stream);
-        case VSC_EPI_PATCH_F32: return launch_t<VSC_EPI_PATCH_F32>(p, (int)tiles_m, stream);
-        case VSC_EPI_F32: return launch_t<VSC_EPI_F32>(p, (int)tiles_m, stream);
-        default: VSC_REQUIRE(false, "gemm: unknown epilogue %d", epilogue);
-    }
-    return VSC_OK;
+    GemmPlan pl;
+    VSC_TRY(gemm_plan_now(m, n, k, epilogue, ex, &pl, &p.abl));
+    // (the 256-row family first: the kernels stand in the code object in the order they are named here)
+    if (pl.kernel != gemmplan::V1) return with_epilogue(epilogue, [&](auto e) { return launch_256<decltype(e)::value>(p, pl, stream); });
+    return with_epilogue(epilogue, [&](auto e) { return launch_v1<decltype(e)::value>(p, pl, stream); });
 }
 
 
 // ---- residual GEMM + LayerNorm: one persistent launch with the LayerNorm as its tail, or today's two launches ----------------------
-// The tail form needs what makes launch_gemm_bf16 pick the persistent kernel for this shape (no diagnostic switch that routes it
-// elsewhere), N = 768 as one N-group, and whole row blocks per XCD range: total % 8 == 0 and (total / 8) % tiles_n == 0, i.e.
-// tiles_m % 8 == 0 (see ln_tail_arrive).
-bool gemm_resadd_ln_tail_eligible(int64_t m, int n, int k) {
-    // OPT-IN (VSC_GEMM_LN_TAIL=1): measured on the MI355X the tail costs ~98 us a launch where the LayerNorm launch it replaces takes
-    // 55 -- one lane -6 %, two lanes inside the run-to-run spread
-    if (!vsc_opt_is(OPT_GEMM_LN_TAIL, '1') || vsc_opt_is(OPT_GEMM_V4, '0') || vsc_opt_is(OPT_GEMM_V3, '0') || vsc_opt(OPT_GEMM_V1) ||
-        vsc_opt(OPT_GEMM_CFG) || vsc_opt(OPT_GEMM_V4_GRID))
-        return false;
-    if (n != 768 || k <= 512 || k % 128 != 0 || m < 1024) return false;
+// (when the tail form exists: gemm_resadd_ln_plan, gemm_plan.h)
+static GemmPlan resadd_ln_plan_now(int64_t m, int n, int k) {   // (on the current device, with the switches as they stand)
+    if (!vsc_opt_is(OPT_GEMM_LN_TAIL, '1')) return GemmPlan{};   // (opt-in: the usual answer, before anything else is read)
+    const GemmSwitches sw = gemm_switches();
     int cus = 0;
-    if (vsc_device_cus(&cus) != VSC_OK) return false;
-    GemmArgs p{};
-    p.m = m;
-    p.n = n;
-    p.k = k;
-    p.tiles_m = (int)((m + 255) / 256);
-    p.tiles_n = n / 256;
-    return p.tiles_m % 8 == 0 && v4_shape_ok(p, cus, false);
+    if (vsc_device_cus(&cus) != VSC_OK) return GemmPlan{};
+    return gemmplan::gemm_resadd_ln_plan(m, n, k, cus, sw);
 }
+bool gemm_resadd_ln_tail_eligible(int64_t m, int n, int k) { return resadd_ln_plan_now(m, n, k).ln_tail; }
 size_t gemm_ln_tail_ws_bytes(int64_t m) {
     const int64_t tiles_m = (m + 255) / 256;
     return (size_t)(tiles_m + 8 * ((tiles_m / 8 + 31) / 32) + 8) * 4;
@@ -1928,10 +1880,9 @@ int launch_gemm_resadd_ln_bf16(const uint16_t *a, const uint16_t *w, const float
                                uint16_t *y, int64_t m, int n, int k, float eps, unsigned *tail_ws, hipStream_t stream) {
     VSC_REQUIRE(a && w && x && gamma && beta && y, "gemm_resadd_ln: null operand");
     VSC_REQUIRE(m > 0 && n > 0 && k > 0, "gemm_resadd_ln: empty problem m=%lld n=%d k=%d", (long long)m, n, k);
-    if (tail_ws && gemm_resadd_ln_tail_eligible(m, n, k)) {
-        int cus = 0;
-        VSC_TRY(vsc_device_cus(&cus));
-        GemmArgs p{a, w, bias, x, x, m, n, k, 0, n / 256, (int)((m + 255) / 256), 1, 0};
+    const GemmPlan pl = tail_ws ? resadd_ln_plan_now(m, n, k) : GemmPlan{};
+    if (pl.ln_tail) {
+        GemmArgs p{a, w, bias, x, x, m, n, k, 0, 0, 0, 1, 0};
         p.abl = vsc_opt_int(OPT_GEMM_ABL, 0);
         p.ex.gamma = gamma;
         p.ex.beta = beta;
@@ -1939,7 +1890,7 @@ int launch_gemm_resadd_ln_bf16(const uint16_t *a, const uint16_t *w, const float
         p.ex.ln_out = y;
         p.ex.tail_ws = tail_ws;
         g_resadd_ln_last_path.store(1, std::memory_order_relaxed);
-        return launch_v4<VSC_EPI_RESADD_LN_F32>(p, cus, stream);
+        return launch_v4<VSC_EPI_RESADD_LN_F32>(p, pl, stream);
     }
     g_resadd_ln_last_path.store(2, std::memory_order_relaxed);
     VSC_TRY(launch_gemm_bf16(a, w, bias, x, x, m, n, k, VSC_EPI_RESADD_F32, 0, stream));
@@ -2020,65 +1971,48 @@ int launch_gemm_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias,
                                    a != xb_out && m % ((int64_t)(merge_res / 2) * (merge_res / 2)) == 0),
                 "gemm_ln: merge gather needs a power-of-two map (%d), channels %% 32 (%d), k = 4 c and an output outside the input", merge_res, merge_c);
     VSC_REQUIRE(m > 0 && k > 0 && k % 32 == 0, "gemm_ln: m=%lld k=%d (k must be a multiple of 32)", (long long)m, k);
-    // Widths 256 / 512 with more 256 x 256 tiles than CUs: the persistent kernel (v4 K loop, ring streaming across tiles)
-    // with the LN_RES write-out -- the row-owning 128 x 512 tile below stages 25 % more operand bytes per MFMA on the
-    // BK = 32 loop and pays a prologue per tile.  N = 512 needs whole tile pairs per XCD range (tiles_m % 8 == 0).
-    {
-        const int64_t tiles_m = (m + 255) / 256;
-        const int tiles_n = n / 256;
-        int dev = 0, cus = 0;
-        VSC_TRY(vsc_device_cus(&cus, &dev));
-        const bool shape_ok = (n == 256 || (n == 512 && tiles_m % 8 == 0)) && k % 128 == 0 && k >= 128 && k <= 3072 && cus == 256 &&
-                              tiles_m * tiles_n > cus && tiles_m * 256 * k * 2 < (1ll << 32) && tiles_m * 256 * n * 4 < (1ll << 32) &&
-                              dev >= 0 && dev < VSC_MAX_DEVICES;   // (dev_ws below)
-        // Where it pays (tools/micro/gemm_ln_ab.py, 256 Swin-V2-B frames; round 4, with the write-out on buffer operations and no
-        // spill left): N = 512 from K = 512 on -- s2 proj 96 vs 100 us, s2 fc2 166 vs 195, the un-gathered merge shape 114 vs
-        // 128; at N = 256 the short-K launch ties (s1 proj 168 vs 168: bound by its bytes whichever kernel runs it) and stays
-        // on the row-owning tile.  VSC_GEMM_LN_V4=1 forces the persistent kernel on every shape it supports (tests), 0
-        // switches it off.
-        const bool pays = n == 512 && k >= 512;
-        if (shape_ok && merge_res == 0 && !vsc_opt_is(OPT_GEMM_LN_V4, '0') && (pays || vsc_opt_is(OPT_GEMM_LN_V4, '1'))) {
-            static void *dev_ws[VSC_MAX_DEVICES] = {};   // callers without a workspace of their own: one call at a time per device
-            if (!pair_ws) {
-                if (!dev_ws[dev]) VSC_CHECK_HIP(hipMalloc(&dev_ws[dev], VSC_GEMM_LN_WS_BYTES));
-                pair_ws = dev_ws[dev];
-            }
-            GemmArgs p{a, w, bias, x_in, x_out, m, n, k, 0, tiles_n, (int)tiles_m, 1, 0};
-            p.abl = 0;
-            p.ex.xb = xb_out;
-            p.ex.gamma = gamma;
-            p.ex.beta = beta;
-            p.ex.eps = eps;
-            p.ex.xch = (float *)pair_ws;
-            p.ex.xflags = (int *)((char *)pair_ws + 2 * 256 * 256 * 2 * 4);
-            int grid = cus;
-            const int g = vsc_opt_int(OPT_GEMM_V4_GRID, 0);   // diagnostic, as in launch_v34
-            if (g >= 16 && g <= cus && g % 16 == 0 && tiles_m * tiles_n >= g) grid = g;
-            if (tiles_n == 2) {
-                // The epoch lives on the host and is baked into the kernel arguments: a captured launch replayed from a HIP graph would
-                // wait for flag values of the capture, not of the replay -- refuse stream capture (common.h: the workspace contract).
-                hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-                VSC_CHECK_HIP(hipStreamIsCapturing(stream, &cap));
-                VSC_REQUIRE(cap == hipStreamCaptureStatusNone, "gemm_ln (N = 512 pair exchange): not capturable into a HIP graph (per-launch epoch)");
-                // the flags of a workspace count up from launch to launch (zeroed once, when the workspace is first seen): no memset
-                // node between the GEMMs of a block.  One launch advances them by its tiles per workgroup.
-                std::lock_guard<std::mutex> lock(g_ln_ws_mutex);
-                auto it = g_ln_ws_epoch.find(pair_ws);
-                if (it == g_ln_ws_epoch.end()) {
-                    VSC_CHECK_HIP(hipMemsetAsync(p.ex.xflags, 0, 256 * 2 * 4, stream));
-                    it = g_ln_ws_epoch.emplace(pair_ws, 0).first;
-                }
-                p.ex.epoch = it->second;
-                const int per_wg = (int)((tiles_m * tiles_n + grid - 1) / grid);
-                it->second = (it->second + per_wg + 1) & 0x3fffffff;
-                if (it->second < p.ex.epoch) {   // wrapped (after ~10^8 launches): start over from zeroed flags
-                    VSC_CHECK_HIP(hipMemsetAsync(p.ex.xflags, 0, 256 * 2 * 4, stream));
-                    p.ex.epoch = 0;
-                    it->second = per_wg + 1;
-                }
-            }
-            return launch_v4<VSC_EPI_LN_RES_F32>(p, grid, stream);
+    int dev = 0, cus = 0;
+    VSC_TRY(vsc_device_cus(&cus, &dev));
+    // (the persistent kernel with the LN_RES write-out, or the row-owning tile: gemm_ln_plan, gemm_plan.h)
+    const GemmPlan pl = gemmplan::gemm_ln_plan(m, n, k, merge_res, cus, dev >= 0 && dev < VSC_MAX_DEVICES /* dev_ws below */, gemm_switches());
+    if (pl.kernel == gemmplan::V4) {
+        static void *dev_ws[VSC_MAX_DEVICES] = {};   // callers without a workspace of their own: one call at a time per device
+        if (!pair_ws) {
+            if (!dev_ws[dev]) VSC_CHECK_HIP(hipMalloc(&dev_ws[dev], VSC_GEMM_LN_WS_BYTES));
+            pair_ws = dev_ws[dev];
         }
+        GemmArgs p{a, w, bias, x_in, x_out, m, n, k, 0, 0, 0, 1, 0};
+        p.abl = 0;
+        p.ex.xb = xb_out;
+        p.ex.gamma = gamma;
+        p.ex.beta = beta;
+        p.ex.eps = eps;
+        p.ex.xch = (float *)pair_ws;
+        p.ex.xflags = (int *)((char *)pair_ws + 2 * 256 * 256 * 2 * 4);
+        if (pl.tiles_n == 2) {
+            // The epoch lives on the host and is baked into the kernel arguments: a captured launch replayed from a HIP graph would
+            // wait for flag values of the capture, not of the replay -- refuse stream capture (common.h: the workspace contract).
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            VSC_CHECK_HIP(hipStreamIsCapturing(stream, &cap));
+            VSC_REQUIRE(cap == hipStreamCaptureStatusNone, "gemm_ln (N = 512 pair exchange): not capturable into a HIP graph (per-launch epoch)");
+            // the flags of a workspace count up from launch to launch (zeroed once, when the workspace is first seen): no memset
+            // node between the GEMMs of a block.  One launch advances them by its tiles per workgroup.
+            std::lock_guard<std::mutex> lock(g_ln_ws_mutex);
+            auto it = g_ln_ws_epoch.find(pair_ws);
+            if (it == g_ln_ws_epoch.end()) {
+                VSC_CHECK_HIP(hipMemsetAsync(p.ex.xflags, 0, 256 * 2 * 4, stream));
+                it = g_ln_ws_epoch.emplace(pair_ws, 0).first;
+            }
+            p.ex.epoch = it->second;
+            const int per_wg = (int)(((int64_t)pl.tiles_m * pl.tiles_n + pl.grid - 1) / pl.grid);
+            it->second = (it->second + per_wg + 1) & 0x3fffffff;
+            if (it->second < p.ex.epoch) {   // wrapped (after ~10^8 launches): start over from zeroed flags
+                VSC_CHECK_HIP(hipMemsetAsync(p.ex.xflags, 0, 256 * 2 * 4, stream));
+                p.ex.epoch = 0;
+                it->second = per_wg + 1;
+            }
+        }
+        return launch_v4<VSC_EPI_LN_RES_F32>(p, pl, stream);
     }
     GemmLnArgs p{a, w, bias, gamma, beta, x_in, x_out, xb_out, m, n, k, eps};
     if (merge_res) {
@@ -2086,10 +2020,10 @@ int launch_gemm_ln_bf16(const uint16_t *a, const uint16_t *w, const float *bias,
         p.g_c = merge_c;
         for (int half = merge_res / 2; half > 1; half >>= 1) ++p.g_lh;
     }
-    switch (n) {
-        case 128: return launch_ln_t<8, 1, 4>(p, stream);  // 4 x 40 KiB = the whole 160 KiB: two tiles stay in flight across a barrier
-        case 256: return launch_ln_t<4, 2, 4>(p, stream);
-        case 512: return launch_ln_t<2, 4, 4>(p, stream);
+    switch (pl.kernel) {
+        case gemmplan::LN_ROW_128: return launch_ln_row<gemmplan::LN_ROW_128>(p, pl, stream);
+        case gemmplan::LN_ROW_256: return launch_ln_row<gemmplan::LN_ROW_256>(p, pl, stream);
+        case gemmplan::LN_ROW_512: return launch_ln_row<gemmplan::LN_ROW_512>(p, pl, stream);
         default: VSC_REQUIRE(false, "gemm_ln: N=%d unsupported (row-owning tiles exist for 128, 256, 512)", n);
     }
     return VSC_OK;

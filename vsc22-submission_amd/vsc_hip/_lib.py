@@ -211,6 +211,7 @@ SIGNATURES = {
     "vsc_score_norm_bias_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_float, c_void_p, c_void_p]),
     "vsc_gemm_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                 c_int32, c_int32, c_int32, c_void_p]),
+    "vsc_gemm_plan": (c_int32, [c_int64, c_int32, c_int32, c_int32, c_void_p]),
     "vsc_gemm_resadd_ln_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                           c_int32, c_float, c_void_p]),
     "vsc_gemm_resadd_ln_last_path": (c_int32, []),

@@ -66,6 +66,21 @@ def gemm_bf16(a, w, bias=None, *, epilogue=_lib.EPI_BF16, aux=None, tokens=0, ou
     return out
 
 
+GEMM_KERNELS = ("V1", "V2_A", "V2_B", "V2_C", "V2_D", "V3", "V4")
+
+
+def gemm_plan(m: int, n: int, k: int, epilogue=_lib.EPI_BF16) -> dict:
+    """the plan gemm_bf16 would execute for this shape now (csrc/gemm_plan.h): kernel (a name of GEMM_KERNELS), tiles_m, tiles_n,
+    group_n, grid, block, lds_bytes.  Launches nothing."""
+    import ctypes
+    out = (ctypes.c_int32 * 8)()
+    check(_rd().vsc_gemm_plan(m, n, k, epilogue, out))
+    keys = ("kernel", "tiles_m", "tiles_n", "group_n", "grid", "block", "lds_bytes")
+    plan = dict(zip(keys, out[:7]))
+    plan["kernel"] = GEMM_KERNELS[plan["kernel"]]
+    return plan
+
+
 def attention_bf16(qkv, frames: int, tokens: int, heads: int):
     lib = _rd()
     qkv = _dev(qkv, lp_dtype())
