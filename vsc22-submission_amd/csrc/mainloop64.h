@@ -316,7 +316,10 @@ __device__ __forceinline__ void bump(Ctx &c, uint32_t da, uint32_t dw) {
     }
 }
 
-// One output tile of a persistent sequence: nk K-tiles (even, >= 4).
+// One output tile of a persistent sequence: nk K-tiles (even, >= 2).  At nk = 2 (K = 128, which v4_shape_ok admits) the loop's one
+// iteration is the wrapping one: K-tile 0 stages its own tile's K-tile 1 (half 1, kt1 = 1, not yet bumped) and the next tile's units 0, 1
+// (half 0, bumped), K-tile 1 the next tile's units 2..5 -- the same six units in the same slots as the last pair of a longer tile;
+// with `nowait` K-tile 0 reads units 1..4, all of them among the six the previous tile_p (or prologue()) left landed.
 //   first  the ring holds units 0..5 from prologue(); otherwise the previous tile_p staged them, every wave has waited for
 //          its own pieces (vmcnt(0) in the write-out) and a workgroup barrier has passed since
 //   da/dw  byte distance from this tile's A / W origin to the next tile's (wrapping 32-bit adds); 0 / 0 behind the last
