@@ -484,6 +484,56 @@ int vsc_tn_align_f32(const float *sims_dev, int64_t sims_len, const int64_t *pai
                      int32_t max_step, int32_t top_k, int32_t max_path, double min_sim, int32_t min_length, double max_iou,
                      int32_t *boxes_dev, int32_t *counts_dev, float *maxsim_dev, void *stream);
 
+/* DP and HV temporal alignment -- VCSL's `dp` (with `njit_dp_matrix`, `find_path`, `cut_path`; VSC22-Descriptor-Track-1st/
+ * infer/vcsl/vta.py:98-127,153-241) and `hv` (:366-426) -- over the matrices of vsc_pair_similarity_f32, beside TN: one wave per
+ * pair, the pair list of a call in as few launches as the scratch cap allows.  A handle API: every call of a handle enqueues on
+ * the stream given at create.  sims_dev / sims_len / pairs_host [n_pairs][3] / bias are vsc_tn_align_f32's; every element is used
+ * as s + bias (fp32 add).  Outputs (device), TN's layout: boxes_dev int32 [n_pairs][max_boxes][4] = {q from, r from, q to, r to}
+ * in acceptance order (unused slots 0); counts_dev int32 [n_pairs] = the number FOUND, which may exceed max_boxes (only the first
+ * max_boxes are stored); maxsim_dev float [n_pairs][max_boxes] = max of (s + bias) over the half-open box [q from:q to,
+ * r from:r to], minus bias in fp32, -inf when that extent is empty (HV, on a one-cell diagonal); unused slots 0.
+ *
+ * vsc_align_dp_f32 -- contract (the reference's text run undecorated under numpy 2 scalar rules: everything float32; under
+ * numba's typing the two half-weight candidates and the min_sim comparison are float64, which agrees wherever rounding does not
+ * decide).  sim = (s + bias) + 1.0f.
+ *   matrix: dp = sim, acc = 0, bt = -1.  For i, j >= 1 in row-major dependency order the candidates are {dp[i-1,j-1] + sim[i,j],
+ *     dp[i-1,j] + 0.5f * sim[i,j], dp[i,j-1] + 0.5f * sim[i,j]}, each rounded to fp32; the FIRST maximum wins, k its index.  If
+ *     sim[i,j] < float32(min_sim): acc[i,j] = acc[prev_k] + 1.  If acc[i,j] <= discontinue: bt[i,j] = k, dp[i,j] = value_k;
+ *     otherwise the cell keeps dp = sim, bt = -1 and its acc.
+ *   rounds (exactly 100 at most): take the cell of the first maximum of dp in row-major order, stop all rounds if it is -inf;
+ *     walk bt back until bt == -1 or until the next cell's dp is -inf (that cell is not appended); path = the walk reversed;
+ *     dp[r1:r2+1, c1:c2+1] = -inf over the path's first and last cell; cut_path(path, diagonal_thres): the maximal runs of steps
+ *     that keep the row index, and those that keep the column index, covering more than diagonal_thres path cells are
+ *     discarded, the ranges [s, e) between consecutive discarded ranges (from 0, up to len(path)) are kept -- a run of one kind
+ *     followed at once by one of the other shares a cell with it and gives s > e --; keep the ranges with e - s > min_length;
+ *     mean = numpy's float32 np.mean of sim along the sub-path (pairwise sum, one fp32 division by the count); emit
+ *     [q0, r0, q1, r1] of the sub-path's ends if mean > float32(ave_sim) and both extents > min_length.
+ * vsc_align_hv_f32 -- contract; max_boxes = max_peaks.
+ *   s' = s + bias, cells with s' < float32(min_sim) become 0.  A diagonal sigma = r - q is a peak if it holds a cell
+ *   >= float32(min_sim) after zeroing; its extent is q in [max(-sigma, 0), min(max(R - sigma, 0), Q)); its score is numpy's
+ *   float32 pairwise np.sum of the WHOLE diagonal.  Peaks in descending score, stable (ties in ascending sigma), the first
+ *   max_peaks of them, those with score <= 0 skipped; box = the diagonal's whole extent [a, a + sigma, e - 1, e - 1 + sigma];
+ *   accepted unless the IoU ("+1" integer areas, float64 division, vsc_tn_align_f32's; 0 with no box yet) against an accepted box
+ *   is > iou_thresh.  (The reference holds the accepted corners in float32 arrays: areas above 2^24 cells round there, not here.)
+ * A pair with an empty side yields no boxes.  Non-finite similarities are outside the contracts.
+ * Limits (refused by name): q_rows, r_rows <= 65536; q_rows * r_rows <= 2^26; 0 <= discontinue <= 254 (acc is kept as a saturating
+ * 8-bit count, which is exact for these: acc only feeds `<= discontinue` and `+ 1`); min_length, diagonal_thres >= 0;
+ * 1 <= max_boxes, max_peaks <= 4096.  Scratch: two of the search path's grow-only per-device buffers (callers on one device are
+ * ordered; vsc_search_release_scratch frees them): 6 bytes per cell + 16 per row + 8 per column (DP), 5 bytes per diagonal (HV), each
+ * pair's rounded up to 16, for the pairs of a launch; a launch takes pairs while they fit the handle's cap (default 256 MiB) and always at least one.
+ * vsc_align_scratch sets the cap (cap_bytes > 0; 0 keeps it) and reports the launches and the arena bytes of the handle's last
+ * call (either pointer may be null).  The entries synchronise the stream once (to upload the pair table). */
+typedef struct vsc_align vsc_align;
+int vsc_align_create(void *stream, vsc_align **out);   /* every call of the handle enqueues on this stream */
+void vsc_align_destroy(vsc_align *h);
+int vsc_align_scratch(vsc_align *h, int64_t cap_bytes, int64_t *last_launches, int64_t *scratch_bytes);
+int vsc_align_dp_f32(vsc_align *h, const float *sims_dev, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias,
+                     int32_t discontinue, double min_sim, double ave_sim, int32_t min_length, int32_t diagonal_thres,
+                     int32_t max_boxes, int32_t *boxes_dev, int32_t *counts_dev, float *maxsim_dev);
+int vsc_align_hv_f32(vsc_align *h, const float *sims_dev, int64_t sims_len, const int64_t *pairs_host, int64_t n_pairs, float bias,
+                     double min_sim, double iou_thresh, int32_t max_peaks, int32_t *boxes_dev, int32_t *counts_dev,
+                     float *maxsim_dev);
+
 /* Matching-track localisation -- the reference's generate_matching_result (VSC22-Matching-Track-1st/infer/src/utils.py:76-117:
  * threshold, cv2.connectedComponentsWithStats, one sklearn RANSACRegressor fit per component group) -- over the refinement
  * networks' probability maps, one workgroup per (map, threshold) item, all items of a call in one launch.

@@ -36,5 +36,6 @@ enum SearchScratchSlot {
     SCRATCH_L2_DIST = 47,                                 // direct path: one materialised [rows, nr] chunk of distance bits
     SCRATCH_L2_COUNTS = 48, SCRATCH_L2_SLIMS = 49,        // range: hits per query row; the sweep's CSR offsets
     SCRATCH_L2_QAUG2 = 50,                                // the augmented queries of the wider probe
+    SCRATCH_ALIGN_TABLE = 51, SCRATCH_ALIGN_ARENA = 52,   // vta_align.hip: pair table; the per-pair state of one launch
     SCRATCH_SLOTS
 };

@@ -10,7 +10,8 @@ Class names, constructor arguments and the `localize` / `localize_all` / `score`
     graph search), imported late exactly as the reference does (:44) -- or any object with `forward_sim` passed as
     `model=`, such as `vsc_hip.alignment.TnAlignment`.  The `HipTN*` classes need no VCSL: similarity, TN alignment and
     MaxSim stay on the device (one pair-similarity launch and one `vsc_tn_align_f32` launch per `localize_all` call), and
-    only boxes and scores come back; they return what `VCSL*(..., model=TnAlignment(...))` returns.
+    only boxes and scores come back; they return what `VCSL*(..., model=TnAlignment(...))` returns.  The `HipVCSL*` classes
+    are the same with `VCSLLocalization`'s `model_type` argument: TN, DP or HV on the device (`vsc_hip.alignment.build_alignment`).
 """
 from __future__ import annotations
 
@@ -188,6 +189,55 @@ class HipTNLocalizationMaxSim(HipTNLocalization):
 
 
 class HipTNLocalizationCandidateScore(HipTNLocalization):
+    """`VCSLLocalizationCandidateScore` on the device: score = the candidate's own score."""
+
+    def score(self, candidate, maxsim):
+        return candidate.score
+
+
+class HipVCSLLocalization(HipTNLocalization):
+    """`VCSLLocalization(queries, refs, model_type, ...)` on the device for the models `vsc_hip.alignment.build_alignment`
+    holds (TN, DP, HV): `HipTNLocalization`'s launches with the model's own alignment kernel.  Returns what
+    `VCSLLocalization(..., model=<that model>)` returns."""
+
+    def __init__(self, queries, refs, model_type, similarity_bias=0.0, **kwargs):
+        from vsc_hip.alignment import build_alignment
+        LocalizationWithMetadata.__init__(self, queries, refs)
+        self.model = build_alignment(model_type, **kwargs)
+        self.similarity_bias = similarity_bias
+
+    def _align(self, candidates):
+        boxes, counts, maxsim = super()._align(candidates)
+        if hasattr(self.model, "max_boxes"):       # DP: the boxes found may outnumber the slots
+            from vsc_hip.alignment import check_counts
+            check_counts(counts, self.model.max_boxes, [f"{c.query_id}-{c.ref_id}" for c in candidates])
+        return boxes, counts, maxsim
+
+
+class HipVCSLLocalizationMaxSim(HipVCSLLocalization):
+    """`VCSLLocalizationMaxSim` on the device.  A box whose half-open extent is empty (HV: a one-cell diagonal) has no
+    similarity to take the maximum of: ValueError, as the reference's `.max()` of an empty slice."""
+
+    def localize_all(self, candidates):
+        candidates = list(candidates)
+        if not candidates:
+            return []
+        boxes, counts, maxsim = self._align(candidates)
+        found: List[Match] = []
+        for i, candidate in enumerate(candidates):
+            for j in range(counts[i]):
+                box = tuple(int(v) for v in boxes[i, j])
+                if box[2] <= box[0] or box[3] <= box[1]:
+                    raise ValueError(f"pair {candidate.query_id}-{candidate.ref_id}: box {box} has an empty half-open extent, "
+                                     f"MaxSim is undefined on it")
+                found.append(self._match(candidate, box, maxsim[i, j]))
+        return found
+
+    def score(self, candidate, maxsim):
+        return maxsim
+
+
+class HipVCSLLocalizationCandidateScore(HipVCSLLocalization):
     """`VCSLLocalizationCandidateScore` on the device: score = the candidate's own score."""
 
     def score(self, candidate, maxsim):

@@ -7,8 +7,9 @@ On the HIP path: optional score normalisation, the exhaustive candidate search
 descriptor-track micro-AP (:219-224).  `localize_and_verify` (:107-152) follows: the per-candidate similarity matrices
 come from one HIP launch per batch (vsc.baseline.localization).  With `--alignment vcsl` (the default) the temporal
 alignment is the reference's own CPU code, and without its VCSL package only candidates.csv is written (in the
-reference's format) and matches.csv is skipped with a log line; with `--alignment hip` the TN alignment and MaxSim run on
-the device (vsc_tn_align_f32) and matches.csv is written without VCSL.
+reference's format) and matches.csv is skipped with a log line; with `--alignment hip` the alignment and MaxSim run on
+the device (vsc_tn_align_f32, or vsc_align_dp_f32 / vsc_align_hv_f32 with `--alignment_model DP` / `HV`) and matches.csv is
+written without VCSL.
 """
 from __future__ import annotations
 
@@ -37,6 +38,7 @@ def search(queries: List[VideoFeature], refs: List[VideoFeature], retrieve_per_q
 
 
 ALIGNMENTS = ("vcsl", "hip")
+ALIGNMENT_MODELS = ("TN", "DP", "HV")
 CANDIDATES = ("host", "hip")
 SCORE_NORMS = ("host", "hip")
 SEGMENT_METRICS = ("none", "hip")
@@ -45,31 +47,42 @@ UAPS = ("host", "hip")
 
 def localize_and_verify(queries: List[VideoFeature], refs: List[VideoFeature], candidates: List[CandidatePair],
                         localize_per_query: float = 5.0, score_normalization: bool = False, model=None,
-                        alignment: str = "vcsl") -> List[Match]:
+                        alignment: str = "vcsl", alignment_model: str = "TN") -> List[Match]:
     """sscd_baseline.py:107-152: the best `localize_per_query * len(queries)` candidates, aligned in batches of 512.
-    alignment="vcsl": the reference's VCSL TN model (or `model=`); "hip": the same TN alignment on the device
-    (vsc_tn_align_f32), no VCSL needed."""
+    alignment="vcsl": the reference's VCSL model (or `model=`); "hip": the same alignment on the device (vsc_tn_align_f32 /
+    vsc_align_dp_f32 / vsc_align_hv_f32), no VCSL needed.  alignment_model: VCSL's model_type, "TN" (the reference's choice),
+    "DP" or "HV"; DP and HV get the bias and min_length of the TN call and otherwise their model's defaults."""
     from vsc.baseline.localization import VCSLLocalizationCandidateScore, VCSLLocalizationMaxSim
     if alignment not in ALIGNMENTS:
         raise ValueError(f"alignment {alignment!r}: one of {ALIGNMENTS}")
+    if alignment_model not in ALIGNMENT_MODELS:
+        raise ValueError(f"alignment_model {alignment_model!r}: one of {ALIGNMENT_MODELS}")
+    options = {"TN": dict(tn_max_step=5, min_length=4), "DP": dict(min_length=4), "HV": dict()}[alignment_model]
     candidates = candidates[: int(len(queries) * localize_per_query)]
     if alignment == "hip":
         if model is not None:
             raise ValueError("model= selects a VCSL-interface model; alignment='hip' runs its own kernel")
-        from vsc.baseline.localization import HipTNLocalizationCandidateScore, HipTNLocalizationMaxSim
+        from vsc.baseline.localization import (HipTNLocalizationCandidateScore, HipTNLocalizationMaxSim,
+                                               HipVCSLLocalizationCandidateScore, HipVCSLLocalizationMaxSim)
         if score_normalization:
-            aligner = HipTNLocalizationMaxSim(queries, refs, similarity_bias=0.5, tn_max_step=5, min_length=4)
+            if alignment_model == "TN":
+                aligner = HipTNLocalizationMaxSim(queries, refs, similarity_bias=0.5, **options)
+            else:
+                aligner = HipVCSLLocalizationMaxSim(queries, refs, alignment_model, similarity_bias=0.5, **options)
         else:
             from vsc.baseline.score_normalization import normalize_videos
-            aligner = HipTNLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), tn_max_step=5,
-                                                      min_length=4)
+            if alignment_model == "TN":
+                aligner = HipTNLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), **options)
+            else:
+                aligner = HipVCSLLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), alignment_model,
+                                                            **options)
     elif score_normalization:
-        aligner = VCSLLocalizationMaxSim(queries, refs, model_type="TN", tn_max_step=5, min_length=4, concurrency=16,
-                                         similarity_bias=0.5, model=model)
+        aligner = VCSLLocalizationMaxSim(queries, refs, model_type=alignment_model, concurrency=16, similarity_bias=0.5,
+                                         model=model, **options)
     else:
         from vsc.baseline.score_normalization import normalize_videos      # row-wise, a block of videos per device round trip
-        aligner = VCSLLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), model_type="TN",
-                                                 tn_max_step=5, min_length=4, concurrency=16, model=model)
+        aligner = VCSLLocalizationCandidateScore(normalize_videos(queries), normalize_videos(refs), model_type=alignment_model,
+                                                 concurrency=16, model=model, **options)
     matches: List[Match] = []
     logger.info("Aligning %s candidate pairs", len(candidates))
     for i in range(0, len(candidates), 512):
@@ -106,7 +119,8 @@ def main(args) -> None:
     logger.info("Candidates: %s", candidate_file)
     try:
         matches = localize_and_verify(queries, refs, candidates, score_normalization=bool(args.score_norm_features),
-                                      alignment=args.alignment)
+                                      alignment=args.alignment,
+                                      alignment_model=getattr(args, "alignment_model", "TN"))   # (namespaces from before the option)
     except ImportError as exc:
         matches_file = None
         logger.warning("matches.csv not written: %s", exc)
@@ -145,6 +159,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--alignment", choices=ALIGNMENTS, default="vcsl",
                     help="temporal alignment of matches.csv: the reference's VCSL package (vcsl) or the HIP kernel (hip)")
+    ap.add_argument("--alignment_model", choices=ALIGNMENT_MODELS, default="TN",
+                    help="the alignment model (VCSL's model_type): temporal network (TN, the reference's choice), dynamic programming "
+                         "(DP) or Hough voting (HV); with --alignment hip on the device, with --alignment vcsl handed to VCSL")
     ap.add_argument("--candidates", choices=CANDIDATES, default="host",
                     help="global top-k selection and video-pair grouping of candidates.csv: on the host (host) or in HIP (hip)")
     ap.add_argument("--score_norm", choices=SCORE_NORMS, default="host",

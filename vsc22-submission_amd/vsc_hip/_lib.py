@@ -142,6 +142,13 @@ SIGNATURES = {
     "vsc_uap_destroy": (None, [c_void_p]),
     "vsc_uap_rank_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "vsc_uap_curve_f64": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "vsc_align_create": (c_int32, [c_void_p, POINTER(c_void_p)]),
+    "vsc_align_destroy": (None, [c_void_p]),
+    "vsc_align_scratch": (c_int32, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_int64)]),
+    "vsc_align_dp_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, ctypes.c_float, c_int32, ctypes.c_double,
+                                   ctypes.c_double, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "vsc_align_hv_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, ctypes.c_float, ctypes.c_double, ctypes.c_double,
+                                   c_int32, c_void_p, c_void_p, c_void_p]),
     "vsc_frame_filter_create": (c_int32, [c_void_p, POINTER(c_void_p)]),
     "vsc_frame_filter_destroy": (None, [c_void_p]),
     "vsc_frame_filter_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_void_p]),

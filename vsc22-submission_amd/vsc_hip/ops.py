@@ -496,6 +496,80 @@ def tn_align(sims, pairs, bias: float, max_step: int, top_k: int, max_path: int,
     return boxes, counts, maxsim
 
 
+class AlignHandle:
+    """The device handle of the DP / HV alignments (vsc_align_*): bound to the stream that is current when it is made (or to
+    `stream`); owns no device memory.  `scratch(cap_bytes)` sets the scratch cap of a launch (0 keeps it) and returns
+    (launches, arena bytes) of the handle's last call."""
+
+    def __init__(self, lib=None, stream=None):
+        import ctypes
+        self._lib = lib or _rd()
+        handle = ctypes.c_void_p()
+        check(self._lib.vsc_align_create(stream if stream is not None else current_stream(), ctypes.byref(handle)))
+        self._h = handle
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.vsc_align_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def scratch(self, cap_bytes: int = 0):
+        import ctypes
+        launches, used = ctypes.c_int64(), ctypes.c_int64()
+        check(self._lib.vsc_align_scratch(self._h, int(cap_bytes), ctypes.byref(launches), ctypes.byref(used)))
+        return launches.value, used.value
+
+
+def _align_call(entry: str, sims, pairs, slots: int, args, handle):
+    import numpy as np
+    slots = int(slots)
+    if not 1 <= slots <= 4096:          # the library refuses it by name too; here before the outputs are sized by it
+        raise ValueError(f"{entry}: {slots} box slots per pair outside [1, 4096]")
+    sims = _dev(sims, torch.float32).reshape(-1)
+    pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int64).reshape(-1, 3))
+    n = pairs.shape[0]
+    boxes = torch.empty((n, slots, 4), dtype=torch.int32, device=sims.device)
+    counts = torch.empty(n, dtype=torch.int32, device=sims.device)
+    maxsim = torch.empty((n, slots), dtype=torch.float32, device=sims.device)
+    own = handle is None
+    h = AlignHandle() if own else handle
+    try:
+        check(getattr(h._lib, entry)(h._h, ptr(sims) if sims.numel() else None, sims.numel(), pairs.ctypes.data, n, *args, slots,
+                                     ptr(boxes), ptr(counts), ptr(maxsim)))
+    finally:
+        if own:
+            h.close()
+    return boxes, counts, maxsim
+
+
+def dp_align(sims, pairs, bias: float, discontinue: int, min_sim: float, ave_sim: float, min_length: int, diagonal_thres: int,
+             max_boxes: int = 100, handle: AlignHandle = None):
+    """DP alignment (VCSL `dp`) of every matrix of a flat fp32 device tensor; `sims`, `pairs`, `bias` as in tn_align.
+    -> (boxes int32 [n, max_boxes, 4], counts int32 [n], maxsim float32 [n, max_boxes]) on the device: counts[p] is the
+    number of boxes FOUND for pair p, of which the first max_boxes are stored, in the reference's order.  `handle`: an
+    AlignHandle (its stream, its scratch cap); None makes one on the current stream for the call.  Contract and limits:
+    vsc_align_dp_f32 in include/vsc_hip.h."""
+    return _align_call("vsc_align_dp_f32", sims, pairs, max_boxes,
+                       (float(bias), int(discontinue), float(min_sim), float(ave_sim), int(min_length), int(diagonal_thres)), handle)
+
+
+def hv_align(sims, pairs, bias: float, min_sim: float, iou_thresh: float, max_peaks: int, handle: AlignHandle = None):
+    """HV alignment (VCSL `hv`) of every matrix of a flat fp32 device tensor; `sims`, `pairs`, `bias` as in tn_align.
+    -> (boxes int32 [n, max_peaks, 4], counts int32 [n] <= max_peaks, maxsim float32 [n, max_peaks]) on the device; maxsim
+    is -inf for a box with an empty half-open extent (a one-cell diagonal).  Contract and limits: vsc_align_hv_f32 in
+    include/vsc_hip.h."""
+    return _align_call("vsc_align_hv_f32", sims, pairs, max_peaks, (float(bias), float(min_sim), float(iou_thresh)), handle)
+
+
 def match_segments(maps, items, thresholds, std_ratios, max_segments: int = 8):
     """Connected components + RANSAC localisation of every probability map of a flat fp32 device tensor at every threshold,
     one launch.  maps: flat float32 device tensor; items: int64 [n, 3] rows (element offset, h, w) on the host; thresholds /
