@@ -1092,6 +1092,19 @@ int vsc_gemm_resadd_ln_last_path(void);
 int vsc_attention_bf16(const uint16_t *qkv_dev, uint16_t *out_dev, int32_t frames, int32_t tokens,
                        int32_t heads, void *stream);
 
+/* The same attention, same layouts and alignment, at any token count 1 .. VSC_ATTENTION_STREAM_MAX_TOKENS: K and V are streamed in
+ * blocks of VSC_ATTENTION_STREAM_KEY_BLOCK keys with an online softmax whose row maximum is taken exactly at every block (the
+ * accumulated context and row sum are multiplied by exp2(m_old - m_new) once per block); probabilities are rounded to the operand
+ * type and the row sum is the sum of the rounded values, so the context is an exact weighted mean of V rows.  vsc_attention_bf16
+ * (whole score rows in registers, <= 320 tokens) rounds in another order: the two agree within the operand type's rounding, not bit
+ * for bit.  The stream is the FIRST argument.  Refused before anything is launched: tokens outside the range, frames or heads < 1,
+ * frames * heads * ceil(tokens / 128) >= 2^31, a null or misaligned pointer.  The encoder uses it above 320 tokens, or everywhere
+ * with vsc_set_option("VSC_ATTN_LONG", "1"). */
+#define VSC_ATTENTION_STREAM_KEY_BLOCK 128
+#define VSC_ATTENTION_STREAM_MAX_TOKENS 16384
+int vsc_attention_stream_bf16(void *stream, const uint16_t *qkv_dev, uint16_t *out_dev, int32_t frames, int32_t tokens,
+                              int32_t heads);
+
 /* Row LayerNorm over `width` of float32 x [rows,width]; out is bf16 (out_f32 = 0)
  * or float32 (out_f32 = 1; may alias x).  Alignment: x_dev, gamma_dev, beta_dev 16 bytes; out_dev 16 (float32) or 8 (bf16). */
 int vsc_layernorm_f32(const float *x_dev, const float *gamma_dev, const float *beta_dev,

@@ -143,6 +143,13 @@ extern "C" int vsc_attention_bf16(const uint16_t *qkv, uint16_t *out, int32_t fr
     return launch_attention_bf16(qkv, out, frames, tokens, heads, (hipStream_t)stream);
 }
 
+extern "C" int vsc_attention_stream_bf16(void *stream, const uint16_t *qkv, uint16_t *out, int32_t frames, int32_t tokens,
+                                         int32_t heads) {
+    VSC_REQUIRE_ALIGNED("attention_stream", qkv, 16);
+    VSC_REQUIRE_ALIGNED("attention_stream", out, 16);
+    return launch_attention_stream_bf16(qkv, out, frames, tokens, heads, (hipStream_t)stream);
+}
+
 extern "C" int vsc_layernorm_f32(const float *x, const float *g, const float *b, void *out,
                                  int64_t rows, int32_t width, float eps, int32_t out_f32,
                                  void *stream) {

@@ -55,7 +55,7 @@ void vsc_set_error(const char *fmt, ...);
 // Every switch that used to be an environment lookup on the launch path.  The environment is read ONCE per process (first use of any
 // switch); afterwards a switch changes only through vsc_set_option() (include/vsc_hip.h).  vsc_opt() is an array read.
 #define VSC_OPT_LIST(X)                                                                                                  \
-    X(ATTN_SKEW) X(ATTN_ABL) X(ATTN_NI) X(ATTN_DMA) X(CONV_IMPLICIT) X(CONV_DIRECT) X(CONV_REMAP) X(CONV_PERSIST) X(CONV_STAGES) X(CONV_WAVES) X(CONV_NARROW_MAX) X(CONV_NARROW_NT) X(CONV_EXPAND) X(DWCONV_SMALL) X(CONV_STEM) X(CONV_STREAM_MIN_COUT) X(CONV_X3)      \
+    X(ATTN_SKEW) X(ATTN_ABL) X(ATTN_NI) X(ATTN_DMA) X(ATTN_LONG) X(CONV_IMPLICIT) X(CONV_DIRECT) X(CONV_REMAP) X(CONV_PERSIST) X(CONV_STAGES) X(CONV_WAVES) X(CONV_NARROW_MAX) X(CONV_NARROW_NT) X(CONV_EXPAND) X(DWCONV_SMALL) X(CONV_STEM) X(CONV_STREAM_MIN_COUT) X(CONV_X3)      \
     X(GEMM_GROUP_N) X(GEMM_V4_SKEW) X(GEMM_TIMING_PRINT) X(GEMM_V4) X(GEMM_V4_GRID) X(GEMM_SKEW_NS_PER_K) X(GEMM_CFG)    \
     X(GEMM_V3) X(GEMM_ABL) X(GEMM_V1) X(KNN_TRIG) X(KNN_ABL) X(KNN_PATH) X(KNN_XCD_MAP) X(KNN_DELTA) X(KNN_TAIL) X(RANGE_PATH) X(PAIRMAX_PATH) X(L2_PATH) X(L2_WIDE) X(WATTN_ABL)      \
     X(SWIN_SPLIT_LN) X(SWIN_SPLIT_K) X(GEMM_LN_V4) X(SWIN_FUSED_MLP) X(SWIN_MLP512) X(SWIN_PROJ512) X(SWIN_QKV512) X(SWIN_MLP512_GRID) X(SWIN_FUSED_PROJ) X(SWIN_MLP_ABL) X(SWIN_MLP_SEQ) X(SWIN_MLP_NW4) X(SWIN_FUSED_MERGE) X(SWIN_ROW_MAX) X(LN_LIGHT) X(WATTN_STREAM) X(GEMM_LN_TAIL) X(JPEG_STAGES)
@@ -268,6 +268,9 @@ int launch_ln_stats_merge(const float *stats, float *rowstats, int64_t rows, int
                           hipStream_t stream);
 int launch_attention_bf16(const uint16_t *qkv, uint16_t *out, int frames, int tokens, int heads,
                           hipStream_t stream);
+// attention_stream.hip: the same layouts at 1 .. VSC_ATTENTION_STREAM_MAX_TOKENS tokens (key blocks + online softmax)
+int launch_attention_stream_bf16(const uint16_t *qkv, uint16_t *out, int frames, int tokens, int heads,
+                                 hipStream_t stream);
 int launch_layernorm(const float *x, const float *g, const float *b, void *out, int64_t rows,
                      int width, float eps, int out_f32, hipStream_t stream);
 int launch_patchify(const float *frames, uint16_t *patches, int64_t n, int channels, int image,

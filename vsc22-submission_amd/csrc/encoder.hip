@@ -106,7 +106,9 @@ extern "C" int vsc_encoder_create(const vsc_encoder_config *cfg, vsc_encoder **o
                 "encoder: the SSCD head needs GeM pooling and a Linear output");
     int g = c.image_size / c.patch_size;
     int tokens = g * g + 1;
-    VSC_REQUIRE(tokens <= 320, "encoder: %d tokens > 320 (attention kernel limit)", tokens);
+    // up to 320 tokens attention.hip (a whole score row in registers), above that attention_stream.hip (key blocks)
+    VSC_REQUIRE(tokens <= VSC_ATTENTION_STREAM_MAX_TOKENS, "encoder: %d tokens > %d (attention kernel limit)", tokens,
+                VSC_ATTENTION_STREAM_MAX_TOKENS);
 
     vsc_encoder *e = new vsc_encoder();
     e->cfg = c;
@@ -254,6 +256,7 @@ static int encoder_run_chunks(vsc_encoder *e, const float *frames, const uint8_t
     const int D = c.width, T = e->tokens;
     const int act_epi = c.act == 0 ? VSC_EPI_GELU_BF16 : VSC_EPI_QGELU_BF16;
     const int64_t frame_elems = (int64_t)c.channels * c.image_size * c.image_size;
+    const bool attn_long = T > 320 || vsc_opt_is(OPT_ATTN_LONG, '1');
     int chunk = 0;
     for (int64_t off = 0; off < n; off += c.max_batch, ++chunk) {
         const int lane = fork ? (chunk & 1) : 0;
@@ -308,7 +311,11 @@ static int encoder_run_chunks(vsc_encoder *e, const float *frames, const uint8_t
                 if (!y_ready) { ProfScope _ps(e, VSC_PROF_LAYERNORM, st); VSC_TRY(launch_layernorm(w.x, L.ln1_g, L.ln1_b, w.y, M, D, c.ln_eps, 0, st)); }
                 { ProfScope _ps(e, VSC_PROF_GEMM_QKV, st); VSC_TRY(launch_gemm_bf16(w.y, L.qkv_w, L.qkv_b, nullptr, w.qkv, M, 3 * D, D, VSC_EPI_BF16, 0, st)); }
             }
-            { ProfScope _ps(e, VSC_PROF_ATTENTION, st); VSC_TRY(launch_attention_bf16(w.qkv, w.y, (int)B, T, c.heads, st)); }
+            {   // the register-row kernel wherever it applies (<= 320 tokens); the streaming kernel above that, or everywhere with VSC_ATTN_LONG=1
+                ProfScope _ps(e, VSC_PROF_ATTENTION, st);
+                if (attn_long) VSC_TRY(launch_attention_stream_bf16(w.qkv, w.y, (int)B, T, c.heads, st));
+                else VSC_TRY(launch_attention_bf16(w.qkv, w.y, (int)B, T, c.heads, st));
+            }
             if (fold) {
                 { ProfScope _ps(e, VSC_PROF_GEMM_PROJ, st); VSC_TRY(launch_gemm_bf16_ex(w.y, L.proj_w, L.proj_b, w.x, w.x, M, D, D, VSC_EPI_RESADD_STATS_F32, 0, emit, st)); }
                 take.colsum = L.fc1_cs;

@@ -21,6 +21,10 @@ PROF_CLASSES = ("patchify", "gemm_patch", "layernorm", "gemm_qkv", "attention", 
                 "gemm_fc1", "gemm_fc2", "pool_head", "misc")
 
 
+# mirrors of VSC_ATTENTION_STREAM_KEY_BLOCK / VSC_ATTENTION_STREAM_MAX_TOKENS in include/vsc_hip.h (vsc_attention_stream_bf16)
+ATTENTION_STREAM_KEY_BLOCK = 128
+ATTENTION_STREAM_MAX_TOKENS = 16384
+
 SWIN_PROF_CLASSES = 27
 SWIN_PROF_STAGE0, SWIN_PROF_PER_STAGE = 3, 6
 SWIN_PROF_KINDS = ("qkv", "attention", "proj_ln", "fc1", "fc2_ln", "merge")
@@ -223,6 +227,7 @@ SIGNATURES = {
                                           c_int32, c_float, c_void_p]),
     "vsc_gemm_resadd_ln_last_path": (c_int32, []),
     "vsc_attention_bf16": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "vsc_attention_stream_bf16": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32]),      # (stream first)
     "vsc_layernorm_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float,
                                     c_int32, c_void_p]),
     "vsc_patchify_bf16": (c_int32, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,

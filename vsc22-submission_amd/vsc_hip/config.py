@@ -11,6 +11,9 @@ Each preset names the reference backbone it stands for:
   (768->2048 Conv1d over tokens, GeM, Linear 2048->512: sscd.py:25-42,88-94).
 * ``clip_vit_l14_224`` -- the video-score CLIP tower
   (train/train_vid_score/video/clip.py:82-161, torch2scripts.py:7-9), CLS readout.
+* ``vit_b16_384`` / ``clip_vit_l14_336`` -- the same two classes at a larger input (577 tokens each): ``VIT`` with
+  ``image_size=384``, ``VisionTransformer(336, 14, 1024, 24, 16)``.  The reference ships no checkpoint of either; they are
+  the stronger siblings its own classes allow.  ``clip_vit_l14_336`` is an encoder only: the video-score gate stays at 224.
 """
 from __future__ import annotations
 
@@ -89,6 +92,19 @@ PRESETS = {
     "tiny_clip": EncoderConfig(name="tiny_clip", image_size=64, patch_size=16, width=128,
                                layers=2, heads=2, mlp_dim=512, out_dim=0, ln_eps=1e-5,
                                act="quick_gelu", pre_ln=True, patch_bias=False, pool="cls"),
+    # ---- more than 320 tokens: the streaming attention kernel (csrc/attention_stream.hip).  The same classes of the reference at a
+    # larger input: VIT is HF ViTModel with a free image_size (backbones/vit.py), VisionTransformer takes any input_resolution
+    # (train/train_vid_score/video/clip.py:89-109).  577 tokens each; the weight formats are unchanged, only the position table is longer.
+    "vit_b16_384": EncoderConfig(name="vit_b16_384", image_size=384),
+    "clip_vit_l14_336": EncoderConfig(name="clip_vit_l14_336", image_size=336, patch_size=14, width=1024,
+                                      layers=24, heads=16, mlp_dim=4096, out_dim=0,
+                                      ln_eps=1e-5, act="quick_gelu", pre_ln=True,
+                                      patch_bias=False, pool="cls"),
+    "tiny_long": EncoderConfig(name="tiny_long", image_size=384, patch_size=16, width=128, layers=2,
+                               heads=2, mlp_dim=512, out_dim=64),                                       # 577 tokens
+    "tiny_clip_long": EncoderConfig(name="tiny_clip_long", image_size=320, patch_size=16, width=128,   # 401 tokens
+                                    layers=2, heads=2, mlp_dim=512, out_dim=0, ln_eps=1e-5,
+                                    act="quick_gelu", pre_ln=True, patch_bias=False, pool="cls"),
 }
 
 

@@ -90,6 +90,17 @@ def attention_bf16(qkv, frames: int, tokens: int, heads: int):
     return out
 
 
+def attention_stream_bf16(qkv, frames: int, tokens: int, heads: int):
+    """attention_bf16 at any token count up to _lib.ATTENTION_STREAM_MAX_TOKENS: key blocks of _lib.ATTENTION_STREAM_KEY_BLOCK and
+    an online softmax (vsc_attention_stream_bf16)."""
+    lib = _rd()
+    qkv = _dev(qkv, lp_dtype())
+    assert qkv.shape == (frames * tokens, 3 * heads * 64)
+    out = torch.empty((frames * tokens, heads * 64), dtype=lp_dtype(), device=qkv.device)
+    check(lib.vsc_attention_stream_bf16(current_stream(), ptr(qkv), ptr(out), frames, tokens, heads))
+    return out
+
+
 def attention_f32(qkv, tokens: int, heads: int, head_dim: int, seqs: int = 1, row_offsets=None, out=None):
     """fp32 softmax(q k^T / sqrt(head_dim)) v of the video-score head; qkv [rows, 3 * heads * head_dim] float32 as q | k | v.
     `seqs` sequences of `tokens` rows back to back (vsc_attention_f32 / vsc_attention_f32_batch), or, with row_offsets (int32
